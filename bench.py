@@ -10,10 +10,14 @@ contiguous row shard; N > 1 adds one all-gather of the packed per-shard top-k (R
 The corpus is fixed (strong scaling: 10M rows total, sharded N ways) and already resident in HBM when the
 timed region starts; queries are device-resident f32.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes the last timed step's
+rows, scores and counts as DIR/*.npy (the inputs are the same bytes on every run with the same arguments).  Everything else the
+line can carry — CPU baseline, latencies, the other sections and, at N > 1, the checks against the oracle — needs `--full`.
+
 Extra objects on that line (task contract):
   roofline     — the scan kernel against the HBM roof: algorithmic bytes (rows x dim x 2 per launch)
                  / mean launch duration measured live with HIP events on the launch stream.
-  cpu_baseline — the oracle's AVX2+F16C restatement of the reference CPU path (kind "port"), timed on the
+  cpu_baseline — (--full) the oracle's AVX2+F16C restatement of the reference CPU path (kind "port"), timed on the
                  host cores of this box on a bounded sample of the same corpus, in the same run, and used as
                  the bit-exact parity checker for the GPU result on that sample.
 """
@@ -398,10 +402,28 @@ def adversarial_section(kind: str, rows: int, dim: int, k: int, device, local_ra
     return res
 
 
-def flatten_for_the_driver(line: dict) -> None:
+def dump_outputs(path: str, out) -> None:
+    """--dump-outputs: what a caller of the timed search receives from its last step, one .npy per array.  Row ids and counts are
+    int32 on the device and exact in float64 (padding rows stay -1); scores are the f32 bits themselves.  Beyond 64 MB in all, a
+    fixed seeded sample of the queries is written instead, with its query indices."""
+    os.makedirs(path, exist_ok=True)
+    rows, scores, counts = (t.cpu().numpy() for t in out)
+    per_query = rows[0].size * 8 + scores[0].size * 4 + 8
+    budget = (64 << 20) - 4096   # (room for the four .npy headers)
+    if rows.shape[0] * per_query > budget:
+        keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], budget // (per_query + 8), replace=False))
+        rows, scores, counts = rows[keep], scores[keep], counts[keep]
+        np.save(os.path.join(path, "query_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), scores.astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), counts.astype(np.float64))
+
+
+def flatten_for_the_driver(line: dict, kernel_resources: bool = True) -> None:
     """The driver's record of a bench line keeps the SCALAR fields of `roofline` (nested objects are dropped) and the tail of
     stdout: the north-star kernel's figures (the exact f16 scan against the HBM roof), the encoders' matrix-core fractions and the
-    main-pass kernel's register spill count are therefore repeated as scalars inside `roofline` and at the top level, in place."""
+    main-pass kernel's register spill count are therefore repeated as scalars inside `roofline` and at the top level, in place.
+    kernel_resources=False leaves out the register counts (read from the library's device code by a separate tool)."""
     roof = line.get("roofline") or {}
     flat = {}
     ex = roof.get("exact_f16_scan")
@@ -423,7 +445,7 @@ def flatten_for_the_driver(line: dict) -> None:
         flat["joint_frac"] = roof["joint"].get("frac")
     if isinstance(roof.get("hbm"), dict):
         flat["main_pass_hbm_frac"] = roof["hbm"].get("frac")
-    res = main_pass_kernel_resources()
+    res = main_pass_kernel_resources() if kernel_resources else None
     if res:
         flat["main_pass_vgpr_count"] = res.get("vgpr_count")
         flat["main_pass_vgpr_spill_count"] = res.get("vgpr_spill_count")
@@ -1237,7 +1259,18 @@ def main() -> None:
     ap.add_argument("--expect", type=str, default=None,
                     help="--sharded-handle: an .npz with the oracle's answers (rows, score bits) for the first queries of the pool, written by the "
                          "parent run: the handle's answers are compared with it (equals_oracle_8_queries)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: CPU baseline and parity, single-query latencies, "
+                         "the exact f16 scan and copy rate, adversarial corpora, encoders, host-pointer ABI, two-pass / MRL / two-tier "
+                         "sections, the main pass's register counts; N > 1: the other scaling form, the merged answer against the oracle "
+                         "and the sharded-handle leg.  Without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's rows, scores and counts to DIR/<name>.npy (float64, float32, float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.sharded_handle:
+        ap.error("--dump-outputs writes the headline search's answer; --sharded-handle has its own line")
     if args.strong and args.batch is None:
         args.batch = 1024 if not args.exact else 4
     args.batched = not args.exact
@@ -1393,8 +1426,11 @@ def main() -> None:
         elapsed = float(t.item())
 
     # ---- N > 1: what the collective really saw, the other scaling form, and the merged answer against the oracle ---------------------
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         multi = {}
         # (1) one more all-gather of one word per rank, counted on arrival: the number of DISTINCT ranks whose word came back — not WORLD_SIZE
         tag = torch.tensor([rank + 1], dtype=torch.int64, device=device)
@@ -1436,7 +1472,7 @@ def main() -> None:
 
     # single-query latency through the host-pointer boundary (H2D query, scan, merge, D2H hits, sync)
     lat = []
-    if world == 1:
+    if world == 1 and args.full:
         q1 = queries[:32].cpu().numpy()
         # fsgpu_search_topk as a host calls it: after the batched steps above the index holds the int8 copy of its slab, so a lone
         # query takes ONE certified pass over it + the exact re-score (rows and score bits of the exact kernels); then the exact
@@ -1585,7 +1621,7 @@ def main() -> None:
                     line["roofline"]["traffic_source"] = (f"profiles/{PROFILE_ROUND}/pmc_summary.json: rocprofv3 --pmc FETCH_SIZE of "
                                                           f"this command for {e['kernel'][:60]}, KiB x 1024 x 2 (gfx950 correction)")
                     break
-        if world == 1:
+        if world == 1 and args.full:
             line["roofline"]["measured_copy_GBps"] = measured_copy_gbps(device)
         if lat:
             line["p50_latency_ms_single_query"] = lat[len(lat) // 2]
@@ -1600,7 +1636,7 @@ def main() -> None:
                             "certified (every block's dropped rows lie below the threshold); uncertified queries take the staged path"}
         # the CPU baseline runs before the thousand-thread load test below: after it the container's CPU quota throttles the
         # oracle's workers for a while (measured: 120-150 GB/s instead of ~290 GB/s on the same 16 threads)
-        if args.batched and not args.exact:
+        if args.full and args.batched and not args.exact:
             # the north-star's HBM target in the same run: the exact f16 kernel, one query per pass over the f16 slab
             # (N > 1: over rank 0's shard — every rank streams its own shard at this rate)
             line["roofline"]["exact_f16_scan"] = exact_scan_roofline(index, queries, k, hi - lo, args.dim, device)
@@ -1615,7 +1651,7 @@ def main() -> None:
                         line["roofline"]["exact_f16_scan"]["traffic_source"] = (
                             f"profiles/{PROFILE_ROUND}/pmc_summary.json (run pmc_fetch_b1): rocprofv3 --pmc FETCH_SIZE, KiB x 1024 x 2 (gfx950 correction)")
                         break
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # N > 1: rank 0 times the port on ITS shard (the first rows of the same corpus) and scales to the full corpus
             line["cpu_baseline"] = cpu_baseline_and_parity(slab, queries, k, args.rows, fa.VectorIndex)
             if world > 1:
@@ -1677,17 +1713,17 @@ def main() -> None:
               except Exception as e:   # (the check must not cost the measured line; a failed check reads as "not equal")
                 line["merged_answer_vs_oracle"] = {"error": f"{type(e).__name__}: {e}"}
                 line["merged_answer_equals_oracle_8_queries"] = False
-        if world == 1 and not args.no_adversarial and args.rows >= 1_000_000 and args.batched:
+        if world == 1 and args.full and not args.no_adversarial and args.rows >= 1_000_000 and args.batched:
             line["adversarial_corpora"] = {kind: adversarial_section(kind, args.rows, args.dim, k, device, local_rank)
                                            for kind in ("uniform", "outlier")}
-        if world == 1 and not args.no_encoders:
+        if world == 1 and args.full and not args.no_encoders:
             line["encoders"] = encoder_section(device, local_rank)
         if world == 1 and args.config5:
             line["config5"] = config5_section(index, args.rows, k, local_rank)
-        if world == 1 and args.batched and not args.exact:
+        if world == 1 and args.full and args.batched and not args.exact:
             line["host_pointer_abi"] = host_pointer_section(index, k, queries, B)
             line["host_pointer_abi_queries_per_sec"] = line["host_pointer_abi"]["queries_per_sec"]
-        if world == 1 and not args.no_two_tier:
+        if world == 1 and args.full and not args.no_two_tier:
             line["int8_two_pass"] = quantized_section(index, args.rows, args.dim, k, queries, 8, 3)
             line["fourbit_two_pass"] = quantized_section(index, args.rows, args.dim, k, queries, 4, 5)
             line["mrl"] = mrl_section(index, args.rows, args.dim, k, queries)
@@ -1717,7 +1753,7 @@ def main() -> None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_sharded_handle:
+        if world > 1 and args.full and not args.no_sharded_handle:
             # the same search through ONE C-ABI handle (fsgpu_sharded_*: RCCL inside libfsgpu.so) and, over such handles, the
             # metric's second half — the two-tier flow (phase 0 + phase 1) and config 5 —, in a child process with a hard limit
             # once the ranks have left their GPUs: a problem there cannot cost the line above.  Under the gloo rehearsal the
@@ -1744,7 +1780,7 @@ def main() -> None:
                 os.unlink(args.expect)
             except OSError:
                 pass
-        flatten_for_the_driver(line)
+        flatten_for_the_driver(line, kernel_resources=args.full)
         # RCCL prints its version banner through C stdio, which sits in libc's buffer until exit when stdout is a pipe: push
         # it out first so that the JSON line is the last thing on stdout
         sys.stdout.flush()

@@ -7,7 +7,7 @@ python tests/fuzz_encoders.py 7 > $O/fuzz_enc.txt 2>&1; tail -1 $O/fuzz_enc.txt
 python scripts/fuzz_batched.py 43 100 > $O/fuzz_batched.txt 2>&1; tail -1 $O/fuzz_batched.txt
 python tests/fuzz_exact.py 11 > $O/fuzz_exact.txt 2>&1; tail -1 $O/fuzz_exact.txt
 python scripts/bench_encoders.py > $O/enc.txt 2>&1; grep -E "^(m2v|bert)" $O/enc.txt
-python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-adversarial > $O/bench_q.json 2>/dev/null
+python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-adversarial > $O/bench_q.json 2>/dev/null
 python bench.py --rows 50000000 --config5 --no-cpu-baseline --no-two-tier --no-adversarial --no-encoders 2>/dev/null | tail -1 > $O/bench_config5.json
 python - <<PY
 import json

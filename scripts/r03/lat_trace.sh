@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel trace of the single-query latency path at 1M rows: what the 0.18 ms consist of
 OUT=gpurun_out/lat1m; mkdir -p $OUT; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --rows 1000000 --exact --batch 1 --steps 50 --warmup 5 --no-cpu-baseline --no-two-tier --no-adversarial --no-encoders > $OUT/trace.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --full --rows 1000000 --exact --batch 1 --steps 50 --warmup 5 --no-cpu-baseline --no-two-tier --no-adversarial --no-encoders > $OUT/trace.json 2> $OUT/trace.err
 python - <<PY
 import csv, glob
 for f in glob.glob("$OUT/trace/**/*kernel_stats.csv", recursive=True):

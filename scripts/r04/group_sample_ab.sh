@@ -15,7 +15,7 @@ for off in "" 1 "" 1; do
 done
 } 2>&1 | tee $O/ab.txt
 cp /tmp/base.so frankensearch_amd/libfsgpu.so
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('adversarial', {k: (round(v['queries_per_sec']), v['refiltered_on_f16_queries'], v['exact_fallback_queries'], v['batched_equals_oracle_rows_and_bits']) for k, v in d['adversarial_corpora'].items()})" | tee $O/adversarial.txt
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('adversarial', {k: (round(v['queries_per_sec']), v['refiltered_on_f16_queries'], v['exact_fallback_queries'], v['batched_equals_oracle_rows_and_bits']) for k, v in d['adversarial_corpora'].items()})" | tee $O/adversarial.txt
 python scripts/r04/filtered_tput.py 2>&1 | tail -5 | tee $O/filtered.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-adversarial --no-encoders > $O/bench_traced.json 2> $O/trace.err
 head -10 $O/trace/*kernel_stats.csv | cut -c1-170 | tee $O/trace_head.txt

@@ -14,12 +14,12 @@ for v in base flags base; do
   echo "== $v 10M"; run ""; echo "== $v 1.25M"; run "--rows 1250000"
 done 2>&1 | tee $O/ab_flags.txt
 cp /tmp/base.so frankensearch_amd/libfsgpu.so
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 > $O/bench_adv.json
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 > $O/bench_adv.json
 python - <<PY
 import json
 d = json.loads(open("$O/bench_adv.json").read().strip().splitlines()[-1])
 for kname, a in d["adversarial_corpora"].items():
     print(kname, {x: a[x] for x in ("queries_per_sec", "int8_filter_active_after", "int8_filter_queries", "refiltered_on_f16_queries", "exact_fallback_queries", "batched_equals_oracle_rows_and_bits", "batched_equals_exact_kernels_64_queries")})
 PY
-( time FSGPU_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 10 --warmup 3 --config5-rows 6000000 ) > $O/rehearsal_gloo2.txt 2>&1; tail -c 3000 $O/rehearsal_gloo2.txt
+( time FSGPU_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 10 --warmup 3 --config5-rows 6000000 ) > $O/rehearsal_gloo2.txt 2>&1; tail -c 3000 $O/rehearsal_gloo2.txt
 ( time python -m pytest tests -m gpu -q -x ) > $O/pytest_all.txt 2>&1; tail -8 $O/pytest_all.txt

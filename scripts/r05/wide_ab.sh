@@ -28,4 +28,4 @@ for v in "$@"; do
 done | tee $O/wide_stamps.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-adversarial --no-encoders > $O/bench_traced.json 2> $O/trace.err
 head -12 $O/trace/*kernel_stats.csv | cut -c1-180 | tee $O/trace_head.txt
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('adversarial', json.dumps(d.get('adversarial_corpora'))[:1500])" | tee $O/adversarial.txt
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-two-tier --no-encoders 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('adversarial', json.dumps(d.get('adversarial_corpora'))[:1500])" | tee $O/adversarial.txt

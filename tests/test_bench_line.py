@@ -101,3 +101,35 @@ def test_the_n_rank_checks_of_the_bench_catch_a_wrong_answer_and_a_wrong_slab():
     corrupt = slab[1000:9000].copy()
     corrupt[4321, 7] ^= 1
     assert bench.slab_checksum(torch.from_numpy(corrupt.view(np.int16)), 1000) != want
+
+
+def test_dump_outputs_writes_the_last_step_as_float_arrays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: rows and counts exact in float64 (padding -1 kept), the f32 score bits unchanged; an answer past
+    64 MB is cut to a fixed seeded sample of queries whose indices are written next to it."""
+    import numpy as np
+    import torch
+    import bench
+
+    rows = torch.tensor([[5, 9_999_999, -1], [7, 0, 1]], dtype=torch.int32)
+    scores = torch.tensor([[0.5, 0.1, float("-inf")], [1.0, 0.0, -0.3]], dtype=torch.float32)
+    counts = torch.tensor([2, 3], dtype=torch.int32)
+    out = tmp_path / "small"
+    bench.dump_outputs(str(out), (rows, scores, counts))
+    assert sorted(p.name for p in out.iterdir()) == ["counts.npy", "rows.npy", "scores.npy"]
+    r, s, c = (np.load(out / f"{n}.npy") for n in ("rows", "scores", "counts"))
+    assert r.dtype == np.float64 and np.array_equal(r, rows.numpy())
+    assert s.dtype == np.float32 and np.array_equal(s.view(np.uint32), scores.numpy().view(np.uint32))
+    assert c.dtype == np.float64 and np.array_equal(c, counts.numpy())
+
+    n, k = 100_000, 64   # 100,000 x 64 x (8 + 4) bytes: past 64 MB
+    big = (torch.arange(n * k, dtype=torch.int32).reshape(n, k), torch.rand((n, k), generator=torch.Generator().manual_seed(1)),
+           torch.full((n,), k, dtype=torch.int32))
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), big)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["counts.npy", "query_index.npy", "rows.npy", "scores.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    keep = np.load(tmp_path / "a" / "query_index.npy").astype(np.int64)
+    assert np.array_equal(keep, np.load(tmp_path / "b" / "query_index.npy"))   # the same sample on every run
+    assert np.array_equal(np.load(tmp_path / "a" / "rows.npy"), big[0].numpy()[keep])
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), big[1].numpy()[keep])
