@@ -127,6 +127,10 @@ SIGNATURES = {
     "fsgpu_m2v_embed": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_bert_create": (_i32, [_i32, _vp, _vp, C.POINTER(_vp)]),
     "fsgpu_bert_create_safetensors": (_i32, [_i32, _vp, _u64, C.c_float, C.POINTER(_vp)]),
+    "fsgpu_bert_create_ex": (_i32, [_i32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "fsgpu_bert_create_safetensors_ex": (_i32, [_i32, _vp, _u64, C.c_float, _vp, C.POINTER(_vp)]),
+    "fsgpu_bert_linear_format": (_u32, [_vp]),
+    "fsgpu_lab_linear_int8_dynamic": (_i32, [_i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),

@@ -48,11 +48,12 @@ NativeEmbedder::~NativeEmbedder() {
     if (q_status_) (void)hipHostFree(q_status_);
     if (docs_io_) (void)hipHostFree(docs_io_);
     for (DeviceBuffer* b : {&word_, &pos_, &type_, &emb_ln_w_, &emb_ln_b_, &ids_, &positions_, &offsets_, &x_f32_, &x_h_,
-                            &qkv_f32_, &ctx_h_, &tmp_f32_, &inter_h_, &out_, &q_x_, &q_parts_, &q_stages_, &q_counter_, &docs_layers_, &docs_in_, &docs_out_})
+                            &qkv_f32_, &ctx_h_, &tmp_f32_, &inter_h_, &out_, &q_x_, &q_parts_, &q_stages_, &q_counter_, &docs_layers_, &docs_in_, &docs_out_,
+                            &qx_, &sx_, &inter_f32_})
         b->release();
     for (Layer& l : layers_)
         for (DeviceBuffer* b : {&l.qkv_w, &l.ao_w, &l.i_w, &l.o_w, &l.qkv_wp, &l.ao_wp, &l.i_wp, &l.o_wp, &l.qkv_b, &l.ao_b, &l.ln1_w, &l.ln1_b, &l.i_b, &l.o_b,
-                                &l.ln2_w, &l.ln2_b})
+                                &l.ln2_w, &l.ln2_b, &l.qkv_q, &l.ao_q, &l.i_q, &l.o_q, &l.qkv_s, &l.ao_s, &l.i_s, &l.o_s})
             b->release();
 }
 
@@ -79,13 +80,31 @@ SearchError NativeEmbedder::pack_weights(DeviceBuffer& dst, const DeviceBuffer& 
     return SearchError{};
 }
 
-SearchError NativeEmbedder::init(int device, const fsgpu_bert_config& cfg, const fsgpu_bert_weights& w) {
+// int8 mode (bert_int8.hip): W [N, K] f32 -> the per-output-channel codes in fragment order + their scales, quantised on the device
+SearchError NativeEmbedder::upload_i8(DeviceBuffer& q, DeviceBuffer& s, const float* src, int N, int K, DeviceBuffer& staging) {
+    if (!src) return err(FSGPU_ERR_NULL_ARGUMENT, "missing weight tensor");
+    BERT_TRY(staging.reserve((size_t)N * K * 4));
+    BERT_TRY(q.reserve(bert_i8_packed_bytes(N, K)));
+    BERT_TRY(s.reserve((size_t)N * 4));
+    BERT_HIP(hipMemcpy(staging.ptr, src, (size_t)N * K * 4, hipMemcpyHostToDevice));
+    BERT_HIP(launch_bert_i8_pack_w(static_cast<const float*>(staging.ptr), q.ptr, static_cast<float*>(s.ptr), N, K, nullptr));
+    BERT_HIP(hipDeviceSynchronize());   // (the staging buffer is refilled by the next tensor)
+    return SearchError{};
+}
+
+SearchError NativeEmbedder::init(int device, const fsgpu_bert_config& cfg, const fsgpu_bert_weights& w, uint32_t linear_format) {
     if (cfg.hidden == 0 || cfg.hidden % 128 != 0 || cfg.hidden > 1024)
         return err(FSGPU_ERR_INVALID_CONFIG, "hidden must be a multiple of 128 and <= 1024");
     if (cfg.heads * 32 != cfg.hidden) return err(FSGPU_ERR_INVALID_CONFIG, "head dimension must be 32");
     if (cfg.inter == 0 || cfg.inter % 128 != 0) return err(FSGPU_ERR_INVALID_CONFIG, "inter must be a multiple of 128");
     if (cfg.layers == 0 || cfg.vocab == 0 || cfg.max_pos == 0 || cfg.max_pos > 512)
         return err(FSGPU_ERR_INVALID_CONFIG, "layers/vocab must be non-zero and max_pos in 1..=512");
+    if (linear_format != FSGPU_BERT_LINEAR_F16 && linear_format != FSGPU_BERT_LINEAR_INT8_DYNAMIC)
+        return err(FSGPU_ERR_INVALID_CONFIG, "unknown linear format");
+    const bool int8 = linear_format == FSGPU_BERT_LINEAR_INT8_DYNAMIC;
+    if (int8 && !(bert_i8_gemm_supported(3 * (int)cfg.hidden, (int)cfg.hidden) && bert_i8_gemm_supported((int)cfg.inter, (int)cfg.hidden) &&
+                  bert_i8_gemm_supported((int)cfg.hidden, (int)cfg.inter)))
+        return err(FSGPU_ERR_INVALID_CONFIG, "int8 linears need hidden and inter to be multiples of 64");
     if (!w.layers) return err(FSGPU_ERR_NULL_ARGUMENT, "layer weights are null");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
@@ -94,6 +113,7 @@ SearchError NativeEmbedder::init(int device, const fsgpu_bert_config& cfg, const
     BERT_HIP(hipSetDevice(device));
     device_ = device;
     cfg_ = cfg;
+    int8_ = int8;
     {
         // The encoder is a chain of short kernels; a scan on another stream is a few long, chip-filling ones.  With equal
         // priority the chain queues behind every scan launch (two-tier load, 1,024 callers: 44 k -> 48 k queries/s and
@@ -125,15 +145,17 @@ SearchError NativeEmbedder::init(int device, const fsgpu_bert_config& cfg, const
         std::copy(lw.q_b, lw.q_b + H, sb.begin());
         std::copy(lw.k_b, lw.k_b + H, sb.begin() + H);
         std::copy(lw.v_b, lw.v_b + H, sb.begin() + 2 * H);
-        SearchError e = upload_f16(l.qkv_w, stacked.data(), stacked.size(), staging);
+        // int8 mode: the fused [3H, H] QKV linear is quantised per output channel as one matrix (native.rs:1546-1600); no f16 copies
+        SearchError e = int8 ? upload_i8(l.qkv_q, l.qkv_s, stacked.data(), (int)(3 * H), (int)H, staging)
+                             : upload_f16(l.qkv_w, stacked.data(), stacked.size(), staging);
         if (e.ok()) e = upload_f32(l.qkv_b, sb.data(), sb.size());
-        if (e.ok()) e = upload_f16(l.ao_w, lw.ao_w, H * H, staging);
+        if (e.ok()) e = int8 ? upload_i8(l.ao_q, l.ao_s, lw.ao_w, (int)H, (int)H, staging) : upload_f16(l.ao_w, lw.ao_w, H * H, staging);
         if (e.ok()) e = upload_f32(l.ao_b, lw.ao_b, H);
         if (e.ok()) e = upload_f32(l.ln1_w, lw.ln1_w, H);
         if (e.ok()) e = upload_f32(l.ln1_b, lw.ln1_b, H);
-        if (e.ok()) e = upload_f16(l.i_w, lw.i_w, I * H, staging);
+        if (e.ok()) e = int8 ? upload_i8(l.i_q, l.i_s, lw.i_w, (int)I, (int)H, staging) : upload_f16(l.i_w, lw.i_w, I * H, staging);
         if (e.ok()) e = upload_f32(l.i_b, lw.i_b, I);
-        if (e.ok()) e = upload_f16(l.o_w, lw.o_w, H * I, staging);
+        if (e.ok()) e = int8 ? upload_i8(l.o_q, l.o_s, lw.o_w, (int)H, (int)I, staging) : upload_f16(l.o_w, lw.o_w, H * I, staging);
         if (e.ok()) e = upload_f32(l.o_b, lw.o_b, H);
         if (e.ok()) e = upload_f32(l.ln2_w, lw.ln2_w, H);
         if (e.ok()) e = upload_f32(l.ln2_b, lw.ln2_b, H);
@@ -143,6 +165,7 @@ SearchError NativeEmbedder::init(int device, const fsgpu_bert_config& cfg, const
         }
     }
     staging.release();
+    if (int8) return SearchError{};   // (the f16 paths below — fragment-order copies, the one-launch table — are not used)
     // Fragment-order copies for the batch path (bert_gemm_w.hip): +2 bytes per weight (22 MB for MiniLM-L6).
     // FSGPU_BERT_GEMM_V1 keeps the LDS-tiled kernels of bert_kernels.hip (A/B runs).
     const int Hi = (int)H, Ii = (int)I;
@@ -194,6 +217,23 @@ void NativeEmbedder::drop_graphs() {
 SearchError NativeEmbedder::reserve_workspaces(uint32_t tokens) {
     const size_t H = cfg_.hidden, I = cfg_.inter;
     const size_t T = tokens <= kGraphMaxTokens ? kGraphMaxTokens : tokens;
+    if (int8_) {   // (int8 mode: no f16 activations but the attention's context)
+        const void* before[] = {x_f32_.ptr, qkv_f32_.ptr, ctx_h_.ptr, tmp_f32_.ptr, qx_.ptr, sx_.ptr, inter_f32_.ptr};
+        BERT_TRY(x_f32_.reserve(T * H * 4));
+        BERT_TRY(qkv_f32_.reserve(T * 3 * H * 4));
+        BERT_TRY(ctx_h_.reserve(T * H * 2));
+        BERT_TRY(tmp_f32_.reserve(T * H * 4));
+        BERT_TRY(qx_.reserve(T * (H > I ? H : I)));
+        BERT_TRY(sx_.reserve(T * 4));
+        BERT_TRY(inter_f32_.reserve(T * I * 4));
+        const void* after[] = {x_f32_.ptr, qkv_f32_.ptr, ctx_h_.ptr, tmp_f32_.ptr, qx_.ptr, sx_.ptr, inter_f32_.ptr};
+        for (int i = 0; i < 7; ++i)
+            if (before[i] && before[i] != after[i]) {
+                drop_graphs();
+                break;
+            }
+        return SearchError{};
+    }
     const void* before[] = {x_f32_.ptr, x_h_.ptr, qkv_f32_.ptr, ctx_h_.ptr, tmp_f32_.ptr, inter_h_.ptr};
     BERT_TRY(x_f32_.reserve(T * H * 4));
     BERT_TRY(x_h_.reserve(T * H * 2));
@@ -212,13 +252,13 @@ SearchError NativeEmbedder::reserve_workspaces(uint32_t tokens) {
 
 bool NativeEmbedder::query_path(uint32_t tokens) const {
     static const bool off = fsgpu::lab_env("FSGPU_BERT_NO_QUERY_PATH") != nullptr;  // A/B runs
-    return !off && tokens <= 32 && bert_query_path_supported((int)cfg_.hidden, (int)cfg_.inter, (int)cfg_.heads);
+    return !off && !int8_ && tokens <= 32 && bert_query_path_supported((int)cfg_.hidden, (int)cfg_.inter, (int)cfg_.heads);
 }
 
 bool NativeEmbedder::one_launch_path() const {
     // (measured slower than the replayed graph of 25 launches — bert_query_kernels.hip —: opt-in, experiments builds only)
     static const bool on = fsgpu::lab_env("FSGPU_BERT_ONE_LAUNCH") != nullptr;
-    return on && q_one_launch_ok_ && bert_q_one_launch_blocks() > 0;
+    return on && !int8_ && q_one_launch_ok_ && bert_q_one_launch_blocks() > 0;
 }
 
 // Query-sized inputs (<= 32 tokens in total): the 25 stages of bert_query_kernels.hip as 4 launches per layer + the pooling (replayed
@@ -398,9 +438,51 @@ SearchError NativeEmbedder::forward_packed_range(uint32_t d0, uint32_t d1, uint3
     return SearchError{};
 }
 
+// int8 mode: every batch shape takes this chain.  Per layer: QKV (one [3H, H] int8 linear) -> the f32-operand attention
+// (bert_kernels.hip) -> quantise the f16 context -> AO -> add + LN + quantise -> FFN-in + GELU -> quantise -> FFN-out -> add + LN
+// (+ quantise for the next layer).  Every kernel of it computes a row (a text, for the attention and the pooling) from that row alone.
+SearchError NativeEmbedder::forward_int8(uint32_t n_docs, uint32_t tokens, uint32_t max_seq) {
+    const int H = (int)cfg_.hidden, I = (int)cfg_.inter, T = (int)tokens;
+    const float eps = cfg_.ln_eps;
+    float* x = static_cast<float*>(x_f32_.ptr);
+    float* qkv = static_cast<float*>(qkv_f32_.ptr);
+    float* tmp = static_cast<float*>(tmp_f32_.ptr);
+    float* inter = static_cast<float*>(inter_f32_.ptr);
+    float* sx = static_cast<float*>(sx_.ptr);
+    void* qx = qx_.ptr;
+    const uint32_t* offs = static_cast<const uint32_t*>(offsets_.ptr);
+    BERT_HIP(launch_bert_i8_embed_ln_quant(static_cast<const int32_t*>(ids_.ptr), static_cast<const int32_t*>(positions_.ptr),
+                                           static_cast<const float*>(word_.ptr), static_cast<const float*>(pos_.ptr),
+                                           static_cast<const float*>(type_.ptr), static_cast<const float*>(emb_ln_w_.ptr),
+                                           static_cast<const float*>(emb_ln_b_.ptr), x, qx, sx, T, H, eps, stream_));
+    const float scale = 0.17677669f;  // ATTN_SCALE_F32 = 1/sqrt(32) (native.rs:44)
+    for (size_t li = 0; li < layers_.size(); ++li) {
+        Layer& l = layers_[li];
+        const bool last = li + 1 == layers_.size();
+        BERT_HIP(launch_bert_i8_gemm(qx, sx, l.qkv_q.ptr, static_cast<const float*>(l.qkv_s.ptr), static_cast<const float*>(l.qkv_b.ptr),
+                                     qkv, T, 3 * H, H, false, stream_));
+        BERT_HIP(launch_bert_attention(qkv, offs, ctx_h_.ptr, (int)n_docs, (int)cfg_.heads, H, (int)max_seq, scale, stream_));
+        BERT_HIP(launch_bert_i8_quant_rows_h(ctx_h_.ptr, qx, sx, T, H, stream_));
+        BERT_HIP(launch_bert_i8_gemm(qx, sx, l.ao_q.ptr, static_cast<const float*>(l.ao_s.ptr), static_cast<const float*>(l.ao_b.ptr), tmp,
+                                     T, H, H, false, stream_));
+        BERT_HIP(launch_bert_i8_add_ln_quant(x, tmp, static_cast<const float*>(l.ln1_w.ptr), static_cast<const float*>(l.ln1_b.ptr), qx, sx,
+                                             T, H, eps, stream_));
+        BERT_HIP(launch_bert_i8_gemm(qx, sx, l.i_q.ptr, static_cast<const float*>(l.i_s.ptr), static_cast<const float*>(l.i_b.ptr), inter,
+                                     T, I, H, true, stream_));
+        BERT_HIP(launch_bert_i8_quant_rows(inter, qx, sx, T, I, stream_));
+        BERT_HIP(launch_bert_i8_gemm(qx, sx, l.o_q.ptr, static_cast<const float*>(l.o_s.ptr), static_cast<const float*>(l.o_b.ptr), tmp,
+                                     T, H, I, false, stream_));
+        BERT_HIP(launch_bert_i8_add_ln_quant(x, tmp, static_cast<const float*>(l.ln2_w.ptr), static_cast<const float*>(l.ln2_b.ptr),
+                                             last ? nullptr : qx, sx, T, H, eps, stream_));
+    }
+    BERT_HIP(launch_bert_pool(x, offs, pooled_out_ ? pooled_out_ : static_cast<float*>(out_.ptr), (int)n_docs, H, stream_));
+    return SearchError{};
+}
+
 SearchError NativeEmbedder::forward(uint32_t n_docs, uint32_t tokens, uint32_t max_seq) {
     const int H = (int)cfg_.hidden, I = (int)cfg_.inter, T = (int)tokens;
     const float eps = cfg_.ln_eps;
+    if (int8_) return forward_int8(n_docs, tokens, max_seq);
     if (query_path(tokens)) return forward_query(n_docs, tokens);
     {
         static const bool ab = fsgpu::lab_env("FSGPU_BERT_SPLIT_AO") || fsgpu::lab_env("FSGPU_BERT_SPLIT_FFN");   // A/B runs below
@@ -510,7 +592,7 @@ bool NativeEmbedder::docs_path(uint32_t tokens, uint32_t max_seq) const {
         const char* e = fsgpu::lab_env("FSGPU_BERT_DOCS_MAX_TOKENS");
         return e ? std::atol(e) : (1L << 30);
     }();
-    return !off && docs_ready_ && tokens > 32 && max_seq <= 32 && (long)tokens <= max_tokens;
+    return !off && !int8_ && docs_ready_ && tokens > 32 && max_seq <= 32 && (long)tokens <= max_tokens;
 }
 
 // Every text at most 32 tokens long (a batch of queries): ONE launch for the whole forward (bert_docs_w.hip).  Consecutive texts

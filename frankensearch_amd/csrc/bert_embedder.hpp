@@ -17,29 +17,40 @@ namespace fsgpu {
 class NativeEmbedder {
   public:
     ~NativeEmbedder();
-    SearchError init(int device, const fsgpu_bert_config& cfg, const fsgpu_bert_weights& w);
+    // linear_format: FSGPU_BERT_LINEAR_F16 (f16 matrix-core linears) or FSGPU_BERT_LINEAR_INT8_DYNAMIC (bert_int8.hip: int8
+    // per-output-channel weights, per-row dynamic int8 activations — the arithmetic of the reference's native forward).
+    SearchError init(int device, const fsgpu_bert_config& cfg, const fsgpu_bert_weights& w,
+                     uint32_t linear_format = FSGPU_BERT_LINEAR_F16);
     // NativeEmbedder::load's weight contract: a safetensors blob in HuggingFace key layout (safetensors.cpp; parse_weights,
     // crates/frankensearch-rerank/src/native.rs:1359-1602).  device < 0 validates the blob only.
-    SearchError init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps);
+    SearchError init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps,
+                                 uint32_t linear_format = FSGPU_BERT_LINEAR_F16);
     // ids: concatenated token ids; text i owns ids[offsets[i]..offsets[i+1]).  out: [n, hidden] f32.
     // out_dev (on this embedder's device, may be null): the pooled vectors are left in device memory — the hand-off to a search that
     // takes device queries; out (may then be null): the host copy.  Either way the call returns when the forward has finished.
     SearchError embed_batch(const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out, float* out_dev = nullptr);
     uint32_t dimension() const { return cfg_.hidden; }
     int device() const { return device_; }
+    uint32_t linear_format() const { return int8_ ? FSGPU_BERT_LINEAR_INT8_DYNAMIC : FSGPU_BERT_LINEAR_F16; }
 
   private:
     struct Layer {
         DeviceBuffer qkv_w, ao_w, i_w, o_w;              // f16 [N,K]
         DeviceBuffer qkv_wp, ao_wp, i_wp, o_wp;          // the same weights in matrix-core fragment order (bert_gemm_w.hip)
         DeviceBuffer qkv_b, ao_b, ln1_w, ln1_b, i_b, o_b, ln2_w, ln2_b;  // f32
+        DeviceBuffer qkv_q, ao_q, i_q, o_q;              // int8 mode: fragment-order int8 codes (bert_i8_pack_w_kernel)
+        DeviceBuffer qkv_s, ao_s, i_s, o_s;              // int8 mode: f32 scale per output channel
     };
     SearchError upload_f32(DeviceBuffer& dst, const float* src, size_t n);
     SearchError upload_f16(DeviceBuffer& dst, const float* src, size_t n, DeviceBuffer& staging);
     SearchError pack_weights(DeviceBuffer& dst, const DeviceBuffer& src, int N, int K);
+    SearchError upload_i8(DeviceBuffer& q, DeviceBuffer& s, const float* src, int N, int K, DeviceBuffer& staging);
     SearchError forward(uint32_t n_docs, uint32_t tokens, uint32_t max_seq);
     // the fragment-order batch path over texts [d0, d1) = tokens [t0, t1) on `stream` (bert_gemm_w.hip)
     SearchError forward_packed_range(uint32_t d0, uint32_t d1, uint32_t t0, uint32_t t1, uint32_t max_seq, hipStream_t stream);
+    // int8 mode: ONE per-layer chain for every batch shape (bert_int8.hip + the f32-operand attention), so a text's vector has the
+    // same bits whatever batch it rides in
+    SearchError forward_int8(uint32_t n_docs, uint32_t tokens, uint32_t max_seq);
     SearchError forward_query(uint32_t n_docs, uint32_t tokens);   // <= 32 tokens: 25 launches (bert_query_kernels.hip)
     bool query_path(uint32_t tokens) const;
     bool one_launch_path() const;                                  // ... as ONE launch with grid-wide barriers (experiments builds)
@@ -56,6 +67,8 @@ class NativeEmbedder {
     std::vector<Layer> layers_;
     // workspaces
     DeviceBuffer ids_, positions_, offsets_, x_f32_, x_h_, qkv_f32_, ctx_h_, tmp_f32_, inter_h_, out_, q_x_, q_parts_;
+    bool int8_ = false;                 // FSGPU_BERT_LINEAR_INT8_DYNAMIC
+    DeviceBuffer qx_, sx_, inter_f32_;  // int8 mode: a linear's input codes [T, max(H, I)] and row scales [T]; the GELU output f32
     // pinned staging for small calls (see embed_batch)
     static constexpr size_t kPinnedIoBytes = 512 * 1024;
     void* io_host_ = nullptr;

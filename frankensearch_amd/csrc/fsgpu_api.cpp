@@ -1425,7 +1425,107 @@ fsgpu_status fsgpu_bert_create_safetensors(int32_t device, const void* blob, uin
     });
 }
 
+namespace {
+// fsgpu_bert_options: NULL = f16; a known format and zero reserved words, else FSGPU_ERR_INVALID_CONFIG
+fsgpu_status bert_linear_format(const fsgpu_bert_options* options, uint32_t* format) {
+    *format = FSGPU_BERT_LINEAR_F16;
+    if (!options) return FSGPU_OK;
+    for (uint32_t r : options->reserved)
+        if (r != 0) return fail(FSGPU_ERR_INVALID_CONFIG, "fsgpu_bert_options: reserved words must be 0");
+    if (options->linear_format != FSGPU_BERT_LINEAR_F16 && options->linear_format != FSGPU_BERT_LINEAR_INT8_DYNAMIC)
+        return fail(FSGPU_ERR_INVALID_CONFIG, "fsgpu_bert_options: unknown linear_format");
+    *format = options->linear_format;
+    return FSGPU_OK;
+}
+}  // namespace
+
+fsgpu_status fsgpu_bert_create_ex(int32_t device, const fsgpu_bert_config* config, const fsgpu_bert_weights* weights,
+                                  const fsgpu_bert_options* options, fsgpu_bert** out) {
+    if (!out || !config || !weights) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    uint32_t format = 0;
+    const fsgpu_status st = bert_linear_format(options, &format);
+    if (st != FSGPU_OK) return st;
+    return guarded([&]() -> fsgpu_status {
+        auto* h = new fsgpu_bert();
+        fsgpu::SearchError e = h->impl.init(device, *config, *weights, format);
+        if (!e.ok()) {
+            delete h;
+            return finish(e);
+        }
+        *out = h;
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_bert_create_safetensors_ex(int32_t device, const void* blob, uint64_t blob_len, float ln_eps,
+                                              const fsgpu_bert_options* options, fsgpu_bert** out) {
+    if (!out || !blob) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    uint32_t format = 0;
+    const fsgpu_status st = bert_linear_format(options, &format);
+    if (st != FSGPU_OK) return st;
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_bert>();
+        // the blob first (a malformed model file is reported as such on any host), then the device
+        fsgpu::SearchError e = h->impl.init_safetensors(-1, blob, blob_len, ln_eps, format);
+        if (!e.ok()) return finish(e);
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+            return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        e = h->impl.init_safetensors(device, blob, blob_len, ln_eps, format);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+uint32_t fsgpu_bert_linear_format(const fsgpu_bert* m) { return m ? m->impl.linear_format() : FSGPU_BERT_LINEAR_F16; }
+
 void fsgpu_bert_destroy(fsgpu_bert* m) { delete m; }
+
+fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float* x, const float* w, const float* bias, uint32_t m, uint32_t n,
+                                           uint32_t k, float* y) {
+    if ((m && (!x || !y)) || !w || !bias) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (!fsgpu::bert_i8_gemm_supported((int)n, (int)k) || n > (1u << 20) || k > (1u << 20))
+        return fail(FSGPU_ERR_INVALID_CONFIG, "int8 linear: K and N must be multiples of 64");
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        if (m == 0) return FSGPU_OK;
+        fsgpu::DeviceBuffer dx, dw, db, dy, qx, sx, wp, sw;
+        fsgpu::SearchError e = dx.reserve((size_t)m * k * 4);
+        if (e.ok()) e = dw.reserve((size_t)n * k * 4);
+        if (e.ok()) e = db.reserve((size_t)n * 4);
+        if (e.ok()) e = dy.reserve((size_t)m * n * 4);
+        if (e.ok()) e = qx.reserve((size_t)m * k);
+        if (e.ok()) e = sx.reserve((size_t)m * 4);
+        if (e.ok()) e = wp.reserve(fsgpu::bert_i8_packed_bytes((int)n, (int)k));
+        if (e.ok()) e = sw.reserve((size_t)n * 4);
+        hipError_t he = hipSuccess;
+        if (e.ok()) {
+            he = hipMemcpy(dx.ptr, x, (size_t)m * k * 4, hipMemcpyHostToDevice);
+            if (he == hipSuccess) he = hipMemcpy(dw.ptr, w, (size_t)n * k * 4, hipMemcpyHostToDevice);
+            if (he == hipSuccess) he = hipMemcpy(db.ptr, bias, (size_t)n * 4, hipMemcpyHostToDevice);
+            if (he == hipSuccess)
+                he = fsgpu::launch_bert_i8_pack_w(static_cast<const float*>(dw.ptr), wp.ptr, static_cast<float*>(sw.ptr), (int)n, (int)k, nullptr);
+            if (he == hipSuccess)
+                he = fsgpu::launch_bert_i8_quant_rows(static_cast<const float*>(dx.ptr), qx.ptr, static_cast<float*>(sx.ptr), (int)m, (int)k, nullptr);
+            if (he == hipSuccess)
+                he = fsgpu::launch_bert_i8_gemm(qx.ptr, static_cast<const float*>(sx.ptr), wp.ptr, static_cast<const float*>(sw.ptr),
+                                                static_cast<const float*>(db.ptr), static_cast<float*>(dy.ptr), (int)m, (int)n, (int)k, false, nullptr);
+            if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+            if (he == hipSuccess) he = hipMemcpy(y, dy.ptr, (size_t)m * n * 4, hipMemcpyDeviceToHost);
+        }
+        for (fsgpu::DeviceBuffer* b : {&dx, &dw, &db, &dy, &qx, &sx, &wp, &sw}) b->release();
+        if (!e.ok()) return finish(e);
+        if (he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(he));
+        return FSGPU_OK;
+    });
+}
 
 fsgpu_status fsgpu_bert_embed_device(fsgpu_bert* m, const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out_dev) {
     if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");

@@ -394,4 +394,19 @@ struct BertDocsArgs {
 bool bert_docs_w_supported(int hidden, int inter, int heads);
 hipError_t launch_bert_docs_w(const BertDocsArgs& a, uint32_t nblocks, hipStream_t stream);
 
+// bert_int8.hip: the int8 dynamic-quant linears (FSGPU_BERT_LINEAR_INT8_DYNAMIC) — per-output-channel int8 weights packed in
+// fragment order, per-row int8 activations, v_mfma_i32_16x16x64_i8, f32 epilogue.  q buffers are int8, s buffers f32 scales.
+bool bert_i8_gemm_supported(int N, int K);   // K % 64 == 0 and N % 64 == 0
+size_t bert_i8_packed_bytes(int N, int K);
+hipError_t launch_bert_i8_pack_w(const float* w, void* wp, float* sw, int N, int K, hipStream_t stream);
+hipError_t launch_bert_i8_quant_rows(const float* x, void* q, float* s, int rows, int K, hipStream_t stream);
+hipError_t launch_bert_i8_quant_rows_h(const void* x_h, void* q, float* s, int rows, int K, hipStream_t stream);
+hipError_t launch_bert_i8_embed_ln_quant(const int32_t* ids, const int32_t* positions, const float* word, const float* pos,
+                                         const float* type0, const float* lnw, const float* lnb, float* x, void* q, float* s, int tokens,
+                                         int hidden, float eps, hipStream_t stream);
+hipError_t launch_bert_i8_add_ln_quant(float* x, const float* delta, const float* lnw, const float* lnb, void* q, float* s, int tokens,
+                                       int hidden, float eps, hipStream_t stream);
+hipError_t launch_bert_i8_gemm(const void* qa, const float* sa, const void* wp, const float* sw, const float* bias, float* out, int M,
+                               int N, int K, bool gelu, hipStream_t stream);
+
 }  // namespace fsgpu

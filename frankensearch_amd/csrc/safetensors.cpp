@@ -120,7 +120,7 @@ struct Tensor {
 
 }  // namespace
 
-SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps) {
+SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps, uint32_t linear_format) {
     const unsigned char* bytes = static_cast<const unsigned char*>(blob);
     if (!bytes || blob_len < 8) return load_failed("safetensors file too small");
     uint64_t header_len = 0;
@@ -288,7 +288,7 @@ SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint6
     }
     w.layers = lw.data();
     if (device < 0) return SearchError{};   // parse only (callers that validate a blob without a device)
-    return init(device, cfg, w);
+    return init(device, cfg, w, linear_format);
 }
 
 }  // namespace fsgpu

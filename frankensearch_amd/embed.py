@@ -97,13 +97,34 @@ _HF_LAYER_KEYS = {
 }
 
 
+class _BertOptions(C.Structure):
+    _fields_ = [("linear_format", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+# fsgpu_bert_options.linear_format (include/fsgpu.h): the keyword of NativeEmbedder -> FSGPU_BERT_LINEAR_*
+LINEAR_FORMATS = {"f16": 0, "int8_dynamic": 1}
+
+
+def _bert_options(linear: str):
+    """None for "f16" (the library's default, through the original create calls); an fsgpu_bert_options otherwise."""
+    if linear not in LINEAR_FORMATS:
+        raise ValueError(f"linear must be one of {sorted(LINEAR_FORMATS)}, not {linear!r}")
+    return None if linear == "f16" else _BertOptions(LINEAR_FORMATS[linear])
+
+
 class NativeEmbedder:
     """MiniLM-class BERT embedder (crates/frankensearch-rerank/src/native_embedder.rs:40-50).
 
     `weights` is a dict of f32 arrays in the HuggingFace key layout; bare `embeddings.*` / `encoder.*` keys are
-    normalised to the `bert.` prefix exactly like `parse_weights` (native.rs:1466-1476)."""
+    normalised to the `bert.` prefix exactly like `parse_weights` (native.rs:1466-1476).
 
-    def __init__(self, weights: dict, device: int = 0, ln_eps: float = 1e-12):
+    `linear` chooses the arithmetic of the linears at create time: "f16" (the default: f16 matrix-core linears) or
+    "int8_dynamic" (the reference's native forward: int8 per-output-channel weights, per-row dynamic int8 activations; within
+    cosine 0.995 / max-abs 6e-2 of the f32 forward instead of 0.999 / 2e-3, and bitwise the same vector for a text whatever
+    batch it rides in — DESIGN §3.8)."""
+
+    def __init__(self, weights: dict, device: int = 0, ln_eps: float = 1e-12, linear: str = "f16"):
+        opts = _bert_options(linear)
         w = {}
         for k, v in weights.items():
             if k.startswith("embeddings.") or k.startswith("encoder."):
@@ -127,30 +148,43 @@ class NativeEmbedder:
                           w["bert.embeddings.LayerNorm.bias"].ctypes.data, lw)
         self._dim = hidden
         h = C.c_void_p()
-        check(_lib.lib().fsgpu_bert_create(device, C.byref(cfg), C.byref(bw), C.byref(h)))
+        if opts is None:
+            check(_lib.lib().fsgpu_bert_create(device, C.byref(cfg), C.byref(bw), C.byref(h)))
+        else:
+            check(_lib.lib().fsgpu_bert_create_ex(device, C.byref(cfg), C.byref(bw), C.byref(opts), C.byref(h)))
         self._h = h
 
     @classmethod
-    def from_safetensors(cls, path: str, device: int = 0, ln_eps: float = 1e-12) -> "NativeEmbedder":
+    def from_safetensors(cls, path: str, device: int = 0, ln_eps: float = 1e-12, linear: str = "f16") -> "NativeEmbedder":
         """NativeEmbedder::load (native_embedder.rs:60-116): the model file goes to the library as it is — the safetensors header and
         the HuggingFace key layout are parsed behind the C ABI (fsgpu_bert_create_safetensors = parse_weights, native.rs:1359-1602)."""
         with open(path, "rb") as f:
-            return cls.from_safetensors_bytes(f.read(), device=device, ln_eps=ln_eps)
+            return cls.from_safetensors_bytes(f.read(), device=device, ln_eps=ln_eps, linear=linear)
 
     @classmethod
-    def from_safetensors_bytes(cls, blob: bytes, device: int = 0, ln_eps: float = 1e-12) -> "NativeEmbedder":
+    def from_safetensors_bytes(cls, blob: bytes, device: int = 0, ln_eps: float = 1e-12, linear: str = "f16") -> "NativeEmbedder":
+        opts = _bert_options(linear)
         buf = np.frombuffer(blob, dtype=np.uint8)   # (numpy's buffer of a bytes object is 16-byte aligned past its header: checked by the library)
         if buf.ctypes.data % 8:
             buf = np.require(buf.copy(), requirements=["ALIGNED"])
         self = cls.__new__(cls)
         h = C.c_void_p()
-        check(_lib.lib().fsgpu_bert_create_safetensors(device, buf.ctypes.data, buf.size, ln_eps, C.byref(h)))
+        if opts is None:
+            check(_lib.lib().fsgpu_bert_create_safetensors(device, buf.ctypes.data, buf.size, ln_eps, C.byref(h)))
+        else:
+            check(_lib.lib().fsgpu_bert_create_safetensors_ex(device, buf.ctypes.data, buf.size, ln_eps, C.byref(opts), C.byref(h)))
         self._h = h
         self._dim = int(_lib.lib().fsgpu_bert_dimension(h))
         return self
 
     def dimension(self) -> int:
         return self._dim
+
+    @property
+    def linear_format(self) -> str:
+        """The `linear` keyword this embedder was created with ("f16" or "int8_dynamic"), as the library reports it."""
+        code = int(_lib.lib().fsgpu_bert_linear_format(self._h))
+        return {v: k for k, v in LINEAR_FORMATS.items()}[code]
 
     def embed_token_ids(self, ids: Sequence[int]) -> np.ndarray:
         return self.embed_batch_token_ids([ids])[0]

@@ -508,6 +508,27 @@ fsgpu_status fsgpu_bert_create(int32_t device, const fsgpu_bert_config *config, 
  * for.  The tensor data must be 4-byte aligned in `blob` (it is when the file is read into a buffer malloc returned: the header
  * is padded to 8 bytes). */
 fsgpu_status fsgpu_bert_create_safetensors(int32_t device, const void *blob, uint64_t blob_len, float ln_eps, fsgpu_bert **out);
+/* Linear format, chosen at create time.  INT8_DYNAMIC is the arithmetic class of the reference's native forward
+ * (native.rs:484-553,1506,1546-1600): every Linear weight int8 per output channel (quantised once at load), every Linear input int8
+ * per row at forward, i32 accumulation, y = ((float)acc * (sx[m] * sw[n])) + b[n]; Q/K/V fused into one [3H, H] linear; embeddings,
+ * LayerNorm, softmax, GELU and the residuals stay f32.  Quantisation of a row: amax = max |x|, inv = 127.0f / amax,
+ * q = clamp(round_half_away(x * inv), -127, 127), scale = amax / 127.0f (all-zero row: q = 0, scale = 0).  It is NOT held to the f16
+ * mode's tolerance against the f32 forward (cosine >= 0.995, max-abs <= 6e-2 instead of 0.999 / 2e-3), and a text's vector has the
+ * same bits whatever batch it is embedded in.  hidden and inter must be multiples of 64 (they are of 128 for every model the
+ * library takes). */
+#define FSGPU_BERT_LINEAR_F16 0           /* default: f16 matrix-core linears (today's behaviour) */
+#define FSGPU_BERT_LINEAR_INT8_DYNAMIC 1  /* native.rs: int8 per-output-channel weights, per-row dynamic int8 activations */
+typedef struct fsgpu_bert_options {
+    uint32_t linear_format;
+    uint32_t reserved[7]; /* must be 0 */
+} fsgpu_bert_options;
+/* fsgpu_bert_create / fsgpu_bert_create_safetensors with options (NULL = FSGPU_BERT_LINEAR_F16, exactly the calls above).  An
+ * unknown format or a non-zero reserved word is FSGPU_ERR_INVALID_CONFIG, reported before a blob is parsed or a device looked for. */
+fsgpu_status fsgpu_bert_create_ex(int32_t device, const fsgpu_bert_config *config, const fsgpu_bert_weights *weights,
+                                  const fsgpu_bert_options *options, fsgpu_bert **out);
+fsgpu_status fsgpu_bert_create_safetensors_ex(int32_t device, const void *blob, uint64_t blob_len, float ln_eps,
+                                              const fsgpu_bert_options *options, fsgpu_bert **out);
+uint32_t fsgpu_bert_linear_format(const fsgpu_bert *m); /* FSGPU_BERT_LINEAR_*; 0 for NULL */
 void fsgpu_bert_destroy(fsgpu_bert *m);
 uint32_t fsgpu_bert_dimension(const fsgpu_bert *m); /* Embedder::dimension: the model's hidden size */
 /* embed_batch_sync over token ids (native_embedder.rs:218-255 -> Model::embed_forward native.rs:1142-1236):

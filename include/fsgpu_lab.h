@@ -40,6 +40,11 @@ const char *fsgpu_last_main_pass_kernel(void);
  * search.rs:449-473), host arrays in and out — so that tests can check it against a host sort at tile boundaries.  varying_bits: the
  * bits in which two keys of the input may differ (~0 when unknown): a digit without one gets no pass. */
 fsgpu_status fsgpu_lab_sort_keys_desc(int32_t device, const uint64_t *keys, uint64_t n, uint64_t varying_bits, uint64_t *out_sorted);
+/* The int8 dynamic-quant linear of FSGPU_BERT_LINEAR_INT8_DYNAMIC on host buffers, for kernel-level tests: W [N, K] f32 through the
+ * load-time weight packer, x [M, K] f32 through the row quantiser, then the int8 GEMM with the bias epilogue: y [M, N] f32.
+ * K and N must be multiples of 64 (else FSGPU_ERR_INVALID_CONFIG). */
+fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float *x, const float *w, const float *bias, uint32_t m, uint32_t n,
+                                           uint32_t k, float *y);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
