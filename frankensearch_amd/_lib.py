@@ -143,6 +143,13 @@ SIGNATURES = {
     "fsgpu_index_device": (_i32, [_vp]),
     "fsgpu_bert_dimension": (_u32, [_vp]),
     "fsgpu_bert_embed": (_i32, [_vp, _vp, _vp, _u32, _vp]),
+    "fsgpu_reranker_create": (_i32, [_i32, _vp, _vp, C.POINTER(_vp)]),
+    "fsgpu_reranker_create_safetensors": (_i32, [_i32, _vp, _u64, C.c_float, C.POINTER(_vp)]),
+    "fsgpu_reranker_destroy": (None, [_vp]),
+    "fsgpu_reranker_device": (_i32, [_vp]),
+    "fsgpu_reranker_max_length": (_u32, [_vp]),
+    "fsgpu_reranker_score": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "fsgpu_rerank_apply": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, C.c_float, _vp]),
     "fsgpu_rrf_fuse": (_i32, [_vp, _u32, _vp, _u32, C.c_double, C.c_double, C.c_double, _i32, _u32, _u32, _vp,
                               C.POINTER(_u32)]),
     "fsgpu_blend_two_tier": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32)]),

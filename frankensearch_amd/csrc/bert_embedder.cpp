@@ -410,8 +410,7 @@ SearchError NativeEmbedder::forward_packed_range(uint32_t d0, uint32_t d1, uint3
                                   static_cast<const float*>(emb_ln_b_.ptr), x, x_h, T, H, eps, stream));
     const float scale = 0.17677669f;  // ATTN_SCALE_F32 = 1/sqrt(32) (native.rs:44)
     for (Layer& l : layers_) {
-        BERT_HIP(launch_bert_gemm_w(x_h, l.qkv_wp.ptr, static_cast<const float*>(l.qkv_b.ptr), nullptr, qkv + (size_t)t0 * 3 * H, T,
-                                    3 * H, H, 2, stream));
+        BERT_TRY(packed_qkv(l, x_h, qkv + (size_t)t0 * 3 * H, T, false, stream));
         BERT_HIP(launch_bert_attention_h(qkv, offs, ctx, (int)(d1 - d0), (int)cfg_.heads, H, (int)max_seq, scale, stream));
         if (T >= FSGPU_BERT_SPLIT_MIN_TOKENS && bert_gemm_ln_w_supported(H, H) && bert_gemm_ln_w_supported(H, I) && bert_gemm_w_supported(I, H)) {
             // Thousands of rows (the documents of an index build): the one-launch post-attention block re-streams its 2.65 MB of
@@ -427,14 +426,29 @@ SearchError NativeEmbedder::forward_packed_range(uint32_t d0, uint32_t d1, uint3
                                            static_cast<const float*>(l.ln2_w.ptr), static_cast<const float*>(l.ln2_b.ptr), T, H, I, eps, stream));
             continue;
         }
-        BERT_HIP(launch_bert_post_attn_w(ctx + (size_t)t0 * H, l.ao_wp.ptr, static_cast<const float*>(l.ao_b.ptr),
-                                         static_cast<const float*>(l.ln1_w.ptr), static_cast<const float*>(l.ln1_b.ptr),
-                                         l.i_wp.ptr, static_cast<const float*>(l.i_b.ptr), l.o_wp.ptr,
-                                         static_cast<const float*>(l.o_b.ptr), x, x_h, static_cast<const float*>(l.ln2_w.ptr),
-                                         static_cast<const float*>(l.ln2_b.ptr), T, H, I, eps, stream));
+        BERT_TRY(packed_post_attention(l, ctx + (size_t)t0 * H, x, x_h, T, false, stream));
     }
     float* out = (pooled_out_ ? pooled_out_ : static_cast<float*>(out_.ptr)) + (size_t)d0 * H;
     BERT_HIP(launch_bert_pool(xa, offs, out, (int)(d1 - d0), H, stream));
+    return SearchError{};
+}
+
+SearchError NativeEmbedder::packed_qkv(const Layer& l, const _Float16* x_h, _Float16* qkv, int T, bool fixed, hipStream_t stream) {
+    const int H = (int)cfg_.hidden;
+    const float* bias = static_cast<const float*>(l.qkv_b.ptr);
+    if (fixed) BERT_HIP(launch_bert_gemm_w_fixed(x_h, l.qkv_wp.ptr, bias, nullptr, qkv, T, 3 * H, H, 2, stream));
+    else BERT_HIP(launch_bert_gemm_w(x_h, l.qkv_wp.ptr, bias, nullptr, qkv, T, 3 * H, H, 2, stream));
+    return SearchError{};
+}
+
+SearchError NativeEmbedder::packed_post_attention(const Layer& l, const _Float16* ctx, float* x, _Float16* x_h, int M, bool fixed,
+                                                  hipStream_t stream) {
+    const int H = (int)cfg_.hidden, I = (int)cfg_.inter;
+    auto launch = fixed ? launch_bert_post_attn_w_fixed : launch_bert_post_attn_w;
+    BERT_HIP(launch(ctx, l.ao_wp.ptr, static_cast<const float*>(l.ao_b.ptr), static_cast<const float*>(l.ln1_w.ptr),
+                    static_cast<const float*>(l.ln1_b.ptr), l.i_wp.ptr, static_cast<const float*>(l.i_b.ptr), l.o_wp.ptr,
+                    static_cast<const float*>(l.o_b.ptr), x, x_h, static_cast<const float*>(l.ln2_w.ptr),
+                    static_cast<const float*>(l.ln2_b.ptr), M, H, I, cfg_.ln_eps, stream));
     return SearchError{};
 }
 

@@ -4,7 +4,9 @@
 #pragma once
 
 #include <cstdint>
+#include <deque>
 #include <map>
+#include <string>
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -13,6 +15,23 @@
 #include "vector_index.hpp"
 
 namespace fsgpu {
+
+// A safetensors blob in HuggingFace key layout, parsed in place (safetensors.cpp; parse_weights, native.rs:1359-1602): the encoder's
+// shape and tensors, and every F32 tensor by its `bert.`-normalised key (the reranker's pooler / classifier are looked up there).
+struct BlobTensor {
+    const float* data = nullptr;
+    std::vector<uint64_t> shape;
+    uint64_t count = 0;
+};
+struct BertBlob {
+    fsgpu_bert_config cfg{};
+    fsgpu_bert_weights w{};
+    uint32_t type_rows = 0;
+    std::vector<fsgpu_bert_layer_weights> layers;
+    std::map<std::string, BlobTensor> tensors;
+    std::deque<std::vector<float>> staged;   // copies of tensors that were not 4-byte aligned in the blob
+};
+SearchError parse_bert_safetensors(const void* blob, uint64_t blob_len, float ln_eps, BertBlob* out);
 
 class NativeEmbedder {
   public:
@@ -58,6 +77,12 @@ class NativeEmbedder {
     SearchError embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out, float* out_dev);
     SearchError reserve_workspaces(uint32_t tokens);
     void drop_graphs();
+    // One layer of the fragment-order path, in pieces its callers share: the QKV projection of T rows (f16 Q | K | V out), then — after
+    // the caller's attention — the post-attention block over M rows (output projection + LN, FFN + LN).  fixed: the launchers that keep
+    // ONE kernel form whatever the row count (launch_bert_*_fixed): the cross-encoder's chain (bert_reranker.cpp)
+    SearchError packed_qkv(const Layer& l, const _Float16* x_h, _Float16* qkv, int T, bool fixed, hipStream_t stream);
+    SearchError packed_post_attention(const Layer& l, const _Float16* ctx, float* x, _Float16* x_h, int M, bool fixed, hipStream_t stream);
+    friend class NativeReranker;   // the cross-encoder runs this embedder's uploaded weights, stream and layer steps
 
     std::mutex mu_;
     int device_ = -1;

@@ -1553,4 +1553,41 @@ extern "C" int fsgpu_lab_ffn_stamps(unsigned long long* out16) {
 }
 #endif
 
+// ONE kernel form per step whatever M is: bert_gemm_w_kernel (64-row tiles) and the 32-row post-attention block — never the
+// weight-stationary or 64-row forms the launchers above switch to for thousands of rows.  Used by the cross-encoder, whose logits must
+// not depend on the call's token count (bert_reranker.cpp).
+hipError_t launch_bert_gemm_w_fixed(const void* a_h, const void* wp, const float* bias, float* out_f32, void* out_h, int M, int N,
+                                    int K, int epilogue, hipStream_t stream) {
+    if (!bert_gemm_w_supported(N, K) || epilogue < 0 || epilogue > 2 || M < 0) return hipErrorInvalidValue;
+    if (M == 0) return hipSuccess;
+#define FSGPU_GWF(E, KS)                                                                                                   \
+    hipLaunchKernelGGL((bert_gemm_w_kernel<E, KS>), dim3(N / 128, (M + 63) / 64), dim3(256), 0, stream,                    \
+                       static_cast<const _Float16*>(a_h), static_cast<const half8*>(wp), bias, out_f32, static_cast<_Float16*>(out_h), M, N)
+#define FSGPU_GWF_K(E)                   \
+    do {                                 \
+        if (K == 384) FSGPU_GWF(E, 12);  \
+        else if (K == 256) FSGPU_GWF(E, 8); \
+        else FSGPU_GWF(E, 4);            \
+    } while (0)
+    if (epilogue == 0) FSGPU_GWF_K(0);
+    else if (epilogue == 1) FSGPU_GWF_K(1);
+    else FSGPU_GWF_K(2);
+#undef FSGPU_GWF_K
+#undef FSGPU_GWF
+    return hipGetLastError();
+}
+
+hipError_t launch_bert_post_attn_w_fixed(const void* ctx_h, const void* w0p, const float* b0, const float* ln0w, const float* ln0b,
+                                         const void* w1p, const float* b1, const void* w2p, const float* b2, float* x_f32, void* x_h,
+                                         const float* lnw, const float* lnb, int M, int hidden, int inter, float eps,
+                                         hipStream_t stream) {
+    if (!bert_post_attn_w_supported(hidden, inter) || M < 0) return hipErrorInvalidValue;
+    if (M == 0) return hipSuccess;
+    switch (hidden) {
+        case 384: return launch_ffn_w_t<6, true>(ctx_h, w0p, b0, ln0w, ln0b, w1p, b1, w2p, b2, x_f32, x_h, lnw, lnb, M, inter, eps, stream);
+        case 256: return launch_ffn_w_t<4, true>(ctx_h, w0p, b0, ln0w, ln0b, w1p, b1, w2p, b2, x_f32, x_h, lnw, lnb, M, inter, eps, stream);
+        default: return launch_ffn_w_t<2, true>(ctx_h, w0p, b0, ln0w, ln0b, w1p, b1, w2p, b2, x_f32, x_h, lnw, lnb, M, inter, eps, stream);
+    }
+}
+
 }  // namespace fsgpu

@@ -15,6 +15,7 @@
 #include <shared_mutex>
 
 #include "bert_embedder.hpp"
+#include "bert_reranker.hpp"
 #include "coalescer.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
@@ -88,6 +89,9 @@ struct fsgpu_bert {
     std::vector<float> co_out;
 };
 
+struct fsgpu_reranker {
+    fsgpu::NativeReranker impl;
+};
 namespace {
 
 thread_local std::string g_last_error;
@@ -1656,6 +1660,50 @@ fsgpu_status fsgpu_index_set_variant(fsgpu_index* idx, int32_t variant) {
     idx->impl.variant = variant;
     idx->impl.sync_replicas();
     return FSGPU_OK;
+}
+
+
+fsgpu_status fsgpu_reranker_create(int32_t device, const fsgpu_bert_config* config, const fsgpu_reranker_weights* weights,
+                                   fsgpu_reranker** out) {
+    if (!out || !config || !weights) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_reranker>();
+        fsgpu::SearchError e = h->impl.init(device, *config, weights->bert, weights->type_vocab, weights->pooler_w, weights->pooler_b,
+                                            weights->classifier_w, weights->classifier_b);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_reranker_create_safetensors(int32_t device, const void* blob, uint64_t blob_len, float ln_eps, fsgpu_reranker** out) {
+    if (!out || !blob) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_reranker>();
+        // the blob first (a malformed model file is reported as such on any host), then the device
+        fsgpu::SearchError e = h->impl.init_safetensors(-1, blob, blob_len, ln_eps);
+        if (!e.ok()) return finish(e);
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+            return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        e = h->impl.init_safetensors(device, blob, blob_len, ln_eps);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_reranker_destroy(fsgpu_reranker* m) { delete m; }
+int32_t fsgpu_reranker_device(const fsgpu_reranker* m) { return m ? m->impl.device() : -1; }
+uint32_t fsgpu_reranker_max_length(const fsgpu_reranker* m) { return m ? m->impl.max_length() : 0; }
+
+fsgpu_status fsgpu_reranker_score(fsgpu_reranker* m, const int32_t* ids, const int32_t* type_ids, const uint32_t* offsets, uint32_t n,
+                                  float* out_logits, float* out_scores) {
+    if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "reranker is null");
+    return guarded([&]() -> fsgpu_status { return finish(m->impl.score(ids, type_ids, offsets, n, out_logits, out_scores)); });
 }
 
 }  // extern "C"

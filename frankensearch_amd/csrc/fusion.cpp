@@ -312,3 +312,56 @@ extern "C" fsgpu_status fsgpu_blend_two_tier_aligned(const fsgpu_scored_doc* fas
     *out_count = (uint32_t)blended.size();
     return FSGPU_OK;
 }
+
+// rerank_step_with_combine after the model call (crates/frankensearch-rerank/src/pipeline.rs:125-360): the scores of the
+// candidates WITH text inside the window, in window order, land on their candidates (stale rerank scores in the window cleared,
+// non-finite scores skipped), then the window is reordered — PureReorder: rerank score desc (non-finite as -inf, total order),
+// doc_id asc (compare_by_rerank_score :290-303); RrfCombine: 1/(k + pre_rank) + 1/(k + rerank_rank) in f64 desc, doc_id asc
+// (apply_rrf_combine :322-360).  Both sorts are stable, as Rust's sort_by is.  Candidates past the window keep their order.
+extern "C" fsgpu_status fsgpu_rerank_apply(fsgpu_rerank_candidate* candidates, uint32_t n, const uint8_t* has_text, const float* scores,
+                                           uint32_t n_scores, uint32_t top_k_rerank, uint32_t min_candidates, int32_t combine, float k,
+                                           uint8_t* out_applied) {
+    if (out_applied) *out_applied = 0;
+    if (combine != FSGPU_RERANK_PURE_REORDER && combine != FSGPU_RERANK_RRF_COMBINE) return FSGPU_ERR_INVALID_CONFIG;
+    if (n > 0 && !candidates) return FSGPU_ERR_NULL_ARGUMENT;
+    if (n < min_candidates) return FSGPU_OK;   // too few candidates (:135-142)
+    const uint32_t window = std::min(n, top_k_rerank);
+    std::vector<uint32_t> included;   // window positions of the candidates with text, in order
+    for (uint32_t i = 0; i < window; ++i)
+        if (!has_text || has_text[i]) included.push_back(i);
+    if (included.size() < min_candidates) return FSGPU_OK;   // too few with text (:165-172)
+    if (n_scores != included.size()) return FSGPU_OK;        // score count mismatch: skipped (:205-213)
+    if (n_scores > 0 && !scores) return FSGPU_ERR_NULL_ARGUMENT;
+    const float none = std::numeric_limits<float>::quiet_NaN();
+    for (uint32_t i = 0; i < window; ++i) candidates[i].rerank_score = none;   // clear_rerank_scores (:265-270)
+    for (uint32_t j = 0; j < n_scores; ++j)
+        if (std::isfinite(scores[j])) candidates[included[j]].rerank_score = scores[j];
+    auto doc = [](const fsgpu_rerank_candidate& c) { return std::string_view(c.doc_id, c.doc_id_len); };
+    auto sort_key = [](const fsgpu_rerank_candidate& c) {
+        return total_key32(std::isfinite(c.rerank_score) ? c.rerank_score : -std::numeric_limits<float>::infinity());
+    };
+    auto by_rerank = [&](const fsgpu_rerank_candidate& a, const fsgpu_rerank_candidate& b) {
+        const int32_t ka = sort_key(a), kb = sort_key(b);
+        if (ka != kb) return ka > kb;
+        return doc(a) < doc(b);
+    };
+    if (combine == FSGPU_RERANK_PURE_REORDER) {
+        std::stable_sort(candidates, candidates + window, by_rerank);
+    } else if (window >= 2) {
+        const double kf = (double)(std::isnan(k) ? 1.0f : std::max(k, 1.0f));   // f32::max: a NaN k gives 1
+        std::vector<uint32_t> order(window);
+        for (uint32_t i = 0; i < window; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return by_rerank(candidates[a], candidates[b]); });
+        std::vector<double> key(window);
+        for (uint32_t r = 0; r < window; ++r) key[order[r]] = 1.0 / (kf + (double)order[r]) + 1.0 / (kf + (double)r);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            const int64_t ka = total_key64(key[a]), kb = total_key64(key[b]);
+            if (ka != kb) return ka > kb;
+            return doc(candidates[a]) < doc(candidates[b]);
+        });
+        std::vector<fsgpu_rerank_candidate> snap(candidates, candidates + window);
+        for (uint32_t i = 0; i < window; ++i) candidates[i] = snap[order[i]];
+    }
+    if (out_applied) *out_applied = 1;
+    return FSGPU_OK;
+}

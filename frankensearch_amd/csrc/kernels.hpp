@@ -334,6 +334,24 @@ hipError_t launch_bert_post_attn_w(const void* ctx_h, const void* w0p, const flo
                                    const void* w1p, const float* b1, const void* w2p, const float* b2, float* x_f32, void* x_h,
                                    const float* lnw, const float* lnb, int M, int hidden, int inter, float eps,
                                    hipStream_t stream);
+// The same two steps in ONE kernel form whatever M is (the 64-row-tile GEMM; the 32-row post-attention block): a row's bits depend on
+// the model's shape only, never on how many rows ride along (the cross-encoder's batch invariance, bert_reranker.cpp)
+hipError_t launch_bert_gemm_w_fixed(const void* a_h, const void* wp, const float* bias, float* out_f32, void* out_h, int M, int N,
+                                    int K, int epilogue, hipStream_t stream);
+hipError_t launch_bert_post_attn_w_fixed(const void* ctx_h, const void* w0p, const float* b0, const float* ln0w, const float* ln0b,
+                                         const void* w1p, const float* b1, const void* w2p, const float* b2, float* x_f32, void* x_h,
+                                         const float* lnw, const float* lnb, int M, int hidden, int inter, float eps,
+                                         hipStream_t stream);
+
+// bert_rerank.hip: the cross-encoder's own kernels — typed embeddings, the last layer's [CLS]-query attention, pooler + classifier
+bool bert_rerank_supported(int hidden);
+hipError_t launch_bert_embed_typed_ln(const int32_t* ids, const int32_t* types, const int32_t* positions, const float* word,
+                                      const float* pos, const float* type_emb, const float* lnw, const float* lnb, float* x_f32,
+                                      void* x_h, int tokens, int hidden, float eps, hipStream_t stream);
+hipError_t launch_bert_cls_attention(const void* qkv_h, const uint32_t* offsets, const float* x, void* ctx_cls_h, float* x_cls,
+                                     int n_pairs, int heads, int hidden, float scale, hipStream_t stream);
+hipError_t launch_bert_cls_head(const float* x_cls, const float* pool_w, const float* pool_b, const float* cls_w, const float* cls_b,
+                                float* logits, float* scores, int n_pairs, int hidden, hipStream_t stream);
 
 // bert_query_kernels.hip: the MiniLM-L6 forward for at most 32 tokens in 25 launches (4 per layer + the pooling), every
 // add+LayerNorm riding in the prologue of the GEMM that consumes it.  One argument block serves all stages; a stage reads

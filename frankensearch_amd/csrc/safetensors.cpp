@@ -112,15 +112,19 @@ struct JsonCursor {
     }
 };
 
-struct Tensor {
-    const float* data = nullptr;
-    std::vector<uint64_t> shape;
-    uint64_t count = 0;
-};
-
 }  // namespace
 
 SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps, uint32_t linear_format) {
+    BertBlob b;
+    SearchError e = parse_bert_safetensors(blob, blob_len, ln_eps, &b);
+    if (!e.ok() || device < 0) return e;   // (device < 0: parse only — callers that validate a blob without a device)
+    return init(device, b.cfg, b.w, linear_format);
+}
+
+SearchError parse_bert_safetensors(const void* blob, uint64_t blob_len, float ln_eps, BertBlob* out) {
+    using Tensor = BlobTensor;
+    std::deque<std::vector<float>>& staged = out->staged;
+    std::map<std::string, Tensor>& raw = out->tensors;
     const unsigned char* bytes = static_cast<const unsigned char*>(blob);
     if (!bytes || blob_len < 8) return load_failed("safetensors file too small");
     uint64_t header_len = 0;
@@ -131,10 +135,8 @@ SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint6
     // A tensor that does not start on a 4-byte address in the caller's blob (a header length that is not a multiple of 4: older
     // writers, hand-made files) is copied to an aligned staging area; the reference decodes with f32::from_le_bytes at any
     // alignment (native.rs parse_weights) and loads such files.
-    std::deque<std::vector<float>> staged;
     JsonCursor c{reinterpret_cast<const char*>(bytes + 8), reinterpret_cast<const char*>(bytes + 8 + header_len)};
     if (!c.eat('{')) return load_failed("safetensors header is not an object");
-    std::map<std::string, Tensor> raw;
     if (!c.eat('}')) {
         for (;;) {
             std::string name;
@@ -235,7 +237,7 @@ SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint6
     e = shape_of("bert.encoder.layer.0.intermediate.dense.weight", &inter, &ih);
     if (!e.ok()) return e;
     if (ph != hidden || ih != hidden || hidden % 32 != 0) return load_failed("hidden size must be a multiple of 32 and agree across tensors (native.rs:36-45: 32-wide heads)");
-    fsgpu_bert_config cfg{};
+    fsgpu_bert_config& cfg = out->cfg;
     cfg.vocab = (uint32_t)vocab;
     cfg.hidden = (uint32_t)hidden;
     cfg.layers = layers;
@@ -243,13 +245,15 @@ SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint6
     cfg.inter = (uint32_t)inter;
     cfg.max_pos = (uint32_t)(max_pos < 512 ? max_pos : 512);   // DEFAULT_MAX_LENGTH (native.rs:41-51)
     cfg.ln_eps = ln_eps > 0.f ? ln_eps : 1e-12f;
-    std::vector<fsgpu_bert_layer_weights> lw(layers);
-    fsgpu_bert_weights w{};
+    std::vector<fsgpu_bert_layer_weights>& lw = out->layers;
+    lw.assign(layers, fsgpu_bert_layer_weights{});
+    fsgpu_bert_weights& w = out->w;
     const uint64_t H = hidden, I = inter;
     uint64_t type_rows = 0, th = 0;
     e = shape_of("bert.embeddings.token_type_embeddings.weight", &type_rows, &th);
     if (!e.ok()) return e;
     if (th != hidden) return load_failed("token_type_embeddings has another hidden size");
+    out->type_rows = (uint32_t)type_rows;
     struct Want {
         const char* key;
         uint64_t rows, cols;
@@ -287,8 +291,7 @@ SearchError NativeEmbedder::init_safetensors(int device, const void* blob, uint6
         }
     }
     w.layers = lw.data();
-    if (device < 0) return SearchError{};   // parse only (callers that validate a blob without a device)
-    return init(device, cfg, w, linear_format);
+    return SearchError{};
 }
 
 }  // namespace fsgpu

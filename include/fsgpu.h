@@ -70,6 +70,7 @@ typedef int32_t fsgpu_status;
 typedef struct fsgpu_index fsgpu_index;     /* device-resident VectorIndex (lib.rs:819) */
 typedef struct fsgpu_m2v fsgpu_m2v;         /* Model2VecEmbedder (embed/src/model2vec_embedder.rs:55) */
 typedef struct fsgpu_bert fsgpu_bert;       /* NativeEmbedder (rerank/src/native_embedder.rs:40-50) */
+typedef struct fsgpu_reranker fsgpu_reranker; /* NativeReranker, the cross-encoder (rerank/src/native.rs:1240) */
 
 /* BERT shape (all-MiniLM-L6-v2: vocab 30522, hidden 384, layers 6, heads 12, inter 1536, max_pos 512,
  * ln_eps 1e-12; crates/frankensearch-rerank/src/native.rs:36-45).  heads*32 must equal hidden. */
@@ -537,6 +538,38 @@ uint32_t fsgpu_bert_dimension(const fsgpu_bert *m); /* Embedder::dimension: the 
  * fastembed_embedder.rs:416-426).  out is [n, hidden]. */
 fsgpu_status fsgpu_bert_embed(fsgpu_bert *m, const int32_t *ids, const uint32_t *offsets, uint32_t n, float *out);
 
+/* ---- MiniLM-class cross-encoder reranker ---- */
+/* NativeReranker (native.rs:1240): a BertForSequenceClassification with num_labels = 1 over `[CLS] query [SEP] doc [SEP]` pairs —
+ * typed embeddings, the encoder's layers (f16 matrix-core linears, as fsgpu_bert), the last layer for the [CLS] rows only
+ * (encoder_layer_cls, native.rs:628-700), pooled = tanh(W_p cls + b_p), logit = w_c . pooled + b_c (forward_batch, :956-1130).
+ * The encoder's shape rules are fsgpu_bert_create's; the reranker also needs hidden 128 / 256 / 384 (else FSGPU_ERR_INVALID_CONFIG).
+ * A pair's logit has the same bits whatever call, batch, order or position it is scored in. */
+typedef struct fsgpu_reranker_weights {
+    fsgpu_bert_weights bert;     /* bert.type_emb holds type_vocab rows */
+    uint32_t type_vocab;         /* token_type_embeddings rows (2 for BERT) */
+    const float *pooler_w;       /* bert.pooler.dense.weight [H, H] */
+    const float *pooler_b;       /* bert.pooler.dense.bias [H] */
+    const float *classifier_w;   /* classifier.weight [1, H] */
+    const float *classifier_b;   /* classifier.bias [1] */
+} fsgpu_reranker_weights;
+fsgpu_status fsgpu_reranker_create(int32_t device, const fsgpu_bert_config *config, const fsgpu_reranker_weights *weights,
+                                   fsgpu_reranker **out);
+/* The model file as a blob: fsgpu_bert_create_safetensors' rules (bare keys, F32 only, the blob checked before a device is looked
+ * for), plus bert.pooler.dense.{weight,bias} and classifier.{weight,bias}, which are required; a classifier with more than one output
+ * row is FSGPU_ERR_MODEL_LOAD_FAILED ("classifier: expected 1 logits, got N"). */
+fsgpu_status fsgpu_reranker_create_safetensors(int32_t device, const void *blob, uint64_t blob_len, float ln_eps,
+                                               fsgpu_reranker **out);
+void fsgpu_reranker_destroy(fsgpu_reranker *m);
+int32_t fsgpu_reranker_device(const fsgpu_reranker *m);
+uint32_t fsgpu_reranker_max_length(const fsgpu_reranker *m); /* min(max_position_embeddings, 512); 0 for NULL */
+/* Scores n pairs: pair i is ids[offsets[i]..offsets[i+1]) with type_ids alongside, already tokenised as [CLS] q [SEP] d [SEP] and
+ * truncated by the caller (native.rs:1652-1666).  out_logits / out_scores [n]: score = sigmoid(logit) when the logit is finite, else
+ * 0 (rerank_sync, native.rs:1631-1710).  An id >= vocab, a type id >= type_vocab or a pair longer than fsgpu_reranker_max_length is
+ * FSGPU_ERR_INVALID_CONFIG, reported before anything runs; n = 0 is OK and does nothing; a zero-length pair gets logit 0 and score
+ * 0.5 and changes nothing for the others.  Callers are served one at a time (native.rs:1668). */
+fsgpu_status fsgpu_reranker_score(fsgpu_reranker *m, const int32_t *ids, const int32_t *type_ids, const uint32_t *offsets, uint32_t n,
+                                  float *out_logits, float *out_scores);
+
 /* ---- device-resident hand-offs: encoder -> search without the vectors crossing PCIe ---- */
 /* The reference's seam between the two is a host Vec<f32> (traits.rs:401-582 -> search.rs:192); on the GPU both ends live in HBM.
  * fsgpu_bert_embed_device / fsgpu_m2v_embed_device are fsgpu_bert_embed / fsgpu_m2v_embed with the [n, dim] output left in device
@@ -591,6 +624,26 @@ fsgpu_status fsgpu_rrf_fuse(const fsgpu_scored_doc *lexical, uint32_t n_lexical,
                             uint32_t n_semantic, double k, double lexical_weight, double semantic_weight,
                             int32_t tiebreak, uint32_t limit, uint32_t offset, fsgpu_fused_hit *out,
                             uint32_t *out_count);
+/* The rerank step after the model call (rerank_step_with_combine, crates/frankensearch-rerank/src/pipeline.rs:125-360).  candidates
+ * [n] arrive in fused order and are reordered in place; rerank_score NaN = None; index is the caller's tag.  has_text[i] (NULL = all)
+ * says whether candidate i has text; scores[n_scores] are the scores of the candidates WITH text inside the window
+ * min(n, top_k_rerank), in window order.  Unchanged (out_applied = 0) when n < min_candidates, when fewer than min_candidates of the
+ * window have text, or when n_scores is not that count.  Otherwise: the window's stale rerank scores are cleared, finite scores land
+ * on their candidates, and the window is sorted — PURE_REORDER: rerank score desc (non-finite as -inf), doc_id bytes asc;
+ * RRF_COMBINE: 1/(k + pre_rank) + 1/(k + rerank_rank) in f64 desc (ranks from 0, k = max(k, 1), a NaN k is 1), doc_id asc; a
+ * window under 2 keeps its order.  Candidates past the window keep theirs.  Host only, O(window log window). */
+typedef struct fsgpu_rerank_candidate {
+    const char *doc_id;
+    uint32_t doc_id_len;
+    float score;          /* the fused score (carried along) */
+    float rerank_score;   /* NaN = None */
+    uint32_t index;
+} fsgpu_rerank_candidate;
+#define FSGPU_RERANK_PURE_REORDER 0 /* RerankCombine::PureReorder */
+#define FSGPU_RERANK_RRF_COMBINE 1  /* RerankCombine::RrfCombine { k } */
+fsgpu_status fsgpu_rerank_apply(fsgpu_rerank_candidate *candidates, uint32_t n, const uint8_t *has_text, const float *scores,
+                                uint32_t n_scores, uint32_t top_k_rerank, uint32_t min_candidates, int32_t combine, float k,
+                                uint8_t *out_applied);
 /* blend_two_tier (crates/frankensearch-fusion/src/blend.rs:107-195): per-list min-max normalisation,
  * alpha*quality + (1-alpha)*fast (single-source docs keep their normalised score), order (score desc, doc_id asc).
  * out holds n_fast + n_quality entries. */
