@@ -150,6 +150,13 @@ SIGNATURES = {
     "fsgpu_reranker_max_length": (_u32, [_vp]),
     "fsgpu_reranker_score": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "fsgpu_rerank_apply": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, C.c_float, _vp]),
+    "fsgpu_mmr_config_default": (_i32, [_vp]),
+    "fsgpu_mmr_rerank": (_i32, [_vp, _vp, _vp, _u32, _u32, C.c_double, _u32, _vp, C.POINTER(_u32), _vp]),
+    "fsgpu_index_vector_at_f32": (_i32, [_vp, _u32, _vp]),
+    "fsgpu_index_mmr_rerank": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), _vp]),
+    "fsgpu_index_mmr_rerank_batched": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "fsgpu_index_mmr_rerank_docs": (_i32, [_vp, _vp, _u32, _vp, _vp, C.POINTER(C.c_uint8)]),
+    "fsgpu_two_tier_mmr_rerank": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(C.c_uint8)]),
     "fsgpu_rrf_fuse": (_i32, [_vp, _u32, _vp, _u32, C.c_double, C.c_double, C.c_double, _i32, _u32, _u32, _vp,
                               C.POINTER(_u32)]),
     "fsgpu_blend_two_tier": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32)]),

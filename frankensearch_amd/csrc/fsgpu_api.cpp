@@ -1185,6 +1185,103 @@ fsgpu_status fsgpu_quality_scores_for_hits_batched(fsgpu_index* fast, fsgpu_inde
     });
 }
 
+// fsgpu_mmr_config: NULL = the reference's defaults (disabled, lambda 0.7, pool 30); enabled 0 / 1 and zero reserved words
+fsgpu_status mmr_config_of(const fsgpu_mmr_config* config, fsgpu_mmr_config* out) {
+    fsgpu_mmr_config_default(out);
+    if (!config) return FSGPU_OK;
+    for (uint32_t r : config->reserved)
+        if (r != 0) return fail(FSGPU_ERR_INVALID_CONFIG, "fsgpu_mmr_config: reserved words must be 0");
+    if (config->enabled > 1) return fail(FSGPU_ERR_INVALID_CONFIG, "fsgpu_mmr_config: enabled must be 0 or 1");
+    *out = *config;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_index_vector_at_f32(fsgpu_index* idx, uint32_t row, float* out) {
+    if (!idx || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.vector_at_f32(row, out));
+    });
+}
+
+fsgpu_status fsgpu_index_mmr_rerank_batched(fsgpu_index* idx, const uint32_t* rows, const double* scores, const uint32_t* offsets, uint32_t nq,
+                                            uint32_t k, const fsgpu_mmr_config* config, uint32_t* out_order, uint32_t* out_counts) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    fsgpu_mmr_config cfg;
+    if (fsgpu_status st = mmr_config_of(config, &cfg)) return st;
+    if (nq && (!offsets || !out_counts)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (nq && offsets[nq] && (!rows || !scores || !out_order)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.mmr_rerank_rows(rows, scores, offsets, nq, k, cfg.lambda, cfg.candidate_pool, nullptr, nullptr, 0, out_order,
+                                                out_counts, nullptr));
+    });
+}
+
+fsgpu_status fsgpu_index_mmr_rerank(fsgpu_index* idx, const uint32_t* rows, const double* scores, uint32_t n, uint32_t k,
+                                    const fsgpu_mmr_config* config, uint32_t* out_order, uint32_t* out_count, double* out_sims) {
+    if (!idx || !out_count) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out_count = 0;
+    fsgpu_mmr_config cfg;
+    if (fsgpu_status st = mmr_config_of(config, &cfg)) return st;
+    if (n && (!rows || !scores || !out_order)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const uint32_t offsets[2] = {0, n};
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.mmr_rerank_rows(rows, scores, offsets, 1, k, cfg.lambda, cfg.candidate_pool, nullptr, nullptr, 0, out_order,
+                                                out_count, out_sims));
+    });
+}
+
+fsgpu_status fsgpu_index_mmr_rerank_docs(fsgpu_index* idx, const fsgpu_scored_doc* docs, uint32_t n, const fsgpu_mmr_config* config,
+                                         uint32_t* out_order, uint8_t* out_applied) {
+    if (!idx || !out_applied) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out_applied = 0;
+    fsgpu_mmr_config cfg;
+    if (fsgpu_status st = mmr_config_of(config, &cfg)) return st;
+    if (n && (!docs || !out_order)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::vector<const char*> ids(n);
+        std::vector<uint32_t> lens(n);
+        std::vector<float> scores(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!docs[i].doc_id && docs[i].doc_id_len) return fail(FSGPU_ERR_NULL_ARGUMENT, "doc id is null");
+            ids[i] = docs[i].doc_id ? docs[i].doc_id : "";
+            lens[i] = docs[i].doc_id_len;
+            scores[i] = docs[i].score;
+        }
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.mmr_rerank_docs(ids.data(), lens.data(), scores.data(), n, cfg.enabled != 0, cfg.lambda, cfg.candidate_pool,
+                                                out_order, out_applied));
+    });
+}
+
+fsgpu_status fsgpu_two_tier_mmr_rerank(fsgpu_index* fast, fsgpu_index* quality, const fsgpu_alignment* alignment, const fsgpu_scored_doc* hits,
+                                       uint32_t n, const fsgpu_mmr_config* config, uint32_t* out_order, uint8_t* out_applied) {
+    if (!fast || !quality || !alignment || !out_applied) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out_applied = 0;
+    fsgpu_mmr_config cfg;
+    if (fsgpu_status st = mmr_config_of(config, &cfg)) return st;
+    if (n && (!hits || !out_order)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::vector<fsgpu::HitRef> refs(n);
+        std::vector<float> scores(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            refs[i] = fsgpu::HitRef{hits[i].doc_id, hits[i].doc_id_len, hits[i].index};
+            scores[i] = hits[i].score;
+        }
+        std::shared_lock<std::shared_mutex> lf(fast->state_mu);
+        std::shared_lock<std::shared_mutex> lq(quality->state_mu, std::defer_lock);
+        if (quality != fast) lq.lock();
+        return finish(fsgpu::two_tier_mmr_rerank(fast->impl, quality->impl, alignment->impl, refs.data(), scores.data(), n, cfg.enabled != 0,
+                                                 cfg.lambda, cfg.candidate_pool, out_order, out_applied));
+    });
+}
+
 // The same pairing over two row-sharded handles: the walk runs over their catalogs (fsgpu_sharded_open_fsvi) — raw shards pair by
 // row —, the re-scoring gathers dot_query_at on the shards that own the quality rows (fsgpu_sharded_gather_dot).
 fsgpu_status fsgpu_sharded_alignment_create(fsgpu_sharded* fast, fsgpu_sharded* quality, fsgpu_alignment** out) {

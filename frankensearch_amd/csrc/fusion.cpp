@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/fsgpu.h"
+#include "mmr.hpp"
 
 namespace {
 
@@ -363,5 +364,146 @@ extern "C" fsgpu_status fsgpu_rerank_apply(fsgpu_rerank_candidate* candidates, u
         for (uint32_t i = 0; i < window; ++i) candidates[i] = snap[order[i]];
     }
     if (out_applied) *out_applied = 1;
+    return FSGPU_OK;
+}
+
+// ---- Maximum Marginal Relevance: mmr_rerank (crates/frankensearch-fusion/src/mmr.rs:103-319), every value in f64 ----
+// (this file is built with -ffp-contract=off: `acc += a * b` stays a multiply and an add, as rustc emits it; the products are exact
+// in f64 either way, the ORDER of the additions is what the bits depend on)
+namespace fsgpu {
+
+namespace {
+constexpr double kF64Epsilon = std::numeric_limits<double>::epsilon();
+
+// cosine_sim (mmr.rs:254-279): the ragged-pool form, one accumulator each for the dot and both norms over the shorter length
+double mmr_cosine_sim(const float* a, uint32_t la, const float* b, uint32_t lb) {
+    const uint32_t len = std::min(la, lb);
+    if (len == 0) return 0.0;
+    double dot = 0.0, norm_a = 0.0, norm_b = 0.0;
+    for (uint32_t i = 0; i < len; ++i) {
+        const double ai = (double)a[i], bi = (double)b[i];
+        dot += ai * bi;
+        norm_a += ai * ai;
+        norm_b += bi * bi;
+    }
+    const double denom = std::sqrt(norm_a) * std::sqrt(norm_b);
+    if (denom < kF64Epsilon) return 0.0;
+    return dot / denom;
+}
+
+// cosine_sim_pre (mmr.rs:285-319): four accumulators, element i to acc[i % 4], ((a0 + a1) + a2) + a3, the tail in order
+double mmr_cosine_sim_pre(const float* a, const float* b, uint32_t len, double root_a, double root_b) {
+    if (len == 0) return 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const uint32_t chunks = len / 4;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const uint32_t i = c * 4;
+        acc[0] += (double)a[i] * (double)b[i];
+        acc[1] += (double)a[i + 1] * (double)b[i + 1];
+        acc[2] += (double)a[i + 2] * (double)b[i + 2];
+        acc[3] += (double)a[i + 3] * (double)b[i + 3];
+    }
+    double dot = ((acc[0] + acc[1]) + acc[2]) + acc[3];
+    for (uint32_t i = chunks * 4; i < len; ++i) dot += (double)a[i] * (double)b[i];
+    const double denom = root_a * root_b;
+    if (denom < kF64Epsilon) return 0.0;
+    return dot / denom;
+}
+}  // namespace
+
+double mmr_clamped_lambda(double lambda) {
+    if (!std::isfinite(lambda) || lambda < 0.0) return 0.0;
+    return lambda > 1.0 ? 1.0 : lambda;
+}
+
+void mmr_rerank_host(const double* scores, const float* const* vectors, const uint32_t* lengths, uint32_t len, uint32_t k, double lambda_in,
+                     uint32_t candidate_pool, uint32_t* out_order, uint32_t* out_count, double* out_sims) {
+    *out_count = 0;
+    const uint32_t n = std::min(len, candidate_pool);
+    if (n == 0 || k == 0) return;
+    k = std::min(k, n);
+    const double lambda = mmr_clamped_lambda(lambda_in), diversity_weight = 1.0 - lambda;
+    double min_score = std::numeric_limits<double>::infinity(), max_score = -std::numeric_limits<double>::infinity();
+    for (uint32_t i = 0; i < n; ++i)
+        if (std::isfinite(scores[i])) {
+            min_score = scores[i] < min_score ? scores[i] : min_score;
+            max_score = scores[i] > max_score ? scores[i] : max_score;
+        }
+    const double score_range = max_score - min_score;
+    std::vector<double> norm_scores(n);
+    for (uint32_t i = 0; i < n; ++i)
+        norm_scores[i] = !std::isfinite(scores[i]) ? 0.0 : score_range < kF64Epsilon ? 1.0 : (scores[i] - min_score) / score_range;
+    bool uniform = true;
+    for (uint32_t i = 0; i < n; ++i) uniform = uniform && lengths[i] == lengths[0];
+    std::vector<double> root(uniform ? n : 0);
+    for (uint32_t i = 0; uniform && i < n; ++i) {
+        double norm = 0.0;
+        for (uint32_t e = 0; e < lengths[i]; ++e) {
+            const double x = (double)vectors[i][e];
+            norm += x * x;
+        }
+        root[i] = std::sqrt(norm);
+    }
+    auto sim = [&](uint32_t i, uint32_t j) {
+        return uniform ? mmr_cosine_sim_pre(vectors[i], vectors[j], lengths[0], root[i], root[j])
+                       : mmr_cosine_sim(vectors[i], lengths[i], vectors[j], lengths[j]);
+    };
+    if (out_sims)
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j = 0; j < n; ++j) out_sims[(size_t)i * n + j] = sim(i, j);
+    uint32_t first = 0;
+    double best_s = -std::numeric_limits<double>::infinity();
+    for (uint32_t i = 0; i < n; ++i)
+        if (norm_scores[i] > best_s) first = i, best_s = norm_scores[i];
+    std::vector<uint8_t> remaining(n, 1);
+    uint32_t count = 0;
+    out_order[count++] = first;
+    remaining[first] = 0;
+    std::vector<double> max_sim(n, -std::numeric_limits<double>::infinity());
+    for (uint32_t i = 0; i < n; ++i)
+        if (remaining[i]) max_sim[i] = sim(i, first);
+    for (uint32_t round = 1; round < k; ++round) {
+        uint32_t best_idx = 0xffffffffu;
+        double best_mmr = -std::numeric_limits<double>::infinity();
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!remaining[i]) continue;
+            const double mmr = std::fma(lambda, norm_scores[i], -(diversity_weight * max_sim[i]));
+            if (mmr > best_mmr) best_mmr = mmr, best_idx = i;
+        }
+        if (best_idx == 0xffffffffu) break;
+        out_order[count++] = best_idx;
+        remaining[best_idx] = 0;
+        for (uint32_t i = 0; i < n; ++i)
+            if (remaining[i]) {
+                const double s = sim(i, best_idx);
+                if (s > max_sim[i]) max_sim[i] = s;
+            }
+    }
+    *out_count = count;
+}
+
+}  // namespace fsgpu
+
+extern "C" fsgpu_status fsgpu_mmr_config_default(fsgpu_mmr_config* config) {
+    if (!config) return FSGPU_ERR_NULL_ARGUMENT;
+    std::memset(config, 0, sizeof(*config));
+    config->lambda = 0.7;
+    config->candidate_pool = 30;
+    return FSGPU_OK;
+}
+
+extern "C" fsgpu_status fsgpu_mmr_rerank(const double* scores, const float* const* vectors, const uint32_t* lengths, uint32_t n, uint32_t k,
+                                         double lambda, uint32_t candidate_pool, uint32_t* out_order, uint32_t* out_count, double* out_sims) {
+    if (!out_count) return FSGPU_ERR_NULL_ARGUMENT;
+    *out_count = 0;
+    if (n && (!scores || !vectors || !lengths || !out_order)) return FSGPU_ERR_NULL_ARGUMENT;
+    const uint32_t pool = std::min(n, candidate_pool);
+    for (uint32_t i = 0; i < pool; ++i)
+        if (lengths[i] && !vectors[i]) return FSGPU_ERR_NULL_ARGUMENT;
+    try {
+        fsgpu::mmr_rerank_host(scores, vectors, lengths, n, k, lambda, candidate_pool, out_order, out_count, out_sims);
+    } catch (...) {
+        return FSGPU_ERR_DEVICE;   // host allocation failed
+    }
     return FSGPU_OK;
 }

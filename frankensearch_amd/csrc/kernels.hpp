@@ -427,4 +427,44 @@ hipError_t launch_bert_i8_add_ln_quant(float* x, const float* delta, const float
 hipError_t launch_bert_i8_gemm(const void* qa, const float* sa, const void* wp, const float* sw, const float* bias, float* out, int M,
                                int N, int K, bool gelu, hipStream_t stream);
 
+// mmr_kernels.hip: Maximum Marginal Relevance over slab rows, one workgroup per pool (mmr.rs:103-319 in f64, the reference's
+// accumulator order).  Pool q owns rows / scores / ovr_index / out_order [offsets[q], offsets[q + 1]).
+constexpr uint32_t kMmrMaxPool = 128, kMmrMaxDim = 1024, kMmrMaxElements = 64 * 1024;   // 128 x 384 and 64 x 1,024 both fit
+constexpr uint32_t kMmrLdsHeader = kMmrMaxPool * 8;     // the root norms
+constexpr uint32_t kMmrLdsBudget = 160 * 1024;
+// the pools the kernel answers; a larger one is left to the host restatement (same bits)
+__host__ __device__ inline bool mmr_device_pool(uint32_t n, uint32_t dim) {
+    return n <= kMmrMaxPool && dim >= 1 && dim <= kMmrMaxDim && n * dim <= kMmrMaxElements;
+}
+enum : int { kMmrStageLdsF16 = 0, kMmrStageLdsF32 = 1, kMmrStageGlobalF32 = 2 };
+struct MmrArgs {
+    const void* slab;             // the index's rows (f16 or f32)
+    u64 row_base;                 // global id of the slab's first row
+    uint32_t row_stride;          // bytes between rows
+    uint32_t dim;
+    uint32_t slab_f32;
+    uint32_t k, candidate_pool;
+    double lambda;                // already clamped (MmrConfig::clamped_lambda)
+    const uint32_t* rows;         // global row ids (not read where an override is given)
+    const uint32_t* offsets;      // [npools + 1]
+    const double* scores;
+    const int32_t* ovr_index;     // per candidate: >= 0 = its vector is ovr_vectors[index * dim ..] (a WAL entry); nullptr = none
+    const float* ovr_vectors;
+    uint32_t* out_order;          // indexes into the pool, in selection order
+    uint32_t* out_counts;         // [npools]; not written for a pool the kernel leaves to the host
+    double* sims;                 // nullptr: the n x n matrix lives in LDS; else pool q's matrix at sims[offsets[q] * sim_pitch]
+    uint32_t sim_pitch;
+    uint32_t lds_sims_offset;
+    float* vec_ws;                // kMmrStageGlobalF32: staged rows, pool q at vec_ws[offsets[q] * vec_stride]
+    uint32_t vec_stride;          // elements between staged rows
+};
+struct MmrPlan {
+    int storage = kMmrStageLdsF16;
+    uint32_t vec_stride = 0, lds_sims_offset = 0, lds_bytes = 0;
+    bool sims_global = false;
+};
+// max_n: the largest pool of the launch; f32_staging: an f32 slab, or any override vector; want_sims: the caller reads the matrix
+MmrPlan mmr_plan(uint32_t max_n, uint32_t dim, bool f32_staging, bool want_sims);
+hipError_t launch_mmr(const MmrArgs& args, uint32_t npools, const MmrPlan& plan, hipStream_t stream);
+
 }  // namespace fsgpu

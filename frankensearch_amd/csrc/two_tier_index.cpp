@@ -1,12 +1,14 @@
 // two_tier_index.cpp — see two_tier_index.hpp.
 #include "two_tier_index.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <string_view>
 #include <unordered_map>
 
 #include "../../include/fsgpu.h"
+#include "mmr.hpp"
 
 namespace fsgpu {
 
@@ -233,6 +235,98 @@ SearchError quality_scores_for_hits_batched(const VectorIndex& fast, VectorIndex
                                                  out_scores + h0, out_present + h0);
         if (!e2.ok()) return e2;
     }
+    return SearchError{};
+}
+
+SearchError two_tier_mmr_rerank(VectorIndex& fast, VectorIndex& quality, const QualityAlignment& align, const HitRef* hits,
+                                const float* scores, uint32_t n, bool enabled, double lambda, uint32_t candidate_pool, uint32_t* out_order,
+                                uint8_t* out_applied) {
+    *out_applied = 0;
+    for (uint32_t i = 0; i < n; ++i) out_order[i] = i;
+    if (!enabled || n < 2) return SearchError{};
+    const uint32_t pool = std::min(n, std::max(candidate_pool, 1u));
+    if (pool < 2) return SearchError{};
+    struct Source {
+        VectorIndex* tier = nullptr;
+        int64_t wal = -1, row = -1;
+    };
+    std::vector<Source> src(pool);
+    uint32_t from_quality = 0;
+    for (uint32_t i = 0; i < pool; ++i) {
+        const HitRef& h = hits[i];
+        Source& s = src[i];
+        const bool id = h.doc_id != nullptr;
+        int64_t fast_row = -1;
+        if (id && fast.has_doc_ids()) fast_row = fast.find_index_by_doc_id(h.doc_id, h.doc_id_len);
+        else if (!fast.has_doc_ids() && h.index != 0xffffffffu && h.index < fast.record_count()) fast_row = h.index;   // raw slabs pair by row
+        // quality_vector_for_doc_id (two_tier.rs:1852-1875)
+        if (id && quality.has_doc_ids() && (s.wal = quality.wal_latest(h.doc_id, h.doc_id_len)) >= 0) {
+            s.tier = &quality;
+        } else {
+            int64_t qrow = fast_row >= 0 ? align.quality_row((uint64_t)fast_row) : -1;
+            if (qrow >= 0 && (uint64_t)qrow >= quality.record_count())
+                return err(FSGPU_ERR_INVALID_CONFIG, "quality row " + std::to_string(qrow) + " out of range for vector_at_f32");
+            if (qrow < 0 && id && quality.has_doc_ids()) qrow = quality.find_index_by_doc_id(h.doc_id, h.doc_id_len);
+            if (qrow >= 0) {
+                s.tier = &quality;
+                s.row = qrow;
+            } else if (id && fast.has_doc_ids() && (s.wal = fast.wal_latest(h.doc_id, h.doc_id_len)) >= 0) {   // fast_vector_for_doc_id (:1832-1845)
+                s.tier = &fast;
+            } else if (fast_row >= 0) {
+                s.tier = &fast;
+                s.row = fast_row;
+            } else {
+                return SearchError{};   // no vector in either tier: the list stays as it is
+            }
+        }
+        from_quality += s.tier == &quality;
+    }
+    std::vector<double> wide(pool);
+    for (uint32_t i = 0; i < pool; ++i) wide[i] = (double)scores[i];
+    std::vector<uint32_t> order(pool);
+    uint32_t count = 0;
+    if (from_quality == pool || from_quality == 0) {
+        VectorIndex& tier = from_quality ? quality : fast;
+        std::vector<uint32_t> rows(pool, 0);
+        std::vector<int32_t> ovr(pool, -1);
+        std::vector<float> ovr_vectors;
+        uint32_t n_ovr = 0;
+        for (uint32_t i = 0; i < pool; ++i) {
+            if (src[i].wal >= 0) {
+                const std::vector<float>& v = tier.wal_vector((size_t)src[i].wal);
+                ovr_vectors.insert(ovr_vectors.end(), v.begin(), v.end());
+                ovr[i] = (int32_t)n_ovr++;
+            } else {
+                rows[i] = (uint32_t)src[i].row;
+            }
+        }
+        const uint32_t offsets[2] = {0, pool};
+        std::lock_guard<std::mutex> lock(tier.mutex());
+        SearchError e = tier.mmr_rerank_rows(rows.data(), wide.data(), offsets, 1, pool, lambda, candidate_pool, n_ovr ? ovr.data() : nullptr,
+                                             ovr_vectors.data(), n_ovr, order.data(), &count, nullptr);
+        if (!e.ok()) return e;
+    } else {
+        std::vector<std::vector<float>> vecs(pool);
+        std::vector<const float*> ptrs(pool);
+        std::vector<uint32_t> lens(pool);
+        for (uint32_t i = 0; i < pool; ++i) {
+            VectorIndex& tier = *src[i].tier;
+            if (src[i].wal >= 0) {
+                vecs[i] = tier.wal_vector((size_t)src[i].wal);
+            } else {
+                vecs[i].resize(tier.dimension());
+                std::lock_guard<std::mutex> lock(tier.mutex());
+                SearchError e = tier.vector_at_f32((uint32_t)src[i].row, vecs[i].data());
+                if (!e.ok()) return e;
+            }
+            ptrs[i] = vecs[i].data();
+            lens[i] = (uint32_t)vecs[i].size();
+        }
+        mmr_rerank_host(wide.data(), ptrs.data(), lens.data(), pool, pool, lambda, candidate_pool, order.data(), &count, nullptr);
+    }
+    if (count != pool) return SearchError{};
+    std::copy(order.begin(), order.end(), out_order);
+    *out_applied = 1;
     return SearchError{};
 }
 

@@ -66,4 +66,14 @@ SearchError quality_scores_for_hits_batched(const VectorIndex& fast, VectorIndex
                                             uint32_t nq, uint32_t query_len, const HitRef* hits, const uint32_t* hit_offsets, float* out_scores,
                                             uint8_t* out_present);
 
+// The searcher's MMR stage over a fast / quality pair (searcher.rs:2696-2745; semantic_vector_with_tier_for_doc_id,
+// two_tier.rs:1832-1925): each document of the pool takes its quality-tier vector (quality WAL, aligned quality row of its live fast
+// row, the quality index's own row), else its fast-tier vector (fast WAL, live fast row).  One tier for the whole pool: that
+// tier's mmr_rerank_rows (device).  Mixed tiers: the vectors are fetched and mmr_rerank_host runs (ragged if the dimensions differ).
+// Takes the mutex of the index it runs on.  out_order[n]: the pool's MMR order then the tail in place; identity and
+// *out_applied = 0 when nothing is to be done or a document has no vector.
+SearchError two_tier_mmr_rerank(VectorIndex& fast, VectorIndex& quality, const QualityAlignment& align, const HitRef* hits,
+                                const float* scores, uint32_t n, bool enabled, double lambda, uint32_t candidate_pool, uint32_t* out_order,
+                                uint8_t* out_applied);
+
 }  // namespace fsgpu

@@ -181,6 +181,20 @@ class VectorIndex {
     int64_t wal_latest(const char* doc_id, uint32_t len) const;
     float wal_dot(size_t wal_index, const float* query) const;
     const std::string& wal_doc_id(size_t wal_index) const { return wal_[wal_index].doc_id; }
+    const std::vector<float>& wal_vector(size_t wal_index) const { return wal_[wal_index].embedding; }
+
+    // VectorIndex::vector_at_f32 (lib.rs:3142): one row of the slab widened to f32 (out holds dimension() values)
+    SearchError vector_at_f32(uint32_t row, float* out);
+    // mmr_rerank (crates/frankensearch-fusion/src/mmr.rs:103-319) over rows of this slab, ONE launch for nq pools (mmr_kernels.hip):
+    // pool q owns rows / scores / ovr_index / out_order [offsets[q], offsets[q + 1]).  ovr_index (nullable): >= 0 = the candidate's
+    // vector is ovr_vectors[index * dim ..] (a WAL entry), its row is not read.  out_sims (nullable, nq == 1): the pool x pool
+    // matrix.  Pools beyond mmr_device_pool run the host restatement on vectors fetched from the slab (same bits).
+    SearchError mmr_rerank_rows(const uint32_t* rows, const double* scores, const uint32_t* offsets, uint32_t nq, uint32_t k, double lambda,
+                                uint32_t candidate_pool, const int32_t* ovr_index, const float* ovr_vectors, uint32_t n_ovr,
+                                uint32_t* out_order, uint32_t* out_counts, double* out_sims);
+    // the searcher's stage over this index alone (searcher.rs:2696-2745; fsgpu_index_mmr_rerank_docs)
+    SearchError mmr_rerank_docs(const char* const* doc_ids, const uint32_t* doc_id_lens, const float* scores, uint32_t n, bool enabled,
+                                double lambda, uint32_t candidate_pool, uint32_t* out_order, uint8_t* out_applied);
 
     std::mutex& mutex() { return mu_; }
     int device() const { return device_; }
@@ -340,6 +354,7 @@ class VectorIndex {
         ws_cand_rows_, ws_cand_scores_, mf_max_norm_, mf_qh_, mf_delta_, mf_tau_, mf_cand_, mf_dense_, mf_sel_,
         mf_fallback_, mf_fallback2_, mf_spill_, mf_io_, mf_io2_, i8_stats_, n4u_slab_, mf_cand_count_, ws_pairs_;
     DeviceBuffer ws_out_;   // rows | scores | counts of a blocking batched search (one block: one copy up)
+    DeviceBuffer ws_mmr_in_, ws_mmr_out_, ws_mmr_sims_, ws_mmr_vec_;   // mmr_rerank_rows: inputs (one copy down), order | counts, matrix, staged rows
     bool i8_ready_ = false, n4_ready_ = false, i8_stats_ready_ = false, n4u_ready_ = false;
     bool quant_max_ready_ = false;   // i8_max_ holds a corpus-wide max-abs handed in by a sharded index: the quantisers keep it
     u64* tp_approx_out_ = nullptr;   // two_pass_candidates_device: where the batch in flight leaves its candidate pairs

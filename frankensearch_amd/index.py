@@ -341,6 +341,57 @@ class VectorIndex:
         check(_lib.lib().fsgpu_gather_dot(self._h, _ptr(q), q.size, _ptr(r), r.size, _ptr(out)))
         return out
 
+    def vector_at(self, row: int) -> np.ndarray:
+        """VectorIndex::vector_at_f32 (lib.rs:3142): one row of the slab widened to f32."""
+        out = np.empty(self.dimension(), dtype=np.float32)
+        check(_lib.lib().fsgpu_index_vector_at_f32(self._h, int(row), _ptr(out)))
+        return out
+
+    def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
+        """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes
+        into `rows` (and the pool x pool f64 similarity matrix with want_sims)."""
+        from .mmr import MmrConfig
+        cfg = (config or MmrConfig())._c()
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        s = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        if r.size != s.size:
+            raise ValueError("scores and rows must have the same length")
+        order = np.zeros(max(r.size, 1), dtype=np.uint32)
+        count = C.c_uint32(0)
+        pool = min(r.size, cfg.candidate_pool)
+        sims = np.zeros((pool, pool), dtype=np.float64) if want_sims else None
+        check(_lib.lib().fsgpu_index_mmr_rerank(self._h, _ptr(r), _ptr(s), r.size, k, C.addressof(cfg), _ptr(order), C.byref(count),
+                                                _ptr(sims) if want_sims and pool else None))
+        got = order[:count.value].copy()
+        return (got, sims) if want_sims else got
+
+    def mmr_rerank_batched(self, rows: np.ndarray, scores: np.ndarray, offsets: np.ndarray, k: int, config=None) -> List[np.ndarray]:
+        """fsgpu_index_mmr_rerank_batched: pool q owns rows / scores [offsets[q], offsets[q + 1]); ONE launch for all pools."""
+        from .mmr import MmrConfig
+        cfg = (config or MmrConfig())._c()
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        s = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        nq = o.size - 1
+        if nq < 0 or r.size != s.size or (nq >= 0 and int(o[-1]) != r.size):
+            raise ValueError("offsets must have nq + 1 entries and end at the number of rows")
+        order = np.zeros(max(r.size, 1), dtype=np.uint32)
+        counts = np.zeros(max(nq, 1), dtype=np.uint32)
+        check(_lib.lib().fsgpu_index_mmr_rerank_batched(self._h, _ptr(r), _ptr(s), _ptr(o), nq, k, C.addressof(cfg), _ptr(order),
+                                                        _ptr(counts)))
+        return [order[int(o[q]):int(o[q]) + int(counts[q])].copy() for q in range(nq)]
+
+    def mmr_rerank_docs(self, docs: Sequence[Tuple[str, float]], config) -> Tuple[List[int], bool]:
+        """fsgpu_index_mmr_rerank_docs: the searcher's MMR stage (searcher.rs:2696-2745) over (doc_id, score) in rank order.  Returns
+        (order over the whole list, applied)."""
+        from . import fusion
+        cfg = config._c()
+        arr, keep = fusion._pack([(d[0], d[1]) for d in docs])
+        order = np.zeros(max(len(docs), 1), dtype=np.uint32)
+        applied = C.c_uint8(0)
+        check(_lib.lib().fsgpu_index_mmr_rerank_docs(self._h, arr, len(docs), C.addressof(cfg), _ptr(order), C.byref(applied)))
+        return [int(i) for i in order[:len(docs)]], bool(applied.value)
+
     # device-pointer path (torch tensors): everything stays in HBM, enqueued on `stream`
     def search_device(self, queries_ptr: int, nq: int, limit: int, out_rows_ptr: int, out_scores_ptr: int,
                       out_counts_ptr: int, stream: int = 0, allow_ptr: Optional[int] = None) -> None:

@@ -87,6 +87,19 @@ class TwoTierIndex:
                  present.ctypes.data))
         return [float(scores[i]) if present[i] else None for i in range(len(hits))]
 
+    def mmr_rerank(self, hits: Sequence[Tuple], config) -> Tuple[List[int], bool]:
+        """fsgpu_two_tier_mmr_rerank: the searcher's MMR stage over (doc_id, score[, fast row]) in rank order — quality-tier vectors
+        first, the fast tier's for a document without one.  Returns (order over the whole list, applied)."""
+        if self.sharded:
+            raise TypeError("MMR over row-sharded handles is not supported: a pool's rows sit on several GPUs")
+        cfg = config._c()
+        arr, keep = fusion._pack([(h[0], h[1], h[2] if len(h) > 2 else 0xFFFFFFFF) for h in hits])
+        order = np.zeros(max(len(hits), 1), dtype=np.uint32)
+        applied = C.c_uint8(0)
+        check(_lib.lib().fsgpu_two_tier_mmr_rerank(self.fast._h, self.quality._h, self._a, arr, len(hits), C.addressof(cfg),
+                                                   order.ctypes.data, C.byref(applied)))
+        return [int(i) for i in order[:len(hits)]], bool(applied.value)
+
     def quality_scores_for_hits_batched(self, queries: np.ndarray, hit_lists: Sequence[Sequence[Tuple[str, float, int]]]) -> List[List[Optional[float]]]:
         """fsgpu_quality_scores_for_hits_batched: quality_scores_for_hits for a chunk of queries, ONE gather launch (unsharded pairs)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
@@ -142,7 +155,9 @@ class SyncTwoTierSearcher:
         return [(self.doc_id_of(int(rows[0, i])), float(scores[0, i]), int(rows[0, i])) for i in range(n)]
 
     def search(self, fast_token_ids: Sequence[int], quality_token_ids: Sequence[int], k: int,
-               lexical: Optional[Sequence[Tuple[str, float]]] = None) -> SearchOutcome:
+               lexical: Optional[Sequence[Tuple[str, float]]] = None, mmr=None) -> SearchOutcome:
+        """mmr: an MmrConfig; when enabled, the final results pass through the MMR stage (searcher.rs:2696-2745) over the pair's
+        document vectors.  Absent or disabled, the outcome is exactly what it is without the argument."""
         cfg = self.config
         fetch = max(k * max(cfg.candidate_multiplier, 1), k)   # candidate_count (rrf.rs:113-115)
         m = TwoTierMetrics()
@@ -173,4 +188,9 @@ class SyncTwoTierSearcher:
         t7 = time.perf_counter()
         m.quality_embed_ms, m.quality_search_ms = (t4 - t3) * 1e3, (t5 - t4) * 1e3
         m.blend_ms, m.phase2_total_ms = (t6 - t5) * 1e3, (t7 - t3) * 1e3
+        if mmr is not None and mmr.enabled and len(final) > 1:
+            from .mmr import mmr_step
+            pair = self.pair or TwoTierIndex(self.fast_index, self.quality_index)
+            final, _ = mmr_step([(h.doc_id, h.rrf_score, h) for h in final], pair, mmr, row_of=lambda t: t[2].semantic_index)
+            final = [h[2] for h in final]
         return SearchOutcome(initial, final, fast_hits, quality_hits, blended, m)

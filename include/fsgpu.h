@@ -700,6 +700,66 @@ fsgpu_status fsgpu_sharded_quality_scores_for_hits(fsgpu_sharded *fast, fsgpu_sh
                                                    const float *query, uint32_t query_len, const fsgpu_scored_doc *hits, uint32_t n,
                                                    float *out_scores, uint8_t *out_present);
 
+/* ---- MMR: diversified reranking over document vectors ---- */
+/* Maximum Marginal Relevance exactly as the reference states it (crates/frankensearch-fusion/src/mmr.rs:103-319; the stage after
+ * the rerank step in TwoTierSearcher, searcher.rs:2696-2745).  All arithmetic is f64: n = min(len, candidate_pool), k = min(k, n);
+ * relevance is min-max normalised over the pool's finite scores (non-finite -> 0, a range below f64::EPSILON -> 1); sim(i, j) is
+ * cosine_sim_pre — four accumulators, element e to acc[e % 4], ((a0 + a1) + a2) + a3, the tail in order, divided by the product of
+ * the root norms (one sequential accumulator each), 0 when that product is below f64::EPSILON —, or cosine_sim (one accumulator
+ * each) when the pool's vectors differ in length; the first pick is the first greatest relevance, then greedy rounds of
+ * fma(lambda, relevance, -((1 - lambda) * max sim to the selected)) with a strict `>` (lowest index wins a tie), ending early when
+ * no candidate beats -inf.  The order is a list of indexes into the pool.
+ * MmrConfig (mmr.rs:43-66): defaults enabled = 0, lambda = 0.7, candidate_pool = 30 (fsgpu_mmr_config_default).  lambda is clamped
+ * (non-finite or negative -> 0, above 1 -> 1).  enabled must be 0 or 1 and the reserved words 0, else FSGPU_ERR_INVALID_CONFIG.
+ * A NULL config means the defaults. */
+typedef struct fsgpu_mmr_config {
+    uint32_t enabled;
+    uint32_t candidate_pool;
+    double lambda;
+    uint32_t reserved[4]; /* must be 0 */
+} fsgpu_mmr_config;
+fsgpu_status fsgpu_mmr_config_default(fsgpu_mmr_config *config);
+/* mmr_rerank on caller-supplied f32 vectors (vectors[i] holds lengths[i] values; ragged pools allowed), on the host: no device is
+ * needed.  out_order holds min(k, n, candidate_pool) entries, *out_count says how many were selected; out_sims (may be NULL) receives
+ * the pool x pool matrix of sim(i, j), pool = min(n, candidate_pool).  This is also what the index-level calls below run for a
+ * pool the kernel does not take, with the same bits. */
+fsgpu_status fsgpu_mmr_rerank(const double *scores, const float *const *vectors, const uint32_t *lengths, uint32_t n, uint32_t k,
+                              double lambda, uint32_t candidate_pool, uint32_t *out_order, uint32_t *out_count, double *out_sims);
+/* VectorIndex::vector_at_f32 (crates/frankensearch-index/src/lib.rs:3142): row `row` of the slab widened to f32; out holds
+ * dimension values.  An out-of-range row is FSGPU_ERR_INVALID_CONFIG. */
+fsgpu_status fsgpu_index_vector_at_f32(fsgpu_index *idx, uint32_t row, float *out);
+/* mmr_rerank over rows of one index, on its device (mmr_kernels.hip: one workgroup per pool; the rows are gathered from the slab
+ * where they are, only scores go up and indexes come back).  rows[n] are global row ids, scores[n] their relevance; config's
+ * lambda and candidate_pool apply (enabled is not consulted: as mmr_rerank itself, the caller decides whether to call).  out_order
+ * holds n entries of which the first *out_count are written.  out_sims (may be NULL) receives the pool x pool similarity matrix.
+ * The batched form takes nq pools — pool q owns rows / scores / out_order [offsets[q], offsets[q + 1]) — in ONE launch; a pool's
+ * order is the same whatever batch it rides in.  Pools of up to 128 rows at up to 384 dimensions and up to 64 rows at up to 1,024
+ * (rows * dimension <= 65,536) run on the device; a larger pool runs fsgpu_mmr_rerank on vectors fetched from the slab, with the
+ * same bits.  A row out of range is FSGPU_ERR_INVALID_CONFIG.  Row-sharded handles (fsgpu_sharded) have no MMR call: a pool's rows
+ * sit on several GPUs. */
+fsgpu_status fsgpu_index_mmr_rerank(fsgpu_index *idx, const uint32_t *rows, const double *scores, uint32_t n, uint32_t k,
+                                    const fsgpu_mmr_config *config, uint32_t *out_order, uint32_t *out_count, double *out_sims);
+fsgpu_status fsgpu_index_mmr_rerank_batched(fsgpu_index *idx, const uint32_t *rows, const double *scores, const uint32_t *offsets,
+                                            uint32_t nq, uint32_t k, const fsgpu_mmr_config *config, uint32_t *out_order,
+                                            uint32_t *out_counts);
+/* The searcher's MMR stage over one index (searcher.rs:2696-2745).  docs[n] is the result list in rank order (doc id and f32 score;
+ * index is not read).  Nothing happens (identity order, *out_applied = 0) when config is not enabled, n < 2 or the pool
+ * min(n, max(candidate_pool, 1)) is below 2.  Each document of the pool resolves as quality_vector_for_doc_id does within one index
+ * (two_tier.rs:1857-1872): its newest WAL entry, else the first live main row with that id; a document that resolves to nothing
+ * leaves the list untouched (identity, *out_applied = 0), and so does a selection shorter than the pool.  Otherwise out_order[n] is
+ * the MMR order of the pool (k = pool, scores widened to f64) followed by the tail in place, and *out_applied = 1.  WAL vectors
+ * travel to the kernel as per-candidate overrides.  The index needs a doc-id table. */
+fsgpu_status fsgpu_index_mmr_rerank_docs(fsgpu_index *idx, const fsgpu_scored_doc *docs, uint32_t n, const fsgpu_mmr_config *config,
+                                         uint32_t *out_order, uint8_t *out_applied);
+/* The same stage over a fast / quality pair (semantic_vector_with_tier_for_doc_id, two_tier.rs:1832-1925): per document the
+ * quality tier first — the quality WAL's newest entry, the aligned quality row of its live fast row, the quality index's own row —
+ * then the fast tier (its WAL, its live row).  Raw slabs without doc-id tables resolve hits[i].index as the fast row.  When every
+ * vector comes from one tier the pool runs on that tier's device; a pool that mixes tiers is fetched (fsgpu_index_vector_at_f32)
+ * and runs fsgpu_mmr_rerank, ragged if the tiers' dimensions differ.  Outputs as fsgpu_index_mmr_rerank_docs. */
+fsgpu_status fsgpu_two_tier_mmr_rerank(fsgpu_index *fast, fsgpu_index *quality, const fsgpu_alignment *alignment,
+                                       const fsgpu_scored_doc *hits, uint32_t n, const fsgpu_mmr_config *config, uint32_t *out_order,
+                                       uint8_t *out_applied);
+
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */
 typedef struct fsgpu_mrl_stats {
