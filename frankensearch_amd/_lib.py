@@ -157,6 +157,12 @@ SIGNATURES = {
     "fsgpu_index_mmr_rerank_batched": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "fsgpu_index_mmr_rerank_docs": (_i32, [_vp, _vp, _u32, _vp, _vp, C.POINTER(C.c_uint8)]),
     "fsgpu_two_tier_mmr_rerank": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(C.c_uint8)]),
+    "fsgpu_hubness_config_default": (_i32, [_vp]),
+    "fsgpu_query_hubness": (_i32, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "fsgpu_apply_hubness_penalty": (_i32, [_vp, _u32, _vp, _u64, _vp, _i32, C.POINTER(C.c_uint8)]),
+    "fsgpu_index_compute_query_hubness": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    "fsgpu_sharded_compute_query_hubness": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    "fsgpu_lab_index_query_hubness_topk": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     "fsgpu_rrf_fuse": (_i32, [_vp, _u32, _vp, _u32, C.c_double, C.c_double, C.c_double, _i32, _u32, _u32, _vp,
                               C.POINTER(_u32)]),
     "fsgpu_blend_two_tier": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32)]),

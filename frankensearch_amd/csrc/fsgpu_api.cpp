@@ -1282,6 +1282,42 @@ fsgpu_status fsgpu_two_tier_mmr_rerank(fsgpu_index* fast, fsgpu_index* quality, 
     });
 }
 
+static fsgpu_status index_query_hubness(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out,
+                                        float* out_topk) {
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (idx->impl.record_count() && !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    if (nq && !queries) return fail(FSGPU_ERR_NULL_ARGUMENT, "queries is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.compute_query_hubness(queries, nq, query_dim, kq, out, out_topk));
+    });
+}
+
+fsgpu_status fsgpu_index_compute_query_hubness(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                               float* out) {
+    return index_query_hubness(idx, queries, nq, query_dim, kq, out, nullptr);
+}
+
+fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                                float* out, float* out_topk) {
+    if (idx && idx->impl.record_count() && !out_topk) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_topk is null");
+    return index_query_hubness(idx, queries, nq, query_dim, kq, out, out_topk);
+}
+
+fsgpu_status fsgpu_sharded_compute_query_hubness(fsgpu_sharded* sh, const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                                 float* out) {
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!sh) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (sh->impl.record_count() && !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    if (nq && !queries) return fail(FSGPU_ERR_NULL_ARGUMENT, "queries is null");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(sh->impl.mutex());
+        return finish(sh->impl.compute_query_hubness(queries, nq, query_dim, kq, out));
+    });
+}
+
 // The same pairing over two row-sharded handles: the walk runs over their catalogs (fsgpu_sharded_open_fsvi) — raw shards pair by
 // row —, the re-scoring gathers dot_query_at on the shards that own the quality rows (fsgpu_sharded_gather_dot).
 fsgpu_status fsgpu_sharded_alignment_create(fsgpu_sharded* fast, fsgpu_sharded* quality, fsgpu_alignment** out) {

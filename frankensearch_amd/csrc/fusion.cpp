@@ -5,14 +5,20 @@
 // Exposed through the C ABI (fsgpu_rrf_fuse / fsgpu_blend_two_tier) so the end-to-end two-tier query path can be
 // driven without the Rust crate.  No GPU needed.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
+#include <new>
 #include <string_view>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/fsgpu.h"
+#include "hubness.hpp"
 #include "mmr.hpp"
 
 namespace {
@@ -505,5 +511,165 @@ extern "C" fsgpu_status fsgpu_mmr_rerank(const double* scores, const float* cons
     } catch (...) {
         return FSGPU_ERR_DEVICE;   // host allocation failed
     }
+    return FSGPU_OK;
+}
+
+// ---- query hubness: compute_query_hubness / apply_hubness_penalty (crates/frankensearch-fusion/src/hubness.rs) ----
+// (this file is built with -ffp-contract=off: every `acc + a * b` below is a multiply and an add, as in simd.rs:134-222)
+namespace fsgpu {
+
+float hubness_dot(const float* a, const float* b, size_t n, int hreduce) {
+    const size_t groups = n / 32, chunks = n / 8;
+    float acc[4][8] = {};
+    for (size_t g = 0; g < groups; ++g)   // simd.rs:160-190: accumulator x takes elements [32 g + 8 x, 32 g + 8 x + 8)
+        for (int x = 0; x < 4; ++x)
+            for (int j = 0; j < 8; ++j) {
+                const size_t o = g * 32 + (size_t)x * 8 + (size_t)j;
+                const float p = a[o] * b[o];
+                acc[x][j] = acc[x][j] + p;
+            }
+    float v[8];
+    for (int j = 0; j < 8; ++j) v[j] = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
+    for (size_t c = groups * 4; c < chunks; ++c)   // leftover chunks join AFTER the tree (the f16 byte dot adds them to s0 before it)
+        for (int j = 0; j < 8; ++j) {
+            const float p = a[c * 8 + (size_t)j] * b[c * 8 + (size_t)j];
+            v[j] = v[j] + p;
+        }
+    float result;
+    if (hreduce == FSGPU_HREDUCE_SEQ) {
+        const float lo = ((v[0] + v[1]) + v[2]) + v[3];
+        const float hi = ((v[4] + v[5]) + v[6]) + v[7];
+        result = lo + hi;
+    } else if (hreduce == FSGPU_HREDUCE_AVX) {
+        const float s0 = v[0] + v[4], s1 = v[1] + v[5], s2 = v[2] + v[6], s3 = v[3] + v[7];
+        const float lo = s0 + s2, hi = s1 + s3;
+        result = lo + hi;
+    } else {
+        const float lo = (v[0] + v[2]) + (v[1] + v[3]);
+        const float hi = (v[4] + v[6]) + (v[5] + v[7]);
+        result = lo + hi;
+    }
+    for (size_t i = chunks * 8; i < n; ++i) {   // the tail is a multiply and an add too (the byte dots fuse theirs)
+        const float p = a[i] * b[i];
+        result = result + p;
+    }
+    return result;
+}
+
+float hubness_mean(const uint32_t* keys_desc, uint32_t k) {
+    if (k == 1) return hubness_value(keys_desc[0]) / 1.0f;
+    float s = hubness_value(keys_desc[0]);
+    for (uint32_t i = 1; i + 1 < k; ++i) s = s + hubness_value(keys_desc[i]);
+    return (hubness_value(keys_desc[k - 1]) + s) / (float)k;   // `*pivot + top.iter().sum()`, `/ k as f32` (hubness.rs:136-137)
+}
+
+namespace {
+uint32_t hubness_threads(uint32_t asked) {
+    if (asked) return std::min(asked, 64u);
+    uint32_t n = 16;
+    if (const char* env = std::getenv("OMP_NUM_THREADS")) {
+        const long v = std::strtol(env, nullptr, 10);
+        if (v >= 1) n = (uint32_t)std::min(v, 16l);
+    }
+    return n;
+}
+}  // namespace
+
+void query_hubness_host(const float* const* docs, const uint32_t* doc_lens, uint64_t n_docs, const float* const* queries,
+                        const uint32_t* query_lens, uint32_t n_queries, uint32_t kq, int hreduce, float* out, float* out_topk,
+                        uint32_t threads) {
+    if (n_queries == 0 || kq == 0) {   // hubness.rs:110-112
+        for (uint64_t d = 0; d < n_docs; ++d) out[d] = 0.0f;
+        return;
+    }
+    const uint32_t k = std::min(kq, n_queries);
+    std::atomic<bool> failed{false};
+    auto range = [&](uint64_t lo, uint64_t hi) {
+        try {   // (a worker's allocation failure must reach the caller as a status, not std::terminate)
+            std::vector<uint32_t> keys(n_queries);
+            for (uint64_t d = lo; d < hi; ++d) {
+                for (uint32_t j = 0; j < n_queries; ++j)
+                    keys[j] = hubness_key(hubness_dot(docs[d], queries[j], std::min(doc_lens[d], query_lens[j]), hreduce));
+                std::partial_sort(keys.begin(), keys.begin() + k, keys.end(), std::greater<uint32_t>());
+                out[d] = hubness_mean(keys.data(), k);
+                if (out_topk)
+                    for (uint32_t i = 0; i < k; ++i) out_topk[d * k + i] = hubness_value(keys[i]);
+            }
+        } catch (...) {
+            failed.store(true);
+        }
+    };
+    // rows are independent (hubness.rs:96-102): contiguous row ranges, one per thread
+    const uint64_t work = n_docs * (uint64_t)n_queries;
+    const uint32_t nt = work < 10000 ? 1u : (uint32_t)std::min<uint64_t>(hubness_threads(threads), n_docs);
+    std::vector<std::thread> pool;
+    uint32_t started = 0;
+    if (nt > 1) {
+        try {
+            pool.reserve(nt);
+            for (; started < nt; ++started) pool.emplace_back(range, n_docs * started / nt, n_docs * (started + 1) / nt);
+        } catch (...) {   // no more threads to be had: the calling thread takes the ranges that are left
+        }
+    }
+    if (started < nt) range(n_docs * started / nt, n_docs);
+    for (std::thread& th : pool) th.join();
+    if (failed.load()) throw std::bad_alloc();
+}
+
+}  // namespace fsgpu
+
+extern "C" fsgpu_status fsgpu_hubness_config_default(fsgpu_hubness_config* config) {
+    if (!config) return FSGPU_ERR_NULL_ARGUMENT;
+    std::memset(config, 0, sizeof(*config));
+    config->beta = 0.2f;   // HubnessConfig::default (hubness.rs:46-50)
+    config->kq = 10;
+    return FSGPU_OK;
+}
+
+extern "C" fsgpu_status fsgpu_query_hubness(const float* const* docs, const uint32_t* doc_lens, uint64_t n_docs, const float* const* queries,
+                                            const uint32_t* query_lens, uint32_t n_queries, uint32_t kq, int32_t hreduce, float* out) {
+    if (n_docs && (!out || !docs || !doc_lens)) return FSGPU_ERR_NULL_ARGUMENT;
+    if (n_queries && (!queries || !query_lens)) return FSGPU_ERR_NULL_ARGUMENT;
+    if (hreduce < FSGPU_HREDUCE_SSE2 || hreduce > FSGPU_HREDUCE_SEQ) return FSGPU_ERR_INVALID_CONFIG;
+    for (uint64_t d = 0; d < n_docs; ++d)
+        if (doc_lens[d] && !docs[d]) return FSGPU_ERR_NULL_ARGUMENT;
+    for (uint32_t j = 0; j < n_queries; ++j)
+        if (query_lens[j] && !queries[j]) return FSGPU_ERR_NULL_ARGUMENT;
+    try {
+        fsgpu::query_hubness_host(docs, doc_lens, n_docs, queries, query_lens, n_queries, kq, hreduce, out, nullptr);
+    } catch (...) {
+        return FSGPU_ERR_DEVICE;   // host allocation failed (the ABI's status for a resource failure; fsgpu_mmr_rerank does the same)
+    }
+    return FSGPU_OK;
+}
+
+// apply_hubness_penalty (hubness.rs:67-86) in place, then — resort != 0 — correct_phase1_pool's sort by VectorHit::cmp_rank
+// (searcher.rs:769-777, types.rs:101-133): score descending with NaN as -inf under total_cmp, doc_id bytes ascending; stable.
+extern "C" fsgpu_status fsgpu_apply_hubness_penalty(fsgpu_scored_doc* hits, uint32_t n, const float* table, uint64_t table_len,
+                                                    const fsgpu_hubness_config* config, int32_t resort, uint8_t* out_applied) {
+    if (out_applied) *out_applied = 0;
+    if (n && !hits) return FSGPU_ERR_NULL_ARGUMENT;
+    if (table_len && !table) return FSGPU_ERR_NULL_ARGUMENT;
+    fsgpu_hubness_config cfg;
+    fsgpu_hubness_config_default(&cfg);
+    if (config) {
+        for (uint32_t r : config->reserved)
+            if (r != 0) return FSGPU_ERR_INVALID_CONFIG;
+        cfg = *config;
+    }
+    if (!std::isfinite(cfg.beta) || cfg.beta <= 0.0f) return FSGPU_OK;   // HubnessConfig::is_identity
+    for (uint32_t i = 0; i < n; ++i) {
+        const float r = hits[i].index < table_len ? table[hits[i].index] : 0.0f;
+        const float p = cfg.beta * r;
+        hits[i].score = hits[i].score - p;
+    }
+    if (resort)
+        std::stable_sort(hits, hits + n, [](const fsgpu_scored_doc& a, const fsgpu_scored_doc& b) {
+            const float inf = std::numeric_limits<float>::infinity();
+            const int32_t x = total_key32(std::isnan(a.score) ? -inf : a.score), y = total_key32(std::isnan(b.score) ? -inf : b.score);
+            if (x != y) return x > y;
+            return sv(a) < sv(b);
+        });
+    if (out_applied) *out_applied = 1;
     return FSGPU_OK;
 }

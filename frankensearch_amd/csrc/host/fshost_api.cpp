@@ -124,6 +124,16 @@ fsgpu_status fshost_two_tier_set_batching(fshost_two_tier* s, uint32_t max_chunk
     }
 }
 
+fsgpu_status fshost_two_tier_set_hubness(fshost_two_tier* s, const float* table, uint64_t table_len, float beta) {
+    if (!s) return FSGPU_ERR_NULL_ARGUMENT;
+    try {
+        s->impl.set_hubness(table, table_len, beta);
+    } catch (const std::exception&) {
+        return FSGPU_ERR_DEVICE;   // host allocation failed
+    }
+    return FSGPU_OK;
+}
+
 fsgpu_status fshost_two_tier_batching_stats(fshost_two_tier* s, uint64_t* chunks, uint64_t* requests) {
     if (!s || !chunks || !requests) return FSGPU_ERR_NULL_ARGUMENT;
     s->impl.batching_stats(chunks, requests);

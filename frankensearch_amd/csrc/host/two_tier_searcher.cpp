@@ -1,6 +1,8 @@
 // two_tier_searcher.cpp — see two_tier_searcher.hpp.  Calls only functions declared in include/fsgpu.h.
 #include "two_tier_searcher.hpp"
 
+#include <cmath>
+
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -158,6 +160,39 @@ fsgpu_status SyncTwoTierSearcher::hits_from_rows(const Tier& tier, const uint32_
     return FSGPU_OK;
 }
 
+void SyncTwoTierSearcher::set_hubness(const float* table, uint64_t table_len, float beta) {
+    HubnessSnapshot next;
+    if (table && table_len > 0 && std::isfinite(beta) && beta > 0.0f) {   // HubnessConfig::is_identity (hubness.rs:55-57)
+        auto t = std::make_shared<HubnessTable>();
+        t->r_d.assign(table, table + table_len);
+        t->beta = beta;
+        next = std::move(t);
+    }
+    std::atomic_store(&hubness_, next);
+}
+
+fsgpu_status SyncTwoTierSearcher::correct_phase1_pool(const HubnessTable* t, std::vector<Hit>* fast_hits, std::string* detail) const {
+    if (!t || fast_hits->empty()) return FSGPU_OK;
+    std::vector<fsgpu_scored_doc> pool;
+    pool.reserve(fast_hits->size());
+    for (const Hit& h : *fast_hits) pool.push_back(fsgpu_scored_doc{h.doc_id.data(), (uint32_t)h.doc_id.size(), h.score, h.index});
+    fsgpu_hubness_config cfg;
+    fsgpu_hubness_config_default(&cfg);
+    cfg.beta = t->beta;
+    uint8_t applied = 0;
+    const fsgpu_status st = fsgpu_apply_hubness_penalty(pool.data(), (uint32_t)pool.size(), t->r_d.data(), t->r_d.size(), &cfg, 1, &applied);
+    if (st != FSGPU_OK) {
+        *detail = "fsgpu_apply_hubness_penalty failed";
+        return st;
+    }
+    if (!applied) return FSGPU_OK;
+    std::vector<Hit> corrected;
+    corrected.reserve(pool.size());
+    for (const fsgpu_scored_doc& d : pool) corrected.push_back(Hit{std::string(d.doc_id, d.doc_id_len), d.score, d.index});
+    fast_hits->swap(corrected);
+    return FSGPU_OK;
+}
+
 fsgpu_status SyncTwoTierSearcher::search(const uint32_t* fast_ids, uint32_t n_fast, const int32_t* quality_ids,
                                          uint32_t n_quality, uint32_t k, const fsgpu_scored_doc* lexical, uint32_t n_lexical,
                                          Outcome* out, std::string* detail) const {
@@ -186,6 +221,7 @@ fsgpu_status SyncTwoTierSearcher::search_unbatched(const uint32_t* fast_ids, uin
     fshost_metrics& m = out->metrics;
     out->refinement_failed = false;
     out->skip_reason.clear();
+    const HubnessSnapshot hubness = hubness_snapshot();   // the table this search started with (fast_hits is corrected once, below)
     const auto t0 = clock::now();
     // quality embedding: needed by phase 1 only, optionally computed while phase 0 runs
     // (a vector has its EMBEDDER's dimension; an index of another dimension answers DimensionMismatch — search.rs:1602-1610 — which
@@ -227,6 +263,8 @@ fsgpu_status SyncTwoTierSearcher::search_unbatched(const uint32_t* fast_ids, uin
     const auto t1 = clock::now();
     std::vector<Hit> fast_hits;
     st = tier_hits(fast_, fast_vec, fetch, cfg_.fast_tier_int8_multiplier, &fast_hits, detail);
+    if (st != FSGPU_OK) return st;
+    st = correct_phase1_pool(hubness.get(), &fast_hits, detail);   // shadows fast_hits for everything downstream (searcher.rs:1869-1873)
     if (st != FSGPU_OK) return st;
     m.fast_search_ms = ms_since(t1);
     st = fuse_initial(fast_hits, k, lexical, n_lexical, &out->initial, detail);

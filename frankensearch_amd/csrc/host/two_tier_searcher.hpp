@@ -23,6 +23,13 @@ struct Hit {  // VectorHit / ScoredResult with an owned doc id (crates/frankense
     uint32_t index;
 };
 
+// The fast tier's r_d table and TwoTierConfig::hubness_beta as one immutable snapshot (fshost_two_tier_set_hubness swaps it whole).
+struct HubnessTable {
+    std::vector<float> r_d;
+    float beta = 0.0f;
+};
+using HubnessSnapshot = std::shared_ptr<const HubnessTable>;
+
 struct Outcome {
     std::vector<fshost_hit> initial, final_results;
     fshost_metrics metrics{};
@@ -90,6 +97,11 @@ class SyncTwoTierSearcher {
     fsgpu_status search_many(const ManyArgs& a, fshost_many_result* result) const;
     // Dynamic batching of concurrent search() callers through the same engine (fshost_two_tier_set_batching): max_chunk = 0 turns it off.
     fsgpu_status set_batching(uint32_t max_chunk, uint32_t max_wait_us);
+    // with_hubness_table + TwoTierConfig::hubness_beta (searcher.rs:696-734): the table is copied; an empty table, or a beta that is
+    // non-finite or <= 0, detaches it.  Safe beside running searches: a search takes ONE snapshot when it starts (search_unbatched
+    // on entry, search_many per call, a batched callers' chunk at admission) and every stage of it works on that snapshot.
+    void set_hubness(const float* table, uint64_t table_len, float beta);
+    HubnessSnapshot hubness_snapshot() const { return std::atomic_load(&hubness_); }
     void batching_stats(uint64_t* chunks, uint64_t* requests) const;
 
   private:
@@ -99,6 +111,10 @@ class SyncTwoTierSearcher {
     void init();
     fsgpu_status tier_hits(const Tier& tier, const std::vector<float>& vec, uint32_t fetch, uint32_t int8_multiplier,
                            std::vector<Hit>* hits, std::string* detail) const;
+    // correct_phase1_pool (searcher.rs:737-777) on the fast tier's pool: apply_hubness_penalty by Hit::index, one sort by cmp_rank.
+    // Every consumer of the fast pool (both RRFs, the blend, quality_scores_for_hits, the rank maps) sees the corrected pool.
+    // `table`: the search's snapshot (null: no correction) — never re-read from the searcher in mid-search.
+    fsgpu_status correct_phase1_pool(const HubnessTable* table, std::vector<Hit>* fast_hits, std::string* detail) const;
     fsgpu_status hits_from_rows(const Tier& tier, const uint32_t* rows, const float* scores, uint32_t count, std::vector<Hit>* hits,
                                 std::string* detail) const;
     fsgpu_status fuse_initial(const std::vector<Hit>& fast_hits, uint32_t k, const fsgpu_scored_doc* lexical, uint32_t n_lexical,
@@ -122,6 +138,7 @@ class SyncTwoTierSearcher {
     mutable std::mutex engine_mu_;
     mutable std::unique_ptr<ManyEngine> engine_;
     std::atomic<bool> batching_{false};
+    HubnessSnapshot hubness_;   // null: no correction (read and swapped with std::atomic_load / _store)
 };
 
 // The many-queries engine (two_tier_many.cpp): four stage threads + a fusion pool over the searcher's handles.

@@ -467,4 +467,25 @@ struct MmrPlan {
 MmrPlan mmr_plan(uint32_t max_n, uint32_t dim, bool f32_staging, bool want_sims);
 hipError_t launch_mmr(const MmrArgs& args, uint32_t npools, const MmrPlan& plan, hipStream_t stream);
 
+// hubness_kernels.hip: the query-hubness table (hubness.rs:109-138) — per slab row the mean of its k greatest
+// dot_product_f32_f32 similarities to a query sample, selected under f32::total_cmp and summed in the canonical order
+// (include/fsgpu.h).  A workgroup owns 16 rows per wave in LDS and streams the sample past them in chunks of kHubQueryChunk.
+constexpr uint32_t kHubMaxK = 64, kHubMaxDim = 1024, kHubRowsPerWave = 16, kHubQueryChunk = 16;
+constexpr uint32_t kHubLaunchRows = 1u << 20;      // rows per launch: no single launch holds a shared card for long
+constexpr size_t kHubLdsBudget = 160 * 1024;
+struct HubnessArgs {
+    const void* slab;         // the index's rows (f16 or f32)
+    uint32_t row_stride;      // bytes between rows
+    uint32_t dim;
+    uint32_t slab_f32;
+    uint32_t row0, nrows;     // this launch: slab rows [row0, row0 + nrows)
+    const float* queries;     // [nq, dim]
+    uint32_t nq;
+    uint32_t k;               // min(kq, nq), 1 .. kHubMaxK
+    int32_t hreduce;
+    float* out;               // [slab rows]
+    float* out_topk;          // nullable: [slab rows, k], greatest first
+};
+hipError_t launch_hubness(const HubnessArgs& args, hipStream_t stream);
+
 }  // namespace fsgpu

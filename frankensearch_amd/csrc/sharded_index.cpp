@@ -6,6 +6,8 @@
 // never needs RCCL on its library path, and inside a PyTorch process the already loaded copy (same SONAME) is reused.
 #include "sharded_index.hpp"
 
+#include <thread>
+
 #include <chrono>
 #include <cstdio>
 
@@ -892,6 +894,38 @@ SearchError ShardedIndex::gather_dot(const float* query, uint32_t query_len, con
         SH_TRY(shards_[r]->index.gather_dot(query, query_len, by_shard[r].data(), (uint32_t)by_shard[r].size(), tmp.data()));
         for (size_t x = 0; x < tmp.size(); ++x) out[slot[r][x]] = tmp[x];
     }
+    return SearchError{};
+}
+
+// compute_query_hubness (crates/frankensearch-fusion/src/hubness.rs:109-138) over a row-sharded index: every row shard (the first
+// group's copy) computes its own row range side by side, one host thread each; the results are concatenated in global row order.
+// No collective: a row's value depends on that row and the sample alone.
+SearchError ShardedIndex::compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out) {
+    if (nq > 0 && query_dim != dim_)
+        return make_err(FSGPU_ERR_DIMENSION_MISMATCH, "expected " + std::to_string(dim_) + ", found " + std::to_string(query_dim));
+    const uint32_t n = std::min<uint32_t>(row_shards_, (uint32_t)shards_.size());
+    std::vector<SearchError> errs(n);
+    auto shard = [&](uint32_t r) {
+        try {
+            Shard& s = *shards_[r];
+            if (!s.rows) return;
+            std::lock_guard<std::mutex> lock(s.index.mutex());
+            errs[r] = s.index.compute_query_hubness(queries, nq, query_dim, kq, out + s.lo, nullptr);
+        } catch (...) {
+            errs[r] = make_err(FSGPU_ERR_DEVICE, "host allocation failed in compute_query_hubness");
+        }
+    };
+    std::vector<std::thread> pool;
+    uint32_t started = 0;
+    try {
+        pool.reserve(n);
+        for (; started + 1 < n; ++started) pool.emplace_back(shard, started);   // the last shard runs on the calling thread
+    } catch (...) {   // no more threads to be had: the calling thread takes the shards that are left
+    }
+    for (uint32_t r = started; r < n; ++r) shard(r);
+    for (std::thread& t : pool) t.join();
+    for (const SearchError& e : errs)
+        if (!e.ok()) return e;
     return SearchError{};
 }
 

@@ -94,6 +94,8 @@ class ShardedIndex {
     uint64_t wal_record_count() const { return catalog_ ? catalog_->wal_record_count() : 0; }
     // dot_query_at over global row ids, routed to the owning shards
     SearchError gather_dot(const float* query, uint32_t query_len, const uint32_t* rows, uint32_t n, float* out);
+    // the query-hubness table of every row (VectorIndex::compute_query_hubness per row shard, concatenated in global row order)
+    SearchError compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out);
 
     uint64_t record_count() const { return nrows_; }
     uint32_t dimension() const { return dim_; }

@@ -196,6 +196,13 @@ class VectorIndex {
     SearchError mmr_rerank_docs(const char* const* doc_ids, const uint32_t* doc_id_lens, const float* scores, uint32_t n, bool enabled,
                                 double lambda, uint32_t candidate_pool, uint32_t* out_order, uint8_t* out_applied);
 
+    // compute_query_hubness (crates/frankensearch-fusion/src/hubness.rs:109-138) over every row of this slab, tombstoned rows too:
+    // out[record_count()] = the mean of the row's min(kq, nq) greatest dot_product_f32_f32 similarities to the sample, in the
+    // canonical order (include/fsgpu.h).  hubness_kernels.hip for k <= 64 and dim <= 1,024, launched over ranges of kHubLaunchRows
+    // rows; else the host restatement over rows fetched in blocks (same bits).  out_topk (nullable): [record_count(), k] selected
+    // sims, greatest first.  Host pointers; blocks; own workspaces on the index's stream.
+    SearchError compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out, float* out_topk);
+
     std::mutex& mutex() { return mu_; }
     int device() const { return device_; }
     int32_t hreduce = 0;
@@ -355,6 +362,7 @@ class VectorIndex {
         mf_fallback_, mf_fallback2_, mf_spill_, mf_io_, mf_io2_, i8_stats_, n4u_slab_, mf_cand_count_, ws_pairs_;
     DeviceBuffer ws_out_;   // rows | scores | counts of a blocking batched search (one block: one copy up)
     DeviceBuffer ws_mmr_in_, ws_mmr_out_, ws_mmr_sims_, ws_mmr_vec_;   // mmr_rerank_rows: inputs (one copy down), order | counts, matrix, staged rows
+    DeviceBuffer ws_hub_q_, ws_hub_out_, ws_hub_topk_;   // compute_query_hubness: the sample, the table, the selected sims (lab)
     bool i8_ready_ = false, n4_ready_ = false, i8_stats_ready_ = false, n4u_ready_ = false;
     bool quant_max_ready_ = false;   // i8_max_ holds a corpus-wide max-abs handed in by a sharded index: the quantisers keep it
     u64* tp_approx_out_ = nullptr;   // two_pass_candidates_device: where the batch in flight leaves its candidate pairs

@@ -71,7 +71,7 @@ class _ManyResult(C.Structure):
 
 
 SYMBOLS = ("fshost_two_tier_create", "fshost_two_tier_create_sharded", "fshost_two_tier_destroy", "fshost_two_tier_search",
-           "fshost_two_tier_search_many", "fshost_run_load_many", "fshost_two_tier_set_batching", "fshost_two_tier_batching_stats", "fshost_run_load", "fshost_embed_search_stream", "fshost_embed_search_stream_dp")
+           "fshost_two_tier_search_many", "fshost_run_load_many", "fshost_two_tier_set_batching", "fshost_two_tier_set_hubness", "fshost_two_tier_batching_stats", "fshost_run_load", "fshost_embed_search_stream", "fshost_embed_search_stream_dp")
 _handle = None
 
 
@@ -104,6 +104,8 @@ def lib() -> C.CDLL:
         h.fshost_run_load.argtypes = [C.c_void_p, C.POINTER(_LoadConfig), C.POINTER(_LoadResult)]
         h.fshost_two_tier_set_batching.restype = C.c_int32
         h.fshost_two_tier_set_batching.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        h.fshost_two_tier_set_hubness.restype = C.c_int32
+        h.fshost_two_tier_set_hubness.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float]
         h.fshost_two_tier_batching_stats.restype = C.c_int32
         h.fshost_two_tier_batching_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         h.fshost_run_load_many.restype = C.c_int32
@@ -241,6 +243,15 @@ class NativeTwoTierSearcher:
     def set_batching(self, max_chunk: int, max_wait_us: int = 200) -> None:
         """fshost_two_tier_set_batching: concurrent search() callers ride the many-queries pipeline (0 = off)."""
         check(lib().fshost_two_tier_set_batching(self._h, max_chunk, max_wait_us))
+
+    def set_hubness(self, table, beta: float) -> None:
+        """fshost_two_tier_set_hubness: attach the fast tier's r_d table (copied) and the penalty weight; table None / empty or
+        beta <= 0 detaches it.  The fast pool is then corrected and re-sorted before the first RRF (searcher.rs:1869-1873)."""
+        if table is None:
+            check(lib().fshost_two_tier_set_hubness(self._h, None, 0, float(beta)))
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+        check(lib().fshost_two_tier_set_hubness(self._h, t.ctypes.data_as(C.c_void_p), t.size, float(beta)))
 
     def batching_stats(self):
         a, b = C.c_uint64(), C.c_uint64()

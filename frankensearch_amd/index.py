@@ -347,6 +347,23 @@ class VectorIndex:
         check(_lib.lib().fsgpu_index_vector_at_f32(self._h, int(row), _ptr(out)))
         return out
 
+    def compute_query_hubness(self, queries, kq: int = 10, want_topk: bool = False):
+        """fsgpu_index_compute_query_hubness: the r_d table of every row (hubness.rs:109-138) against the query sample [nq, dim], on
+        the device.  want_topk (lab): also the selected similarities per row, greatest first, [rows, min(kq, nq)]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq, qdim = (q.shape[0], q.shape[1]) if q.size else (0, self.dimension())
+        n = self.record_count()
+        out = np.zeros(n, dtype=np.float32)
+        if not want_topk:
+            check(_lib.lib().fsgpu_index_compute_query_hubness(self._h, _ptr(q) if nq else None, nq, qdim, kq, _ptr(out) if n else None))
+            return out
+        topk = np.zeros((n, max(min(kq, nq), 1)), dtype=np.float32)
+        check(_lib.lib().fsgpu_lab_index_query_hubness_topk(self._h, _ptr(q) if nq else None, nq, qdim, kq, _ptr(out) if n else None,
+                                                            _ptr(topk)))
+        return out, topk
+
     def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
         """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes
         into `rows` (and the pool x pool f64 similarity matrix with want_sims)."""
@@ -673,6 +690,17 @@ class NativeShardedIndex:
         r = np.ascontiguousarray(rows, dtype=np.uint32)
         out = np.zeros(r.size, dtype=np.float32)
         check(_lib.lib().fsgpu_sharded_gather_dot(self._h, _ptr(q), q.size, _ptr(r), r.size, _ptr(out)))
+        return out
+
+    def compute_query_hubness(self, queries, kq: int = 10) -> np.ndarray:
+        """fsgpu_sharded_compute_query_hubness: every row shard computes its rows; one table in global row order."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq, qdim = (q.shape[0], q.shape[1]) if q.size else (0, self.dimension())
+        n = self.record_count()
+        out = np.zeros(n, dtype=np.float32)
+        check(_lib.lib().fsgpu_sharded_compute_query_hubness(self._h, _ptr(q) if nq else None, nq, qdim, kq, _ptr(out) if n else None))
         return out
 
     def set_coalescing(self, max_batch: int, max_wait_us: int) -> None:

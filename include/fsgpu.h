@@ -760,6 +760,56 @@ fsgpu_status fsgpu_two_tier_mmr_rerank(fsgpu_index *fast, fsgpu_index *quality, 
                                        const fsgpu_scored_doc *hits, uint32_t n, const fsgpu_mmr_config *config, uint32_t *out_order,
                                        uint8_t *out_applied);
 
+/* ---- query hubness: the r_d table and the phase-1 penalty ---- */
+/* The reference's query-hubness correction (crates/frankensearch-fusion/src/hubness.rs; applied by TwoTierSearcher's
+ * correct_phase1_pool, searcher.rs:737-777, 1869-1873).  r_d is the mean of document d's k = min(kq, n_queries) greatest
+ * similarities to a background query sample; the penalty is s' = s - beta * r_d over the fast-tier pool, then one re-sort.
+ *   sim(d, j) = dot_product_f32_f32 (crates/frankensearch-index/src/simd.rs:134-222) in the horizontal order `hreduce`: four 8-lane
+ *     accumulators over groups of 32 with a separate multiply and add, (acc0 + acc1) + (acc2 + acc3), the leftover 8-element chunks
+ *     added to that sum AFTER the tree, reduce_add, then the last n % 8 elements as an unfused multiply and add.  (The scan's f16
+ *     byte dot puts the leftovers into acc0 before the tree and fuses its tail; the F32-slab byte dot fuses its tail.)
+ *   selection: the k greatest under f32::total_cmp (hubness.rs:135): -0.0 < +0.0, +NaN above +inf, -NaN below -inf.
+ *   mean: the reference sums `top` in whatever order select_nth_unstable_by left it, which pins the multiset but not the bits.
+ *     This library fixes ONE of those orders, on every path: v_1 >= ... >= v_k; s = v_1; s += v_2; ...; s += v_{k-1};
+ *     r_d = (v_k + s) / (float)k; for k == 1, v_1 / 1.0f.
+ *   an empty sample or kq == 0 gives zeros; every row gets an entry, tombstoned rows too (the table is indexed by VectorHit::index).
+ * HubnessConfig (hubness.rs:36-58): defaults beta = 0.2, kq = 10; the reserved words must be 0. */
+typedef struct fsgpu_hubness_config {
+    float beta;
+    uint32_t kq;
+    uint32_t reserved[4]; /* must be 0 */
+} fsgpu_hubness_config;
+fsgpu_status fsgpu_hubness_config_default(fsgpu_hubness_config *config);
+/* compute_query_hubness on caller-supplied f32 vectors, on the host (no device is needed): docs[d] holds doc_lens[d] values,
+ * queries[j] query_lens[j]; each dot runs over the common prefix of its two vectors, as the reference's does (hubness.rs:157-161).
+ * out[n_docs].  Threaded over rows (OMP_NUM_THREADS threads, at most 16); a row's value does not depend on the thread count or on
+ * the other rows.  This is also what the index-level calls below run for k > 64, with the same bits. */
+fsgpu_status fsgpu_query_hubness(const float *const *docs, const uint32_t *doc_lens, uint64_t n_docs, const float *const *queries,
+                                 const uint32_t *query_lens, uint32_t n_queries, uint32_t kq, int32_t hreduce, float *out);
+/* apply_hubness_penalty (hubness.rs:67-86) in place: the identity (*out_applied = 0) when beta is non-finite or <= 0; otherwise
+ * score - beta * r as a separate f32 multiply and subtract with r = table[index], or 0 when index >= table_len.  resort != 0 then
+ * sorts as correct_phase1_pool does, by VectorHit::cmp_rank (types.rs:101-133): score descending with NaN as -inf, doc_id bytes
+ * ascending.  A NULL config means the defaults. */
+fsgpu_status fsgpu_apply_hubness_penalty(fsgpu_scored_doc *hits, uint32_t n, const float *table, uint64_t table_len,
+                                         const fsgpu_hubness_config *config, int32_t resort, uint8_t *out_applied);
+/* compute_query_hubness over every row of an index, on its device (hubness_kernels.hip): a workgroup keeps a tile of rows in LDS
+ * widened to f32 (exact for an f16 slab), streams the query sample past it and keeps a running top-k per row; the slab is read
+ * once.  queries[nq, query_dim] are host values, out[record_count] is written in row order, the call blocks.  It runs on the
+ * index's own stream with workspaces of its own.  query_dim must equal the index's dimension (FSGPU_ERR_DIMENSION_MISMATCH): this
+ * is STRICTER than the reference, whose dot truncates to the common length — use fsgpu_query_hubness for ragged inputs.
+ * k = min(kq, nq) <= 64 at up to 1,024 dimensions runs on the device; anything else runs fsgpu_query_hubness over rows fetched
+ * from the slab in blocks, with the same bits — on the HOST, tens of seconds at corpus size, and like every call on an index it
+ * holds the index for its whole duration: searches on the same handle wait behind it.  Build such a table on a handle that is not
+ * serving, or keep kq <= 64.  (A similarity that is a NaN GENERATED by the arithmetic — inf - inf, 0 x inf —
+ * has an architecture-defined sign; such rows are outside the bit contract between the two.)  Without a device:
+ * FSGPU_ERR_NO_DEVICE. */
+fsgpu_status fsgpu_index_compute_query_hubness(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                               float *out);
+/* The same over a row-sharded handle: every row shard computes its own rows, the results are concatenated in global row order.  No
+ * collective: a row's value does not depend on the layout. */
+fsgpu_status fsgpu_sharded_compute_query_hubness(fsgpu_sharded *sh, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                                 float *out);
+
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */
 typedef struct fsgpu_mrl_stats {

@@ -45,6 +45,10 @@ fsgpu_status fsgpu_lab_sort_keys_desc(int32_t device, const uint64_t *keys, uint
  * K and N must be multiples of 64 (else FSGPU_ERR_INVALID_CONFIG). */
 fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float *x, const float *w, const float *bias, uint32_t m, uint32_t n,
                                            uint32_t k, float *y);
+/* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
+ * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
+fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
+                                                float *out, float *out_topk);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 

@@ -138,6 +138,19 @@ fsgpu_status fshost_two_tier_search_many(fshost_two_tier *s, const uint32_t *fas
 fsgpu_status fshost_two_tier_set_batching(fshost_two_tier *s, uint32_t max_chunk, uint32_t max_wait_us);
 fsgpu_status fshost_two_tier_batching_stats(fshost_two_tier *s, uint64_t *chunks, uint64_t *requests);
 
+/* The query-hubness correction of phase 1: TwoTierSearcher::with_hubness_table + TwoTierConfig::hubness_beta in one call
+ * (crates/frankensearch-fusion/src/searcher.rs:696-777, 1869-1873; core/src/config.rs:117-130).  table[table_len] is the r_d table of
+ * the FAST tier, indexed by the hit's row (fsgpu_index_compute_query_hubness / fsgpu_sharded_compute_query_hubness build it); it is
+ * copied.  A NULL table, table_len 0, or a beta that is non-finite or <= 0 detaches it, and every search returns what it returned
+ * before the call was ever made.  kq belongs to the table build, not to query time.  When active, the fast tier's pool is corrected
+ * (fsgpu_apply_hubness_penalty: score - beta * r_d, then one sort by VectorHit::cmp_rank) right after the tier search and BEFORE the
+ * first RRF, and the corrected pool replaces the fast pool everywhere downstream: both RRFs, the blend, quality_scores_for_hits, the
+ * rank maps — in fshost_two_tier_search, in fshost_two_tier_search_many (on the fusion threads) and over sharded tiers alike.
+ * This stage comes from the reference's async TwoTierSearcher (as the MMR stage of libfsgpu does); SyncTwoTierSearcher, which the
+ * rest of this header restates, has no such stage.  May be called between searches or beside them: a search in flight keeps the
+ * table it started with. */
+fsgpu_status fshost_two_tier_set_hubness(fshost_two_tier *s, const float *table, uint64_t table_len, float beta);
+
 /* Closed-loop load generator: `threads` native threads each issue fshost_two_tier_search calls back to back on
  * synthetic queries (SURVEY §8d config 5 shapes: fast ids uniform in [0, fast_vocab), 4-23 tokens; quality ids
  * [CLS] + uniform [1000, quality_vocab) + [SEP], 8-32 tokens; stub lexical list of 3k "doc-%08u" ids), the way a
