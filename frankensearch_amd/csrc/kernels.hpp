@@ -117,6 +117,8 @@ struct MfmaScanArgs {
                                          // group g's queries/tau/cand/spill/overflow/dense follow group g-1's
     uint32_t* cand_count;                // mfma_wide.hip: [nq_pad, gridDim.x] entries in each (query, block) list, clamped to
                                          // slots (may be null: the lists are then padded with kEmpty instead)
+    uint32_t side_by_side;               // mfma_wide.hip main pass, groups > 1: the groups run concurrently on gridDim.x walkers each and
+                                         // walk the slab in the same direction (0: one after the other, alternating directions)
 };
 
 // select_kernel (mfma_scan.hip): per query, the k-th best of the packed approximate entries without sorting them

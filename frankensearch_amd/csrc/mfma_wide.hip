@@ -310,7 +310,11 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     if (gridDim.y > 1) {
         // several query groups in ONE launch (args.groups = gridDim.y): group g's queries / thresholds / lists / spill area follow group
         // g - 1's, its blocks take over the CUs as the previous group's blocks leave them (one block per CU is resident) — no launch
-        // ramp and no chip-wide tail between two passes over the slab; consecutive groups walk the slab in opposite directions
+        // ramp and no chip-wide tail between two passes over the slab; consecutive groups walk the slab in opposite directions.
+        // args.side_by_side: the launch is dim3(W, groups) with W x groups <= the resident blocks, so every group runs at once on W
+        // walkers; walker w of every group visits the same tiles at the same time and in the SAME direction, and the later fetch of
+        // a tile is served by the L2 the earlier one filled when both blocks sit on one XCD (linear ids W apart, W % 8 == 0).
+        // Nothing but speed depends on that placement or on the groups being co-resident.
         const uint32_t grp = blockIdx.y;
         args.queries = static_cast<const unsigned char*>(args.queries) + (size_t)grp * NQ * ROWB;
         args.tau += (size_t)grp * NQ;
@@ -319,7 +323,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
         args.spill += (size_t)grp * NQ * args.spill_cap;
         args.spill_count += (size_t)grp * NQ * kMfmaSpillCountStride;
         args.overflow += (size_t)grp * NQ;
-        args.reverse ^= grp & 1u;
+        if (!args.side_by_side) args.reverse ^= grp & 1u;
     }
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const uint32_t ring = (uint32_t)(uintptr_t)smem;                // LDS byte address of the ring (low half of the flat address)

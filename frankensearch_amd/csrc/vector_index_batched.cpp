@@ -1055,16 +1055,34 @@ SearchError VectorIndex::batched_main(const BatchedPlan& p, BatchedRound& r) {
     }
     // stage C: every group the B sample did not cover
     a.stage = 2;
-    const int main_grid = r.wide_qt ? r.wide_grid : r.full_grid;
+    // The register-resident-query kernel takes ALL the round's groups in one launch (gridDim.y = passes over the slab): a step pays
+    // one launch ramp and one chip-wide tail instead of one per 512 queries — what a 1.25M-row shard, whose pass is 0.2 ms, feels most.
+#ifdef FSGPU_LAB_SPLIT_LAUNCHES   // lab: one launch per 512-query group, as before round 4 (same-box A/B of the merged launch)
+    const uint32_t wide_groups = 0;
+#else
+    const uint32_t wide_groups = r.wide_qt ? r.ngroups / r.wide_mult : 0;
+#endif
+    // Two layouts of that launch.  Side by side: the groups run at once on wide_grid / groups walkers each, all blocks
+    // resident, walker w of every group on the same tiles at the same time — the slab is read from HBM once per launch, the other
+    // groups' fetches hit the L2 of the XCD the walker's blocks share (linear ids a multiple of 8 apart).  Sequential: group g's
+    // blocks take over the CUs as group g - 1's leave them, every group on the whole grid — one read of the slab per group.  The
+    // sequential layout stays for what cannot pair up: one group, a grid the groups do not divide into multiples of 8, slabs with
+    // fewer than four 128-row tiles per walker (nothing to share, and fewer, longer walkers lengthen the tail); FSGPU_WIDE_LAYOUT picks it.
+    const uint32_t walkers = wide_groups > 1 && (uint32_t)r.wide_grid % wide_groups == 0 ? (uint32_t)r.wide_grid / wide_groups : 0;
+    const bool side_by_side = walkers != 0 && walkers % 8 == 0 && (uint64_t)p.N >= (uint64_t)walkers * 4 * 128 && !knobs().wide_sequential;
+    const int main_grid = r.wide_qt ? (side_by_side ? (int)walkers : r.wide_grid) : r.full_grid;
     if (r.wide_qt) {  // the wide main pass visits every row (no skip test in its loop): stage B only tightened tau
         a.group_stride = 1;
         a.group_count = 0;
     }
     // (the wide pass appends to global lists: 16 slots per (query, block) keep lists + pool inside one selection pass;
     // ranks above 32 — the int8 fast tier anchors on 90 — let ~1,700 rows per query through and get 32)
+    // (side by side a list sees `groups` times the rows of a sequential one: it gets that many times the slots, up to kWideSlots —
+    // a query's lists hold what they held, and walkers x slots stays what one selection pass covers)
+    const uint32_t wide_slots = p.ksel_est > 32 ? (r.short_stages && p.i8f ? 16 : kWideSlots)
+                                                : std::min<uint32_t>(16, std::max<uint32_t>(8, (CAPQ - KC) / (uint32_t)r.wide_grid));
     a.slots = r.wide_qt ? (knobs().slots_main > 0 ? (uint32_t)knobs().slots_main
-                           : p.ksel_est > 32 ? (r.short_stages && p.i8f ? 16 : kWideSlots)
-                                             : std::min<uint32_t>(16, std::max<uint32_t>(8, (CAPQ - KC) / (uint32_t)main_grid)))
+                           : side_by_side ? std::min<uint32_t>(kWideSlots, wide_slots * wide_groups) : wide_slots)
                         : r.slots_for(r.full_grid);
     if (knobs().debug_batched) {   // the rule above
         std::vector<uint32_t> counts((size_t)r.QP * kMfmaSpillCountStride);
@@ -1075,14 +1093,6 @@ SearchError VectorIndex::batched_main(const BatchedPlan& p, BatchedRound& r) {
     }
     a.groups = 1;
     const uint32_t GM = r.G * r.wide_mult;  // queries per main-pass launch
-    // The register-resident-query kernel takes ALL the round's groups in one launch (gridDim.y = passes over the slab): a group's
-    // blocks start on a CU as the previous group's block leaves it, so a step pays one launch ramp and one chip-wide tail instead of
-    // one per 512 queries — what a 1.25M-row shard, whose pass is 0.2 ms, feels most.
-#ifdef FSGPU_LAB_SPLIT_LAUNCHES   // lab: one launch per 512-query group, as before round 4 (same-box A/B of the merged launch)
-    const uint32_t wide_groups = 0;
-#else
-    const uint32_t wide_groups = r.wide_qt ? r.ngroups / r.wide_mult : 0;
-#endif
     if (wide_groups) {
         MfmaScanArgs c = a;
         c.groups = wide_groups;
@@ -1093,8 +1103,11 @@ SearchError VectorIndex::batched_main(const BatchedPlan& p, BatchedRound& r) {
         c.spill = p.spill;
         c.spill_count = p.spill_count;
         c.overflow = r.overflow;
-        c.reverse = knobs().no_reverse ? 0 : (mf_pass_parity_ & 1);   // group g walks in direction (parity + g) & 1
-        mf_pass_parity_ += wide_groups;
+        c.side_by_side = side_by_side;
+        // sequential: group g walks in direction (parity + g) & 1; side by side: every group in direction parity & 1, consecutive
+        // launches alternate — either way a pass starts where the one before it ended (the turn stays in the Infinity Cache)
+        c.reverse = knobs().no_reverse ? 0 : (mf_pass_parity_ & 1);
+        mf_pass_parity_ += side_by_side ? 1 : wide_groups;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (profiling) {
             FSGPU_HIP(hipEventCreateWithFlags(&e0, hipEventReleaseToDevice));   // (timing only: no cache write-back around the launch)
