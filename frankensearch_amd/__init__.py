@@ -7,13 +7,13 @@ from . import _lib
 from .embed import Model2VecEmbedder, NativeEmbedder
 from .errors import (DeviceError, DimensionMismatch, IndexCorrupted, IndexVersionMismatch, InvalidConfig, IoError,
                      ModelLoadFailed, NoDevice, SearchError)
-from .index import (ClassifiedHits, NativeShardedIndex, VectorHit, VectorIndex, encode_f32_to_f16, pack_bitmap, widen_f16_to_f32,
+from .index import (ClassifiedHits, CompactionStats, VacuumStats, NativeShardedIndex, VectorHit, VectorIndex, encode_f32_to_f16, pack_bitmap, widen_f16_to_f32,
                     write_fsvi)
 from .hubness import HubnessConfig, apply_hubness_penalty, compute_query_hubness
 from .mmr import MmrConfig, mmr_rerank, mmr_step
 from .rerank import PURE_REORDER, RRF_COMBINE, NativeReranker, RerankCandidate, RerankScore, rerank_step
 
-__all__ = ["write_fsvi", "VectorIndex", "NativeShardedIndex", "VectorHit", "ClassifiedHits", "Model2VecEmbedder", "NativeEmbedder", "NativeReranker",
+__all__ = ["write_fsvi", "VectorIndex", "NativeShardedIndex", "VectorHit", "ClassifiedHits", "CompactionStats", "VacuumStats", "Model2VecEmbedder", "NativeEmbedder", "NativeReranker",
            "RerankCandidate", "RerankScore", "rerank_step", "MmrConfig", "mmr_rerank", "mmr_step", "HubnessConfig", "compute_query_hubness", "apply_hubness_penalty", "PURE_REORDER", "RRF_COMBINE", "SearchError", "DimensionMismatch",
            "InvalidConfig", "IndexCorrupted", "IndexVersionMismatch", "IoError", "DeviceError", "NoDevice", "ModelLoadFailed",
            "encode_f32_to_f16", "widen_f16_to_f32", "pack_bitmap", "_lib"]

@@ -61,6 +61,22 @@ SIGNATURES = {
     "fsgpu_index_soft_delete": (_i32, [_vp, C.c_char_p, _u32, C.POINTER(_i32)]),
     "fsgpu_index_wal_append": (_i32, [_vp, C.c_char_p, _u32, _vp, _u32]),
     "fsgpu_index_wal_record_count": (_u64, [_vp]),
+    "fsgpu_index_wal_append_batch": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32]),
+    "fsgpu_index_compact": (_i32, [_vp, C.c_char_p, _vp]),
+    "fsgpu_index_vacuum": (_i32, [_vp, C.c_char_p, _vp]),
+    "fsgpu_index_needs_compaction": (_i32, [_vp, _u64, C.c_double, C.POINTER(_i32)]),
+    "fsgpu_index_needs_vacuum": (_i32, [_vp, C.POINTER(_i32)]),
+    "fsgpu_index_tombstone_count": (_u64, [_vp]),
+    "fsgpu_index_live_count": (_u64, [_vp]),
+    "fsgpu_index_generation": (_u64, [_vp]),
+    "fsgpu_index_compaction_gen": (_u32, [_vp]),
+    "fsgpu_sharded_compact": (_i32, [_vp, C.c_char_p, _vp]),
+    "fsgpu_sharded_vacuum": (_i32, [_vp, C.c_char_p, _vp]),
+    "fsgpu_lab_index_set_compact_launch_rows": (_i32, [_vp, _u32]),
+    "fsgpu_lab_index_set_compact_nt_stores": (_i32, [_vp, _i32]),
+    "fsgpu_lab_index_last_rewrite": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    "fsgpu_lab_index_attach_synthetic_doc_ids": (_i32, [_vp]),
+    "fsgpu_lab_device_copy_ms": (_i32, [_i32, _u64, _u32, C.POINTER(C.c_double)]),
     "fsgpu_index_set_live_bitmap": (_i32, [_vp, _vp]),
     "fsgpu_search_topk": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "fsgpu_search_topk_exact": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),

@@ -63,6 +63,7 @@ struct fsgpu_alignment {
 struct fsgpu_allow_bitmap {   // a precomputed SearchFilter resident on an index's device
     int device = -1;
     uint64_t nrows = 0, allowed = 0;
+    uint64_t generation = 0;       // the index's slab generation it was made for: row ids do not survive compact / vacuum
     std::vector<uint64_t> words;   // host copy: the selectivity rule (1/50) and the coalescer's batch key
     fsgpu::DeviceBuffer dev;
 };
@@ -277,6 +278,23 @@ fsgpu_status coalesced_sharded_search(fsgpu_sharded* idx, const float* query, ui
     });
 }
 
+// compact / vacuum: the state lock exclusively — a search holds it shared for as long as it is on a lane, so none is —, the index's
+// lock, and every replica's lock taken once so that whatever held it has left (they cannot be held across the call: a rewrite destroys
+// the replicas).  The lanes are made again on demand.
+template <typename F>
+fsgpu_status rewrite_locked(fsgpu_index* idx, F&& body) {
+    return guarded([&]() -> fsgpu_status {
+        std::unique_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lanes(idx->lanes_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        for (size_t i = 0; i < idx->impl.replica_count(); ++i) std::lock_guard<std::mutex> drained(idx->impl.replica(i)->mutex());
+        const uint64_t before = idx->impl.generation();
+        const fsgpu::SearchError e = body();
+        if (idx->impl.generation() != before) idx->lanes_ready.store(false, std::memory_order_release);
+        return finish(e);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,6 +402,7 @@ fsgpu_status fsgpu_index_set_int8_latency(fsgpu_index* idx, int32_t enabled) {
     std::unique_lock<std::shared_mutex> state(idx->state_mu);
     std::lock_guard<std::mutex> lock(idx->impl.mutex());
     idx->impl.int8_latency = enabled != 0;
+    idx->impl.int8_latency_build_now = enabled == FSGPU_INT8_LATENCY_BUILD_NOW;
     if (enabled == FSGPU_INT8_LATENCY_BUILD_NOW) return finish(idx->impl.prepare_int8_latency());
     return FSGPU_OK;
 }
@@ -506,6 +525,7 @@ fsgpu_status fsgpu_allow_bitmap_create(fsgpu_index* idx, const uint64_t* allow_b
         auto f = std::make_unique<fsgpu_allow_bitmap>();
         f->device = idx->impl.device();
         f->nrows = idx->impl.record_count();
+        f->generation = idx->impl.generation();
         const size_t words = (size_t)((f->nrows + 63) / 64);
         f->words.assign(allow_bitmap, allow_bitmap + words);
         if (words && (f->nrows & 63)) f->words.back() &= (1ull << (f->nrows & 63)) - 1ull;
@@ -536,6 +556,8 @@ static fsgpu_status check_filter(const fsgpu_index* idx, const fsgpu_allow_bitma
     if (!idx || !f) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
     if (f->device != idx->impl.device() || f->nrows != idx->impl.record_count())
         return fail(FSGPU_ERR_INVALID_CONFIG, "the allow bitmap was made for another index (device or record count differ)");
+    if (f->generation != idx->impl.generation())   // (a vacuum followed by appends can restore the old record count)
+        return fail(FSGPU_ERR_INVALID_CONFIG, "the allow bitmap was made before the index was compacted or vacuumed: its row ids are stale");
     return FSGPU_OK;
 }
 
@@ -1121,6 +1143,154 @@ fsgpu_status fsgpu_index_wal_append(fsgpu_index* idx, const char* doc_id, uint32
 }
 
 uint64_t fsgpu_index_wal_record_count(const fsgpu_index* idx) { return idx ? idx->impl.wal_record_count() : 0; }
+
+// VectorIndex::append_batch (lib.rs:2546-2720)
+fsgpu_status fsgpu_index_wal_append_batch(fsgpu_index* idx, uint32_t n, const char* const* doc_ids, const uint32_t* doc_id_lens,
+                                          const float* vectors, uint32_t vector_len) {
+    if (!idx || (n && (!doc_ids || !doc_id_lens || !vectors))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::unique_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        const fsgpu::SearchError e = idx->impl.wal_append_batch(n, doc_ids, doc_id_lens, vectors, vector_len);
+        idx->impl.sync_replicas();   // the shadowed main rows were tombstoned
+        return finish(e);
+    });
+}
+
+// VectorIndex::compact (lib.rs:2734-2854)
+fsgpu_status fsgpu_index_compact(fsgpu_index* idx, const char* path, fsgpu_compaction_stats* out) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return rewrite_locked(idx, [&]() {
+        fsgpu::VectorIndex::CompactionStats st;
+        const fsgpu::SearchError e = idx->impl.compact(path, &st);
+        if (e.ok() && out) *out = fsgpu_compaction_stats{st.main_records_before, st.wal_records, st.total_records_after, st.elapsed_ms};
+        return e;
+    });
+}
+
+// VectorIndex::vacuum (lib.rs:2485-2521)
+fsgpu_status fsgpu_index_vacuum(fsgpu_index* idx, const char* path, fsgpu_vacuum_stats* out) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return rewrite_locked(idx, [&]() {
+        fsgpu::VectorIndex::VacuumStats st;
+        const fsgpu::SearchError e = idx->impl.vacuum(path, &st);
+        if (e.ok() && out) *out = fsgpu_vacuum_stats{st.records_before, st.records_after, st.tombstones_removed, st.bytes_reclaimed, st.elapsed_ms};
+        return e;
+    });
+}
+
+// VectorIndex::needs_compaction (lib.rs:2270-2292)
+fsgpu_status fsgpu_index_needs_compaction(fsgpu_index* idx, uint64_t threshold, double ratio, int32_t* out) {
+    if (!idx || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::unique_lock<std::shared_mutex> state(idx->state_mu);
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    *out = idx->impl.needs_compaction(threshold, ratio) ? 1 : 0;
+    return FSGPU_OK;
+}
+
+// VectorIndex::needs_vacuum (lib.rs:174, 2464-2475)
+fsgpu_status fsgpu_index_needs_vacuum(fsgpu_index* idx, int32_t* out) {
+    if (!idx || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::unique_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        const fsgpu::SearchError e = idx->impl.fetch_live_host();
+        if (!e.ok()) return finish(e);
+        *out = idx->impl.needs_vacuum() ? 1 : 0;
+        return FSGPU_OK;
+    });
+}
+
+static uint64_t counted_rows(fsgpu_index* idx, bool tombstones) {
+    if (!idx) return 0;
+    std::unique_lock<std::shared_mutex> state(idx->state_mu);
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    if (!idx->impl.fetch_live_host().ok()) return 0;
+    return tombstones ? idx->impl.tombstone_count() : idx->impl.live_count();
+}
+uint64_t fsgpu_index_tombstone_count(fsgpu_index* idx) { return counted_rows(idx, true); }   /* VectorIndex::tombstone_count */
+uint64_t fsgpu_index_live_count(fsgpu_index* idx) { return counted_rows(idx, false); }
+
+uint64_t fsgpu_index_generation(const fsgpu_index* idx) { return idx ? idx->impl.generation() : 0; }
+uint32_t fsgpu_index_compaction_gen(const fsgpu_index* idx) { return idx ? idx->impl.compaction_gen() : 0; }
+
+// a row-sharded handle refuses both: the rows would have to be re-sharded and exchanged
+fsgpu_status fsgpu_sharded_compact(fsgpu_sharded* idx, const char* path, fsgpu_compaction_stats* out) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    (void)out;
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.compact(path));
+    });
+}
+fsgpu_status fsgpu_sharded_vacuum(fsgpu_sharded* idx, const char* path, fsgpu_vacuum_stats* out) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    (void)out;
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.vacuum(path));
+    });
+}
+
+// ---- lab (include/fsgpu_lab.h) ----
+fsgpu_status fsgpu_lab_index_set_compact_launch_rows(fsgpu_index* idx, uint32_t rows) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    idx->impl.compact_launch_rows = rows;
+    return FSGPU_OK;
+}
+fsgpu_status fsgpu_lab_index_set_compact_nt_stores(fsgpu_index* idx, int32_t enabled) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    idx->impl.compact_nt_stores = enabled != 0;
+    return FSGPU_OK;
+}
+fsgpu_status fsgpu_lab_index_last_rewrite(fsgpu_index* idx, double* out_ms5, uint64_t* out_counts3) {
+    if (!idx || !out_ms5 || !out_counts3) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    const fsgpu::VectorIndex::RewriteTimes& t = idx->impl.last_rewrite;
+    out_ms5[0] = t.plan_ms, out_ms5[1] = t.kernel_ms, out_ms5[2] = t.tables_ms, out_ms5[3] = t.file_ms, out_ms5[4] = t.rebuild_ms;
+    out_counts3[0] = t.runs, out_counts3[1] = t.launches, out_counts3[2] = t.dst_bytes;
+    return FSGPU_OK;
+}
+fsgpu_status fsgpu_lab_index_attach_synthetic_doc_ids(fsgpu_index* idx) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::unique_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.lab_attach_synthetic_doc_ids());
+    });
+}
+fsgpu_status fsgpu_lab_device_copy_ms(int32_t device, uint64_t bytes, uint32_t reps, double* out_ms) {
+    if (!out_ms && reps) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_NO_DEVICE, "hipSetDevice failed");
+        fsgpu::DeviceBuffer a, b;
+        fsgpu::SearchError e = a.reserve((size_t)bytes);
+        if (e.ok()) e = b.reserve((size_t)bytes);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipError_t he = hipSuccess;
+        if (e.ok()) he = hipMemset(a.ptr, 1, (size_t)bytes);
+        if (e.ok() && he == hipSuccess) he = hipEventCreate(&e0);
+        if (e.ok() && he == hipSuccess) he = hipEventCreate(&e1);
+        for (uint32_t r = 0; e.ok() && he == hipSuccess && r < reps; ++r) {
+            he = hipEventRecord(e0, nullptr);
+            if (he == hipSuccess) he = hipMemcpyAsync(b.ptr, a.ptr, (size_t)bytes, hipMemcpyDeviceToDevice, nullptr);
+            if (he == hipSuccess) he = hipEventRecord(e1, nullptr);
+            if (he == hipSuccess) he = hipEventSynchronize(e1);
+            float ms = 0.f;
+            if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+            out_ms[r] = ms;
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        a.release();
+        b.release();
+        if (!e.ok()) return finish(e);
+        if (he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(he));
+        return FSGPU_OK;
+    });
+}
 
 fsgpu_status fsgpu_gather_dot(fsgpu_index* idx, const float* query, uint32_t query_len, const uint32_t* rows,
                               uint32_t n, float* out_scores) {

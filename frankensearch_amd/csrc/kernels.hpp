@@ -490,4 +490,25 @@ struct HubnessArgs {
 };
 hipError_t launch_hubness(const HubnessArgs& args, hipStream_t stream);
 
+// compact_kernels.hip: rewrite_index's vector pass (lib.rs:3003-3045) as a segmented copy.  The host hands over RUNS — maximal
+// stretches of surviving consecutive rows, in destination order, covering the new slab without a gap; a run reads the old slab or
+// (kCompactFromWal) the block of already encoded WAL rows.  A wave owns a contiguous range of destination bytes, finds its first
+// run by one binary search and walks on from there.
+constexpr uint32_t kCompactLaunchRows = 1u << 20;     // destination rows per launch: no single launch holds a shared card for long
+constexpr uint32_t kCompactWaveBytes = 16 * 1024;     // destination bytes per wave
+constexpr uint64_t kCompactFromWal = 1ull << 63;      // in CompactRun::src: the offset is into the WAL block
+struct CompactRun {
+    uint64_t src;     // byte offset of the run's first row in its source (| kCompactFromWal)
+    uint64_t dst;     // byte offset of the run's first row in the new slab
+};                    // (a run ends where the next begins; runs[nruns].dst = the new slab's size)
+struct CompactArgs {
+    const unsigned char* slab;   // the old slab
+    const unsigned char* wal;    // WAL rows in slab format, [W, row_bytes]
+    unsigned char* out;          // the new slab
+    const CompactRun* runs;      // [nruns + 1]
+    uint64_t nruns;
+    uint64_t dst_begin, dst_end; // this launch's destination bytes
+};
+hipError_t launch_compact_runs(const CompactArgs& args, bool nt_stores, hipStream_t stream);
+
 }  // namespace fsgpu

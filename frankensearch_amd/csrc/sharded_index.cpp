@@ -855,6 +855,18 @@ SearchError ShardedIndex::soft_delete(const char* doc_id, uint32_t len, int32_t*
     return SearchError{};
 }
 
+// compact / vacuum permute the rows: under a row-sharded handle that means re-sharding and an exchange of rows, which is not built.
+// The catalog refuses with the reason (VectorIndex::rewrite_refusal); a handle without a catalog has nothing to rewrite here either.
+SearchError ShardedIndex::compact(const char* path) {
+    if (catalog_) return catalog_->compact(path, nullptr);
+    return make_err(FSGPU_ERR_INVALID_CONFIG, "compact / vacuum of a row-sharded index is not supported: the rows would have to be re-sharded");
+}
+
+SearchError ShardedIndex::vacuum(const char* path) {
+    if (catalog_) return catalog_->vacuum(path, nullptr);
+    return make_err(FSGPU_ERR_INVALID_CONFIG, "compact / vacuum of a row-sharded index is not supported: the rows would have to be re-sharded");
+}
+
 SearchError ShardedIndex::wal_append(const char* doc_id, uint32_t len, const float* vector, uint32_t vector_len) {
     if (!catalog_) return make_err(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
     for (const RootSlot& r : root_)

@@ -88,6 +88,9 @@ class ShardedIndex {
     // VectorIndex::soft_delete / append / doc ids / search_top_k with WAL + dedup: need open_fsvi's tables
     SearchError soft_delete(const char* doc_id, uint32_t len, int32_t* deleted);
     SearchError wal_append(const char* doc_id, uint32_t len, const float* vector, uint32_t vector_len);
+    // refused (FSGPU_ERR_INVALID_CONFIG): a rewrite of the rows would have to re-shard them
+    SearchError compact(const char* path);
+    SearchError vacuum(const char* path);
     SearchError doc_id_at(uint32_t row, const char** ptr, uint32_t* len) const;
     SearchError search_hits(const float* query, uint32_t query_len, uint32_t k, uint32_t* out_rows, float* out_scores,
                             uint32_t* out_count);

@@ -26,31 +26,6 @@ using namespace detail;
 
 namespace {
 
-uint32_t crc32_ieee(const uint8_t* p, size_t n) {
-    static uint32_t table[256];
-    static bool init = false;
-    if (!init) {
-        for (uint32_t i = 0; i < 256; ++i) {
-            uint32_t c = i;
-            for (int b = 0; b < 8; ++b) c = (c & 1u) ? (0xedb88320u ^ (c >> 1)) : (c >> 1);
-            table[i] = c;
-        }
-        init = true;
-    }
-    uint32_t c = 0xffffffffu;
-    for (size_t i = 0; i < n; ++i) c = table[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-    return ~c;
-}
-
-uint64_t fnv1a(const char* p, size_t n) {
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (size_t i = 0; i < n; ++i) {
-        h ^= (uint8_t)p[i];
-        h *= 0x100000001b3ull;
-    }
-    return h;
-}
-
 template <typename T>
 T read_le(const uint8_t* p) {
     T v = 0;
@@ -366,12 +341,15 @@ SearchError VectorIndex::open_fsvi_impl(const char* path, int device, FsviImage*
     if (version != 1)
         return make_error(FSGPU_ERR_INDEX_VERSION_MISMATCH,
                           "FSVI version expected 1, found " + std::to_string(version));
+    std::string header_strings[2];   // IndexMetadata::embedder_id / embedder_revision: kept for rewrite_index (compact / vacuum)
+    int header_field = 0;
     for (const char* field : {"embedder_id", "embedder_revision"}) {
         if (!need(2)) return corrupt(std::string("truncated header (") + field + "_len)");
         const size_t len = read_le<uint16_t>(&data[c]);
         c += 2;
         if (!need(len)) return corrupt(std::string("truncated header (") + field + ")");
         if (!valid_utf8(&data[c], len)) return corrupt(std::string("invalid UTF-8 in ") + field);  // lib.rs:4073-4095
+        header_strings[header_field++].assign(reinterpret_cast<const char*>(&data[c]), len);
         c += len;
     }
     if (!need(4)) return corrupt("truncated header (dimension)");
@@ -382,6 +360,8 @@ SearchError VectorIndex::open_fsvi_impl(const char* path, int device, FsviImage*
     const uint8_t quant = data[c++];
     if (quant > 1) return corrupt("unknown quantization byte");
     if (!need(3)) return corrupt("truncated header (reserved)");
+    const uint8_t file_gen = data[c];   // compaction_gen, then the u16 publication nonce (lib.rs:5714-5768)
+    const uint16_t file_nonce = read_le<uint16_t>(&data[c + 1]);
     c += 3;
     if (!need(16)) return corrupt("truncated header (record_count / vectors_offset)");
     const uint64_t record_count = read_le<uint64_t>(&data[c]);
@@ -426,6 +406,11 @@ SearchError VectorIndex::open_fsvi_impl(const char* path, int device, FsviImage*
         if ((flags & 0x0001u) == 0) live[(size_t)(r >> 6)] |= 1ull << (r & 63);
     }
     doc_offsets_[(size_t)record_count] = doc_blob_.size();
+    embedder_id_ = header_strings[0];
+    embedder_revision_ = header_strings[1];
+    compaction_gen_ = file_gen;
+    publication_nonce_ = file_nonce;
+    from_fsvi_ = true;
     if (image) {   // catalog of a sharded index: no device copy here
         catalog_only_ = true;
         dim_ = dim;
@@ -510,44 +495,9 @@ uint32_t host_score_ord(float score) {
 
 }  // namespace
 
+// VectorIndex::append (lib.rs:2532-2534): a batch of one (vector_index_compact.cpp)
 SearchError VectorIndex::wal_append(const char* doc_id, uint32_t len, const float* vector, uint32_t vector_len) {
-    if (doc_offsets_.empty()) return make_error(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
-        return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
-    if (vector_len != dim_)
-        return make_error(FSGPU_ERR_DIMENSION_MISMATCH,
-                          "expected " + std::to_string(dim_) + ", found " + std::to_string(vector_len));
-    float norm_sq = 0.f;
-    for (uint32_t i = 0; i < vector_len; ++i) {
-        if (!std::isfinite(vector[i]))
-            return make_error(FSGPU_ERR_INVALID_CONFIG, "all embedding values must be finite");
-        const float p = vector[i] * vector[i];
-        norm_sq = norm_sq + p;
-    }
-    if (!(norm_sq > 0.0f) || !std::isfinite(norm_sq))
-        return make_error(FSGPU_ERR_INVALID_CONFIG, "embedding norm must be non-zero and finite");
-    if (len > 0xffffu) return make_error(FSGPU_ERR_INVALID_CONFIG, "doc_id byte length must fit in u16");
-    const std::string id(doc_id, len);
-    // supersede older resident copies (lib.rs:2641-2647), then admit the new entry
-    wal_.erase(std::remove_if(wal_.begin(), wal_.end(), [&](const WalEntry& e) { return e.doc_id == id; }),
-               wal_.end());
-    wal_.push_back(WalEntry{id, std::vector<float>(vector, vector + vector_len)});
-    // tombstone the first live main row with this doc id so it cannot take a top-k slot (lib.rs:2665-2710)
-    const uint64_t h = fnv1a(doc_id, len);
-    auto lo = std::lower_bound(doc_hashes_.begin(), doc_hashes_.end(), h);
-    for (auto it = lo; it != doc_hashes_.end() && *it == h; ++it) {
-        const size_t r = (size_t)(it - doc_hashes_.begin());
-        const size_t dl = (size_t)(doc_offsets_[r + 1] - doc_offsets_[r]);
-        if (dl != len || std::memcmp(doc_blob_.data() + doc_offsets_[r], doc_id, len) != 0) continue;
-        if (live_host_.empty()) live_host_.assign((size_t)((nrows_ + 63) / 64), ~0ull);
-        if ((live_host_[r >> 6] >> (r & 63)) & 1ull) {
-            live_host_[r >> 6] &= ~(1ull << (r & 63));
-            std::vector<uint64_t> copy = live_host_;
-            FSGPU_TRY(set_live_bitmap(copy.data()));
-            break;
-        }
-    }
-    return ok();
+    return wal_append_batch(1, &doc_id, &len, vector, vector_len);
 }
 
 SearchError VectorIndex::search_hits(const float* query, uint32_t query_len, uint32_t k, uint32_t* out_rows,
@@ -644,6 +594,7 @@ SearchError VectorIndex::soft_delete(const char* doc_id, uint32_t len, int32_t* 
     if (doc_offsets_.empty()) return make_error(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
     if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
+    FSGPU_TRY(fetch_live_host());
     const uint64_t h = fnv1a(doc_id, len);
     // rows are sorted by (hash, doc_id) (lib.rs:3758-3762): binary-search the hash run
     auto lo = std::lower_bound(doc_hashes_.begin(), doc_hashes_.end(), h);

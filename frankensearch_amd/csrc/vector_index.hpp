@@ -203,6 +203,44 @@ class VectorIndex {
     // sims, greatest first.  Host pointers; blocks; own workspaces on the index's stream.
     SearchError compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out, float* out_topk);
 
+    // VectorIndex::append_batch (lib.rs:2546-2720): every entry validated before anything changes, last-wins dedup inside the batch,
+    // resident copies superseded, the first live main row of each doc id tombstoned, ONE live-bitmap upload.  wal_append is a batch of one.
+    SearchError wal_append_batch(uint32_t n, const char* const* doc_ids, const uint32_t* doc_id_lens, const float* vectors, uint32_t vector_len);
+    // VectorIndex::compact / vacuum / rewrite_index (lib.rs:2734-2854, 2485-2521, 2871-3094) on the device-resident slab
+    // (vector_index_compact.cpp, compact_kernels.hip): the host merges the sorted record table with the sorted WAL into RUNS of
+    // surviving rows, the device copies them into a fresh slab, the tables are rebuilt, everything derived from row ids or slab bytes is
+    // dropped.  path (nullable): the new FSVI image is also written beside it and renamed over it.  On failure nothing has changed.
+    struct CompactionStats {
+        uint64_t main_records_before = 0, wal_records = 0, total_records_after = 0;
+        double elapsed_ms = 0.0;
+    };
+    struct VacuumStats {
+        uint64_t records_before = 0, records_after = 0, tombstones_removed = 0, bytes_reclaimed = 0;
+        double elapsed_ms = 0.0;
+    };
+    SearchError compact(const char* path, CompactionStats* out);
+    SearchError vacuum(const char* path, VacuumStats* out);
+    // needs_compaction (lib.rs:2270-2292) with WalConfig's two numbers as arguments; needs_vacuum (lib.rs:174, 2464-2475)
+    bool needs_compaction(uint64_t threshold, double ratio) const;
+    bool needs_vacuum() const { return nrows_ != 0 && (double)tombstone_count() / (double)nrows_ > 0.20; }   // strict
+    // (an adopted device slab came with a device bitmap only: fetch_live_host brings it down once, before anything counts tombstones)
+    SearchError fetch_live_host();
+    uint64_t tombstone_count() const;
+    uint64_t live_count() const { return nrows_ - tombstone_count(); }
+    uint64_t generation() const { return generation_; }   // rewrites that changed the slab since the handle was made
+    uint8_t compaction_gen() const { return compaction_gen_; }
+    // lab: rows one launch of the compaction kernel covers (0 = kCompactLaunchRows) and its stores' cache policy; what the last rewrite cost
+    uint32_t compact_launch_rows = 0;
+    bool compact_nt_stores = false;
+    struct RewriteTimes {
+        double plan_ms = 0, kernel_ms = 0, tables_ms = 0, file_ms = 0, rebuild_ms = 0;
+        uint64_t runs = 0, launches = 0, dst_bytes = 0;
+    };
+    RewriteTimes last_rewrite;
+    // lab: a doc-id table for an index made from a bare slab ("doc-000000000" ... in (hash, doc id) order over the rows as they are),
+    // so that the write path can be measured on a generated corpus that never was a file
+    SearchError lab_attach_synthetic_doc_ids();
+
     std::mutex& mutex() { return mu_; }
     int device() const { return device_; }
     int32_t hreduce = 0;
@@ -218,6 +256,7 @@ class VectorIndex {
     int32_t batched_filter = 0;
     // fsgpu_index_set_int8_latency: unfiltered fsgpu_search_topk calls of a few queries go through the int8 filter too
     bool int8_latency = false;
+    bool int8_latency_build_now = false;   // FSGPU_INT8_LATENCY_BUILD_NOW is in force: a rewrite of the slab rebuilds the copies before it returns
     // fsgpu_index_set_filter_rotation: 0 = automatic (rotate the filter's copy when the slab has outlier channels), 1 = never, 2 = always.
     // Takes effect when the filter's copy is built (first batched search / fsgpu_index_int8_filter_bound).
     int32_t filter_rotation = 0;
@@ -328,6 +367,12 @@ class VectorIndex {
     };
     TwoPassLane tp_lane_;
     SearchError common_init(int device);
+    // rewrite_index: `sources` in output order — a main row, or (kWalSource | WAL index)
+    static constexpr uint64_t kWalSource = 1ull << 63;
+    SearchError rewrite(const std::vector<uint64_t>& sources, uint8_t new_gen, bool clear_wal, const char* path);
+    SearchError rewrite_refusal() const;
+    void drop_derived_state();
+    uint64_t fsvi_image_bytes(uint64_t rows, uint64_t strings_len) const;
     SearchError fused_search(const float* queries_dev, uint32_t nq, uint32_t k_out, uint32_t k_eff,
                              const uint64_t* allow_dev, uint32_t* out_rows_dev, float* out_scores_dev,
                              uint32_t* out_counts_dev, u64* out_packed_dev, hipStream_t stream);
@@ -415,6 +460,12 @@ class VectorIndex {
         std::vector<float> embedding;
     };
     std::vector<WalEntry> wal_;
+    // what parse_header keeps of an FSVI file (IndexMetadata, lib.rs:4049-4144): rewrite_index writes it back
+    std::string embedder_id_, embedder_revision_;
+    uint8_t compaction_gen_ = 0;
+    uint16_t publication_nonce_ = 0;
+    bool from_fsvi_ = false;
+    uint64_t generation_ = 0;
 };
 
 class Model2VecEmbedder {

@@ -3,10 +3,12 @@
 //   vector_index.cpp          lifecycle, FSVI image, WAL, tombstones, the exact scan paths, MRL views, packed lists
 //   vector_index_batched.cpp  the batched (matrix-core) search: plan, sample, main pass, selections, fallback, tickets, and the
 //                             int8 filter's copy of the slab
+//   vector_index_compact.cpp  append_batch, compact, vacuum: the plan, the device rewrite of the slab, the tables, the FSVI image
 //   vector_index_lone.cpp     one query at a time: the certified int8 pass, the exact halves, the quantised two-pass lanes
 #pragma once
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -32,6 +34,32 @@ inline SearchError make_error(int32_t code, std::string detail) {
     e.code = code;
     e.detail = std::move(detail);
     return e;
+}
+
+// CRC-32 (IEEE) of the FSVI header and FNV-1a 64 of a doc id (lib.rs fnv1a_hash): shared by the reader, the writer and rewrite_index
+inline uint32_t crc32_ieee(const uint8_t* p, size_t n) {
+    static uint32_t table[256];
+    static bool init = false;
+    if (!init) {
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int b = 0; b < 8; ++b) c = (c & 1u) ? (0xedb88320u ^ (c >> 1)) : (c >> 1);
+            table[i] = c;
+        }
+        init = true;
+    }
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < n; ++i) c = table[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+    return ~c;
+}
+
+inline uint64_t fnv1a(const char* p, size_t n) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i) {
+        h ^= (uint8_t)p[i];
+        h *= 0x100000001b3ull;
+    }
+    return h;
 }
 
 // Switches read from the environment ONCE (getenv is not safe against concurrent setenv).  A default build reads four:

@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .errors import check
+from .errors import DimensionMismatch, check
 
 
 @dataclass(frozen=True)
@@ -53,6 +53,35 @@ def pack_bitmap(mask: np.ndarray) -> np.ndarray:
 class _MrlStats(C.Structure):
     _fields_ = [("scan_dims", C.c_uint32), ("rescore_dims", C.c_uint32), ("candidates_rescored", C.c_uint32),
                 ("records_scanned", C.c_uint64), ("fell_back_to_full", C.c_int32)]
+
+
+class _CompactionStats(C.Structure):
+    _fields_ = [("main_records_before", C.c_uint64), ("wal_records", C.c_uint64), ("total_records_after", C.c_uint64),
+                ("elapsed_ms", C.c_double)]
+
+
+class _VacuumStats(C.Structure):
+    _fields_ = [("records_before", C.c_uint64), ("records_after", C.c_uint64), ("tombstones_removed", C.c_uint64),
+                ("bytes_reclaimed", C.c_uint64), ("elapsed_ms", C.c_double)]
+
+
+@dataclass
+class CompactionStats:
+    """wal::CompactionStats (wal.rs:111)."""
+    main_records_before: int
+    wal_records: int
+    total_records_after: int
+    elapsed_ms: float
+
+
+@dataclass
+class VacuumStats:
+    """VacuumStats (lib.rs:726); the duration in milliseconds."""
+    records_before: int
+    records_after: int
+    tombstones_removed: int
+    bytes_reclaimed: int
+    elapsed_ms: float
 
 
 class VectorIndex:
@@ -172,6 +201,59 @@ class VectorIndex:
 
     def wal_record_count(self) -> int:
         return _lib.lib().fsgpu_index_wal_record_count(self._h)
+
+    def append_batch(self, entries: Sequence[Tuple[str, Sequence[float]]]) -> None:
+        """VectorIndex::append_batch (lib.rs:2546): all entries validated before anything changes, last-wins inside the batch, one
+        live-bitmap upload."""
+        entries = list(entries)
+        if not entries:
+            return
+        ids = [doc_id.encode() for doc_id, _ in entries]
+        vecs = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for _, v in entries]
+        if any(v.size != vecs[0].size for v in vecs):
+            raise DimensionMismatch("the vectors of a batch must have one length")
+        block = np.ascontiguousarray(np.stack(vecs))
+        ptrs = (C.c_char_p * len(ids))(*ids)
+        lens = np.asarray([len(b) for b in ids], dtype=np.uint32)
+        check(_lib.lib().fsgpu_index_wal_append_batch(self._h, len(ids), C.cast(ptrs, C.c_void_p), _ptr(lens), _ptr(block),
+                                                      block.shape[1]))
+
+    def compact(self, path: Optional[str] = None) -> CompactionStats:
+        """VectorIndex::compact (lib.rs:2734): folds the resident WAL into the slab on the device (fsgpu_index_compact); path: the
+        new FSVI image is also written there.  Row ids change: resident filters, alignments and hubness tables must be made again."""
+        st = _CompactionStats()
+        check(_lib.lib().fsgpu_index_compact(self._h, None if path is None else str(path).encode(), C.byref(st)))
+        return CompactionStats(st.main_records_before, st.wal_records, st.total_records_after, st.elapsed_ms)
+
+    def vacuum(self, path: Optional[str] = None) -> VacuumStats:
+        """VectorIndex::vacuum (lib.rs:2485): drops the tombstoned rows from the slab on the device; the WAL stays resident."""
+        st = _VacuumStats()
+        check(_lib.lib().fsgpu_index_vacuum(self._h, None if path is None else str(path).encode(), C.byref(st)))
+        return VacuumStats(st.records_before, st.records_after, st.tombstones_removed, st.bytes_reclaimed, st.elapsed_ms)
+
+    def needs_compaction(self, threshold: int = 1000, ratio: float = 0.10) -> bool:
+        """VectorIndex::needs_compaction (lib.rs:2270) with WalConfig's two numbers (defaults: the reference's)."""
+        out = C.c_int32()
+        check(_lib.lib().fsgpu_index_needs_compaction(self._h, threshold, ratio, C.byref(out)))
+        return bool(out.value)
+
+    def needs_vacuum(self) -> bool:
+        out = C.c_int32()
+        check(_lib.lib().fsgpu_index_needs_vacuum(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def tombstone_count(self) -> int:
+        return _lib.lib().fsgpu_index_tombstone_count(self._h)
+
+    def live_count(self) -> int:
+        return _lib.lib().fsgpu_index_live_count(self._h)
+
+    def generation(self) -> int:
+        """Rewrites (compact / vacuum) that changed the slab since the handle was made."""
+        return _lib.lib().fsgpu_index_generation(self._h)
+
+    def compaction_gen(self) -> int:
+        return _lib.lib().fsgpu_index_compaction_gen(self._h)
 
     def set_live(self, live: Optional[np.ndarray]) -> None:
         bm = pack_bitmap(live) if live is not None else None
@@ -670,6 +752,13 @@ class NativeShardedIndex:
 
     def wal_record_count(self) -> int:
         return _lib.lib().fsgpu_sharded_wal_record_count(self._h)
+
+    def compact(self, path: Optional[str] = None) -> None:
+        """Always InvalidConfig: a row-sharded handle cannot be rewritten (its rows would have to be re-sharded)."""
+        check(_lib.lib().fsgpu_sharded_compact(self._h, None if path is None else str(path).encode(), None))
+
+    def vacuum(self, path: Optional[str] = None) -> None:
+        check(_lib.lib().fsgpu_sharded_vacuum(self._h, None if path is None else str(path).encode(), None))
 
     def doc_id_at(self, row: int) -> str:
         p, n = C.c_void_p(), C.c_uint32()

@@ -133,6 +133,67 @@ fsgpu_status fsgpu_index_allow_bitmap_for_hashes(const fsgpu_index *idx, const u
 fsgpu_status fsgpu_index_wal_append(fsgpu_index *idx, const char *doc_id, uint32_t doc_id_len, const float *vector,
                                     uint32_t vector_len);
 uint64_t fsgpu_index_wal_record_count(const fsgpu_index *idx); /* VectorIndex::wal_record_count */
+/* VectorIndex::append_batch (lib.rs:2546-2720): n entries, vectors [n, vector_len] row-major.  EVERY entry is validated before
+ * anything changes (dimension, finite values, usable norm, doc id <= u16 bytes: one bad entry and the index is as it was); a doc id
+ * repeated inside the batch keeps its last vector (lib.rs:2604-2615); resident copies are superseded; the first live main row of each
+ * doc id is tombstoned; the live bitmap goes up ONCE.  fsgpu_index_wal_append is a batch of one. */
+fsgpu_status fsgpu_index_wal_append_batch(fsgpu_index *idx, uint32_t n, const char *const *doc_ids, const uint32_t *doc_id_lens,
+                                          const float *vectors, uint32_t vector_len);
+
+/* ---- compaction and vacuum: the WAL and the tombstones folded into the slab, on the device ----
+ * Both calls replace the index's slab by a new one that holds the surviving rows only (an HBM-to-HBM segmented copy into a fresh
+ * allocation: transiently both slabs are resident), rebuild the record tables on the host and clear every record flag.
+ * path = NULL: device only.  path != NULL: the new FSVI v1 image is ALSO written — rewrite_index's layout (lib.rs:2871-3094): header
+ * with CRC32, 16-byte records, string table, padding to 64, slab — under a temporary name beside the target and renamed over it.  The
+ * WAL sidecar file stays the caller's business, as for fsgpu_index_wal_append.
+ * Failure: the new slab is allocated before anything is touched; if that, the copy or the file write fails, the error is returned and
+ * the index is exactly as it was (slab, bitmap, tables, WAL, generations).
+ * Quiescence: NO search may be in flight on the handle.  The calls take the index's lock and every lane's, and are refused with
+ * FSGPU_ERR_INVALID_CONFIG while a ticket of fsgpu_search_topk_batched_device_begin is outstanding.  Row-sharded handles
+ * (fsgpu_sharded_compact / _vacuum) always answer FSGPU_ERR_INVALID_CONFIG: their rows would have to be re-sharded.
+ * After a call that changed the slab (fsgpu_index_generation moved) every row id means another row, so
+ *   - the library drops what IT derived: the int8 / rotated int8 / 4-bit copies, the measured slab statistics, the MRL views, the
+ *     lanes of concurrent callers, the certificate back-off; with FSGPU_INT8_LATENCY_BUILD_NOW in force the copies are rebuilt before
+ *     the call returns;
+ *   - an fsgpu_allow_bitmap made before is refused (FSGPU_ERR_INVALID_CONFIG): make a new one;
+ *   - the CALLER rebuilds what it derived: alignments (fsgpu_alignment_create), hubness tables (fsgpu_index_compute_query_hubness),
+ *     allow bitmaps from fsgpu_index_allow_bitmap_for_hashes, and any fshost_two_tier searcher built over the index (libfshost does
+ *     not follow a compaction);
+ *   - doc-id pointers handed out by fsgpu_index_doc_id before the call are invalid. */
+typedef struct fsgpu_compaction_stats { /* wal::CompactionStats (wal.rs:111) */
+    uint64_t main_records_before, wal_records, total_records_after;
+    double elapsed_ms;
+} fsgpu_compaction_stats;
+typedef struct fsgpu_vacuum_stats { /* VacuumStats (lib.rs:726); duration as milliseconds */
+    uint64_t records_before, records_after, tombstones_removed, bytes_reclaimed;
+    double elapsed_ms;
+} fsgpu_vacuum_stats;
+/* VectorIndex::compact (lib.rs:2734-2854).  Empty WAL: a no-op that reports {main_before, 0, main_before} — tombstones STAY.  Else the
+ * sources are every live main row in row order, then every resident WAL entry in order, stably sorted by (doc_id_hash, doc id bytes);
+ * adjacent equal keys collapse to the last (WAL beats main; of two live main duplicates the higher row wins).  Main rows are copied
+ * byte for byte (NaN payloads and -0.0 survive); WAL rows are encoded f32 -> f16 round-to-nearest-even on an F16 slab and stored as raw
+ * little-endian f32 on an F32 slab.  The WAL is emptied; compaction_gen becomes next_generation (255 -> 1, else +1, lib.rs:6156); the
+ * publication nonce, embedder id and revision, dimension and quantization are kept.  Needs a doc-id table (FSVI-opened indexes),
+ * else FSGPU_ERR_INVALID_CONFIG.  out may be NULL. */
+fsgpu_status fsgpu_index_compact(fsgpu_index *idx, const char *path_or_null, fsgpu_compaction_stats *out);
+/* VectorIndex::vacuum (lib.rs:2485-2521).  No rows or no tombstones: a no-op.  Else the live main rows in order, no dedup; the WAL
+ * stays resident; compaction_gen is unchanged.  bytes_reclaimed: for an FSVI-opened index the difference of the two FSVI image
+ * lengths (layout formula), otherwise the difference in slab bytes.  Works on ANY index (no doc ids needed unless a path is given).
+ * On an adopted device slab (fsgpu_index_create_device) the new slab is owned by the library: the caller's slab and live-bitmap
+ * buffers are no longer referenced after a vacuum that removed rows and may be freed. */
+fsgpu_status fsgpu_index_vacuum(fsgpu_index *idx, const char *path_or_null, fsgpu_vacuum_stats *out);
+/* VectorIndex::needs_compaction (lib.rs:2270-2292) with WalConfig's compaction_threshold and compaction_ratio as arguments (the
+ * handle keeps no WalConfig; the reference's defaults are 1000 and 0.10): WAL non-empty and (entries >= threshold or, with main
+ * rows, entries / record_count >= ratio).  A non-finite ratio means 0.10. */
+fsgpu_status fsgpu_index_needs_compaction(fsgpu_index *idx, uint64_t threshold, double ratio, int32_t *out);
+/* VectorIndex::needs_vacuum (lib.rs:174, 2464-2475): tombstone_count / record_count > 0.20, strictly. */
+fsgpu_status fsgpu_index_needs_vacuum(fsgpu_index *idx, int32_t *out);
+uint64_t fsgpu_index_tombstone_count(fsgpu_index *idx); /* VectorIndex::tombstone_count: main rows whose live bit is clear */
+uint64_t fsgpu_index_live_count(fsgpu_index *idx);      /* record_count - tombstone_count */
+/* Rewrites that changed the slab since the handle was made: starts at 0, +1 per compact / vacuum that was not a no-op. */
+uint64_t fsgpu_index_generation(const fsgpu_index *idx);
+/* IndexMetadata::compaction_gen (lib.rs:5714-5768): the file header's generation byte, as compact last left it. */
+uint32_t fsgpu_index_compaction_gen(const fsgpu_index *idx);
 /* Replace the live bitmap (host words, ceil(nrows/64)); NULL = all live. */
 fsgpu_status fsgpu_index_set_live_bitmap(fsgpu_index *idx, const uint64_t *live_bitmap);
 
@@ -456,6 +517,9 @@ fsgpu_status fsgpu_sharded_set_live_bitmap(fsgpu_sharded *idx, const uint64_t *l
 fsgpu_status fsgpu_sharded_soft_delete(fsgpu_sharded *idx, const char *doc_id, uint32_t doc_id_len, int32_t *out_deleted);
 fsgpu_status fsgpu_sharded_wal_append(fsgpu_sharded *idx, const char *doc_id, uint32_t doc_id_len, const float *vector,
                                       uint32_t vector_len);
+/* VectorIndex::compact / vacuum under a row-sharded handle: always FSGPU_ERR_INVALID_CONFIG (re-sharding is not built). */
+fsgpu_status fsgpu_sharded_compact(fsgpu_sharded *idx, const char *path_or_null, fsgpu_compaction_stats *out);
+fsgpu_status fsgpu_sharded_vacuum(fsgpu_sharded *idx, const char *path_or_null, fsgpu_vacuum_stats *out);
 uint64_t fsgpu_sharded_wal_record_count(const fsgpu_sharded *idx);
 fsgpu_status fsgpu_sharded_doc_id(const fsgpu_sharded *idx, uint32_t row, const char **out_ptr, uint32_t *out_len);
 fsgpu_status fsgpu_sharded_search_hits(fsgpu_sharded *idx, const float *query, uint32_t query_len, uint32_t k, uint32_t *out_rows,

@@ -49,6 +49,20 @@ fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float *x, const
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
                                                 float *out, float *out_topk);
+/* ---- compaction (fsgpu_index_compact / _vacuum) ---- */
+/* Destination rows one launch of the segmented-copy kernel covers (0 = the default, 2^20): lets a test cross launch boundaries with a
+ * few thousand rows. */
+fsgpu_status fsgpu_lab_index_set_compact_launch_rows(fsgpu_index *idx, uint32_t rows);
+/* The kernel's stores with (1) / without (0, default) the non-temporal hint: the A/B of DESIGN 3.12. */
+fsgpu_status fsgpu_lab_index_set_compact_nt_stores(fsgpu_index *idx, int32_t enabled);
+/* What the last rewrite cost: out_ms5 = plan (merge, runs, upload, WAL encode), kernel launches until done, table rebuild, file,
+ * rebuild of derived copies; out_counts3 = runs, launches, destination bytes. */
+fsgpu_status fsgpu_lab_index_last_rewrite(fsgpu_index *idx, double *out_ms5, uint64_t *out_counts3);
+/* Gives an index made from a bare slab (fsgpu_index_create / _create_device) a doc-id table: the ids "doc-000000000", ... assigned so
+ * that the rows as they stand are in (hash, doc id) order.  For measurements of the write path on a generated corpus. */
+fsgpu_status fsgpu_lab_index_attach_synthetic_doc_ids(fsgpu_index *idx);
+/* The yardstick of the copy kernel: `reps` hipMemcpyDtoD of `bytes` between two fresh buffers, each timed by events (ms). */
+fsgpu_status fsgpu_lab_device_copy_ms(int32_t device, uint64_t bytes, uint32_t reps, double *out_ms);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
