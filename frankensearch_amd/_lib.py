@@ -147,6 +147,7 @@ SIGNATURES = {
     "fsgpu_bert_create_safetensors_ex": (_i32, [_i32, _vp, _u64, C.c_float, _vp, C.POINTER(_vp)]),
     "fsgpu_bert_linear_format": (_u32, [_vp]),
     "fsgpu_lab_linear_int8_dynamic": (_i32, [_i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
+    "fsgpu_lab_bert_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_stage_args: BertStageArgs below)
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
@@ -210,6 +211,15 @@ SIGNATURES = {
     "fsgpu_index_filter_stats": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "fsgpu_index_set_variant": (_i32, [_vp, _i32]),
 }
+
+
+
+class BertStageArgs(C.Structure):
+    """fsgpu_lab_bert_stage_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("stage", "form", "epilogue", "m", "n", "k", "hidden", "inter", "n_docs", "vocab", "max_pos")] + [
+        ("eps", C.c_float), ("scale", C.c_float), ("offsets", _vp), ("ids", _vp), ("positions", _vp), ("types", _vp),
+        ("in_", _vp * 12), ("out0", _vp), ("out1", _vp)]
+
 
 _lib = None
 

@@ -3,6 +3,7 @@
 #include "../../include/fsgpu.h"
 #include "../../include/fsgpu_lab.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -1830,6 +1831,271 @@ fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float* x, const
         for (fsgpu::DeviceBuffer* b : {&dx, &dw, &db, &dy, &qx, &sx, &wp, &sw}) b->release();
         if (!e.ok()) return finish(e);
         if (he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(he));
+        return FSGPU_OK;
+    });
+}
+
+namespace {
+// Device side of fsgpu_lab_bert_stage: uploads (as f32, as f16 through launch_bert_to_half, as fragment-order f16 through
+// launch_bert_pack_w) and outputs that sit between two guard bands of 64 rows.  The first failure sticks; every later step is skipped.
+struct LabStage {
+    static constexpr size_t kGuardRows = 64;
+    static constexpr int kGuardByte = 0xA5;
+    struct Out {
+        unsigned char* base = nullptr;
+        size_t rows = 0, cols = 0, elem = 0;
+        float* host = nullptr;
+        void* ptr() const { return base + kGuardRows * cols * elem; }
+    };
+    std::vector<fsgpu::DeviceBuffer> bufs;
+    std::vector<Out> outs;
+    fsgpu::SearchError e;
+    hipError_t he = hipSuccess;
+    bool guard_hit = false;
+
+    LabStage() { bufs.reserve(64); }
+    ~LabStage() {
+        for (fsgpu::DeviceBuffer& b : bufs) b.release();
+    }
+    bool ok() const { return e.ok() && he == hipSuccess; }
+    void hip(hipError_t r) {
+        if (ok()) he = r;
+    }
+    void* alloc(size_t bytes) {
+        if (!ok()) return nullptr;
+        bufs.emplace_back();
+        e = bufs.back().reserve(bytes ? bytes : 16);
+        return e.ok() ? bufs.back().ptr : nullptr;
+    }
+    void* raw(const void* src, size_t bytes) {
+        void* d = alloc(bytes);
+        if (ok()) he = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+        return d;
+    }
+    const float* f32(const float* src, size_t n) { return static_cast<const float*>(raw(src, n * 4)); }
+    void* f16(const float* src, size_t n) {
+        const float* s = f32(src, n);
+        void* d = alloc(n * 2);
+        if (ok()) he = fsgpu::launch_bert_to_half(s, d, n, nullptr);
+        return d;
+    }
+    void* packed(const float* w, int N, int K) {
+        void* h = f16(w, (size_t)N * K);
+        void* d = alloc((size_t)N * K * 2);
+        if (ok()) he = fsgpu::launch_bert_pack_w(h, d, N, K, nullptr);
+        return d;
+    }
+    // an output of rows x cols elements of elem bytes (2: f16, 4: f32) for the caller's `host`; init: f32 rows the kernel updates in place
+    void* out(size_t rows, size_t cols, size_t elem, float* host, const float* init = nullptr) {
+        Out o;
+        o.rows = rows, o.cols = cols, o.elem = elem, o.host = host;
+        const size_t bytes = (rows + 2 * kGuardRows) * cols * elem;
+        o.base = static_cast<unsigned char*>(alloc(bytes));
+        if (ok()) he = hipMemset(o.base, kGuardByte, bytes);
+        if (ok() && init) he = hipMemcpy(o.ptr(), init, rows * cols * elem, hipMemcpyHostToDevice);
+        outs.push_back(o);
+        return ok() ? o.ptr() : nullptr;
+    }
+    void collect() {
+        hip(hipStreamSynchronize(nullptr));
+        for (const Out& o : outs) {
+            if (!ok()) return;
+            const size_t band = kGuardRows * o.cols * o.elem, body = o.rows * o.cols * o.elem;
+            std::vector<unsigned char> h(body + 2 * band);
+            he = hipMemcpy(h.data(), o.base, h.size(), hipMemcpyDeviceToHost);
+            if (!ok()) return;
+            for (size_t i = 0; i < band; ++i)
+                if (h[i] != kGuardByte || h[band + body + i] != kGuardByte) guard_hit = true;
+            if (o.elem == 4) {
+                std::memcpy(o.host, h.data() + band, body);
+            } else {
+                const _Float16* s = reinterpret_cast<const _Float16*>(h.data() + band);
+                for (size_t i = 0; i < o.rows * o.cols; ++i) o.host[i] = (float)s[i];
+            }
+        }
+    }
+};
+
+// offsets [n_docs + 1] from 0 to m, non-decreasing; the longest document (embed_batch's max_seq)
+bool lab_offsets(const uint32_t* offsets, uint32_t n_docs, uint32_t m, uint32_t* max_seq, uint32_t* min_seq) {
+    if (!offsets || n_docs == 0 || n_docs > (1u << 20) || offsets[0] != 0 || offsets[n_docs] != m) return false;
+    *max_seq = 0;
+    *min_seq = ~0u;
+    for (uint32_t i = 0; i < n_docs; ++i) {
+        if (offsets[i + 1] < offsets[i]) return false;
+        const uint32_t len = offsets[i + 1] - offsets[i];
+        *max_seq = std::max(*max_seq, len);
+        *min_seq = std::min(*min_seq, len);
+    }
+    return true;
+}
+}  // namespace
+
+fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_bert_stage_args& a = *args;
+    const uint32_t st = a.stage, form = a.form;
+    const int M = (int)a.m, N = (int)a.n, K = (int)a.k, H = (int)a.hidden, I = (int)a.inter;
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    if (a.m == 0 || a.m > (1u << 20)) return bad("bert stage: m must be in 1..=2^20");
+    if (st > FSGPU_LAB_BERT_POOL || form > 2) return bad("bert stage: unknown stage or form");
+    static const int n_in[] = {1, 3, 6, 12, 5, 1};
+    const int need = n_in[st] + ((st == FSGPU_LAB_BERT_ATTENTION && form == 2) ? 1 : 0);
+    for (int i = 0; i < need; ++i)
+        if (!a.in[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: missing input");
+    if (!a.out0) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: out0 is null");
+    const bool two_outs = st == FSGPU_LAB_BERT_LINEAR_LN || st == FSGPU_LAB_BERT_POST_ATTN || st == FSGPU_LAB_BERT_EMBED_LN ||
+                          (st == FSGPU_LAB_BERT_ATTENTION && form == 2);
+    if (two_outs && !a.out1) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: out1 is null");
+    // the encoder's own shape rule (NativeEmbedder::init); the linear stage has no hidden
+    if (st != FSGPU_LAB_BERT_LINEAR && (H <= 0 || H % 128 != 0 || H > 1024)) return bad("bert stage: hidden must be a multiple of 128 and <= 1024");
+    uint32_t max_seq = 0, min_seq = 0;
+    switch (st) {
+        case FSGPU_LAB_BERT_ATTENTION:
+            if (!lab_offsets(a.offsets, a.n_docs, a.m, &max_seq, &min_seq) || max_seq > 512) return bad("bert stage: offsets must run from 0 to m in documents of at most 512 tokens");
+            if (form == 2 && (min_seq == 0 || !fsgpu::bert_rerank_supported(H))) return bad("bert stage: the [CLS] attention takes no empty document");
+            break;
+        case FSGPU_LAB_BERT_LINEAR:
+            if (N <= 0 || N > (1 << 20) || K <= 0 || K > (1 << 20)) return bad("bert stage: n and k must be in 1..=2^20");
+            if (form == 0 ? (K % 32 != 0 || N % 64 != 0 || a.epilogue > 1) : (!fsgpu::bert_gemm_w_supported(N, K) || a.epilogue > 2))
+                return bad("bert stage: linear shape or epilogue not supported by this form");
+            break;
+        case FSGPU_LAB_BERT_LINEAR_LN:
+            if (K <= 0 || K > (1 << 20) || K % 32 != 0) return bad("bert stage: k must be a multiple of 32");
+            if ((form == 0 && !fsgpu::bert_gemm_ln_supported(H)) || (form == 1 && !fsgpu::bert_gemm_ln_w_supported(H, K)))
+                return bad("bert stage: linear + LayerNorm shape not supported by this form");
+            break;
+        case FSGPU_LAB_BERT_POST_ATTN:
+            if (I <= 0 || I > (1 << 20)) return bad("bert stage: inter must be in 1..=2^20");
+            if (form == 2 ? !(fsgpu::bert_gemm_ln_w_supported(H, H) && fsgpu::bert_ffn_w_supported(H, I)) : !fsgpu::bert_post_attn_w_supported(H, I))
+                return bad("bert stage: post-attention shape not supported by this form");
+            break;
+        case FSGPU_LAB_BERT_EMBED_LN:
+            if (form > 1 || a.vocab == 0 || a.max_pos == 0 || !a.ids || !a.positions || (form == 1 && (!a.types || !fsgpu::bert_rerank_supported(H))))
+                return bad("bert stage: embedding needs ids, positions (and types), vocab and max_pos");
+            for (uint32_t t = 0; t < a.m; ++t)
+                if (a.ids[t] < 0 || (uint32_t)a.ids[t] >= a.vocab || a.positions[t] < 0 || (uint32_t)a.positions[t] >= a.max_pos ||
+                    (form == 1 && (a.types[t] < 0 || a.types[t] > 1)))
+                    return bad("bert stage: token id, position or type out of range");
+            break;
+        default:
+            if (!lab_offsets(a.offsets, a.n_docs, a.m, &max_seq, &min_seq)) return bad("bert stage: offsets must run from 0 to m");
+            break;
+    }
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        const size_t m = a.m, h = a.hidden;
+        if (st == FSGPU_LAB_BERT_ATTENTION) {
+            const uint32_t* offs = static_cast<const uint32_t*>(s.raw(a.offsets, ((size_t)a.n_docs + 1) * 4));
+            const int heads = H / 32;
+            if (form == 1) {
+                const float* qkv = s.f32(a.in[0], m * 3 * h);
+                void* ctx = s.out(m, h, 2, a.out0);
+                if (s.ok()) s.hip(fsgpu::launch_bert_attention(qkv, offs, ctx, (int)a.n_docs, heads, H, (int)max_seq, a.scale, nullptr));
+            } else if (form == 0) {
+                const void* qkv = s.f16(a.in[0], m * 3 * h);
+                void* ctx = s.out(m, h, 2, a.out0);
+                if (s.ok()) s.hip(fsgpu::launch_bert_attention_h(qkv, offs, ctx, (int)a.n_docs, heads, H, (int)max_seq, a.scale, nullptr));
+            } else {
+                const void* qkv = s.f16(a.in[0], m * 3 * h);
+                const float* x = s.f32(a.in[1], m * h);
+                void* ctx = s.out(a.n_docs, h, 2, a.out0);
+                float* x_cls = static_cast<float*>(s.out(a.n_docs, h, 4, a.out1));
+                if (s.ok()) s.hip(fsgpu::launch_bert_cls_attention(qkv, offs, x, ctx, x_cls, (int)a.n_docs, heads, H, a.scale, nullptr));
+            }
+        } else if (st == FSGPU_LAB_BERT_LINEAR) {
+            const void* act = s.f16(a.in[0], m * a.k);
+            const void* w = form == 0 ? s.f16(a.in[1], (size_t)a.n * a.k) : s.packed(a.in[1], N, K);
+            const float* bias = s.f32(a.in[2], a.n);
+            const bool half_out = a.epilogue != 0;
+            void* y = s.out(m, a.n, half_out ? 2 : 4, a.out0);
+            float* y32 = half_out ? nullptr : static_cast<float*>(y);
+            void* y16 = half_out ? y : nullptr;
+            if (!s.ok()) {
+                // (an upload failed: nothing is launched)
+            } else if (form == 0) {
+                s.hip(fsgpu::launch_bert_gemm(act, w, bias, y32, y16, M, N, K, a.epilogue == 1, nullptr));
+            } else if (form == 1) {
+                s.hip(fsgpu::launch_bert_gemm_w(act, w, bias, y32, y16, M, N, K, (int)a.epilogue, nullptr));
+            } else {
+                s.hip(fsgpu::launch_bert_gemm_w_fixed(act, w, bias, y32, y16, M, N, K, (int)a.epilogue, nullptr));
+            }
+        } else if (st == FSGPU_LAB_BERT_LINEAR_LN) {
+            const void* act = s.f16(a.in[0], m * a.k);
+            const void* w = form == 1 ? s.packed(a.in[1], H, K) : s.f16(a.in[1], h * a.k);
+            const float* bias = s.f32(a.in[2], h);
+            const float* lnw = s.f32(a.in[4], h);
+            const float* lnb = s.f32(a.in[5], h);
+            float* x = static_cast<float*>(s.out(m, h, 4, a.out0, a.in[3]));
+            void* x_h = s.out(m, h, 2, a.out1);
+            if (!s.ok()) {
+                // (an upload failed: nothing is launched)
+            } else if (form == 0) {
+                s.hip(fsgpu::launch_bert_gemm_ln(act, w, bias, x, x_h, lnw, lnb, M, H, K, a.eps, nullptr));
+            } else if (form == 1) {
+                s.hip(fsgpu::launch_bert_gemm_ln_w(act, w, bias, x, x_h, lnw, lnb, M, H, K, a.eps, nullptr));
+            } else {
+                float* tmp = static_cast<float*>(s.alloc(m * h * 4));
+                if (s.ok()) s.hip(fsgpu::launch_bert_gemm(act, w, bias, tmp, nullptr, M, H, K, false, nullptr));
+                if (s.ok()) s.hip(fsgpu::launch_bert_add_ln(x, tmp, lnw, lnb, x_h, M, H, a.eps, nullptr));
+            }
+        } else if (st == FSGPU_LAB_BERT_POST_ATTN) {
+            const size_t in = a.inter;
+            const void* ctx = s.f16(a.in[0], m * h);
+            const void* w0 = s.packed(a.in[1], H, H);
+            const float* b0 = s.f32(a.in[2], h);
+            const float* ln0w = s.f32(a.in[3], h);
+            const float* ln0b = s.f32(a.in[4], h);
+            const void* w1 = s.packed(a.in[5], I, H);
+            const float* b1 = s.f32(a.in[6], in);
+            const void* w2 = s.packed(a.in[7], H, I);
+            const float* b2 = s.f32(a.in[8], h);
+            const float* lnw = s.f32(a.in[9], h);
+            const float* lnb = s.f32(a.in[10], h);
+            float* x = static_cast<float*>(s.out(m, h, 4, a.out0, a.in[11]));
+            void* x_h = s.out(m, h, 2, a.out1);
+            if (!s.ok()) {
+                // (an upload failed: nothing is launched)
+            } else if (form == 0) {
+                s.hip(fsgpu::launch_bert_post_attn_w(ctx, w0, b0, ln0w, ln0b, w1, b1, w2, b2, x, x_h, lnw, lnb, M, H, I, a.eps, nullptr));
+            } else if (form == 1) {
+                s.hip(fsgpu::launch_bert_post_attn_w_fixed(ctx, w0, b0, ln0w, ln0b, w1, b1, w2, b2, x, x_h, lnw, lnb, M, H, I, a.eps, nullptr));
+            } else {
+                s.hip(fsgpu::launch_bert_gemm_ln_w(ctx, w0, b0, x, x_h, ln0w, ln0b, M, H, H, a.eps, nullptr));
+                if (s.ok()) s.hip(fsgpu::launch_bert_ffn_w(w1, b1, w2, b2, x, x_h, lnw, lnb, M, H, I, a.eps, nullptr));
+            }
+        } else if (st == FSGPU_LAB_BERT_EMBED_LN) {
+            const int32_t* ids = static_cast<const int32_t*>(s.raw(a.ids, m * 4));
+            const int32_t* positions = static_cast<const int32_t*>(s.raw(a.positions, m * 4));
+            const int32_t* types = form == 1 ? static_cast<const int32_t*>(s.raw(a.types, m * 4)) : nullptr;
+            const float* word = s.f32(a.in[0], (size_t)a.vocab * h);
+            const float* pos = s.f32(a.in[1], (size_t)a.max_pos * h);
+            const float* type = s.f32(a.in[2], (form == 1 ? 2 : 1) * h);
+            const float* lnw = s.f32(a.in[3], h);
+            const float* lnb = s.f32(a.in[4], h);
+            float* x = static_cast<float*>(s.out(m, h, 4, a.out0));
+            void* x_h = s.out(m, h, 2, a.out1);
+            if (!s.ok()) {
+                // (an upload failed: nothing is launched)
+            } else if (form == 0) {
+                s.hip(fsgpu::launch_bert_embed_ln(ids, positions, word, pos, type, lnw, lnb, x, x_h, M, H, a.eps, nullptr));
+            } else {
+                s.hip(fsgpu::launch_bert_embed_typed_ln(ids, types, positions, word, pos, type, lnw, lnb, x, x_h, M, H, a.eps, nullptr));
+            }
+        } else {
+            const uint32_t* offs = static_cast<const uint32_t*>(s.raw(a.offsets, ((size_t)a.n_docs + 1) * 4));
+            const float* x = s.f32(a.in[0], m * h);
+            float* pooled = static_cast<float*>(s.out(a.n_docs, h, 4, a.out0));
+            if (s.ok()) s.hip(fsgpu::launch_bert_pool(x, offs, pooled, (int)a.n_docs, H, nullptr));
+        }
+        s.collect();
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (s.guard_hit) return fail(FSGPU_ERR_DEVICE, "bert stage: a kernel wrote into a guard band of its output");
         return FSGPU_OK;
     });
 }

@@ -45,6 +45,42 @@ fsgpu_status fsgpu_lab_sort_keys_desc(int32_t device, const uint64_t *keys, uint
  * K and N must be multiples of 64 (else FSGPU_ERR_INVALID_CONFIG). */
 fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float *x, const float *w, const float *bias, uint32_t m, uint32_t n,
                                            uint32_t k, float *y);
+/* ONE stage of the f16 encoder (or of the cross-encoder built on it) on host arrays, through the launch_bert_* function the product
+ * calls, so that the kernel a shape selects is the product's choice: for kernel-level tests against a high-precision reference
+ * (tests/encoder_stage_ref.py).  f32 host inputs the product holds as f16 (activations `a`, contexts, Q/K/V of the f16 attention,
+ * weight matrices) are rounded on the device (RNE) and weights of the packed forms re-laid in fragment order, as at model load; f16
+ * outputs come back widened to f32.  max_seq is derived from `offsets` as embed_batch does.  A shape a launcher's own *_supported
+ * predicate refuses is FSGPU_ERR_INVALID_CONFIG and nothing is launched.  Every output buffer lies between two guard bands of 64
+ * rows of a fixed pattern: FSGPU_ERR_DEVICE ("guard band") if a kernel wrote into one.  in[] / out0 / out1 by stage and form:
+ *   ATTENTION   in: qkv [m, 3 hidden] (Q | K | V), form 2 also x [m, hidden]; offsets [n_docs + 1] (documents of <= 512 tokens);
+ *               forms 0 launch_bert_attention_h, 1 launch_bert_attention: out0 = ctx [m, hidden];
+ *               form 2 launch_bert_cls_attention (no empty document): out0 = ctx_cls [n_docs, hidden], out1 = x_cls [n_docs, hidden]
+ *   LINEAR      in: a [m, k], w [n, k], bias [n]; out0 = y [m, n].  form 0 launch_bert_gemm (epilogue 0 f32, 1 GELU f16),
+ *               1 launch_bert_gemm_w, 2 launch_bert_gemm_w_fixed (epilogue 0 f32, 1 GELU f16, 2 f16)
+ *   LINEAR_LN   x = LayerNorm(x + a w^T + bias): in: a [m, k], w [hidden, k], bias, x [m, hidden], ln_w, ln_b; out0 = x (f32), out1 = its
+ *               f16 copy.  form 0 launch_bert_gemm_ln, 1 launch_bert_gemm_ln_w, 2 launch_bert_gemm then launch_bert_add_ln
+ *   POST_ATTN   everything of a layer after the attention: in: ctx [m, hidden], w0 [hidden, hidden], b0, ln0_w, ln0_b, w1 [inter, hidden],
+ *               b1, w2 [hidden, inter], b2, ln_w, ln_b, x [m, hidden]; out0 / out1 as LINEAR_LN.  form 0 launch_bert_post_attn_w,
+ *               1 launch_bert_post_attn_w_fixed, 2 launch_bert_gemm_ln_w then launch_bert_ffn_w
+ *   EMBED_LN    in: word [vocab, hidden], pos [max_pos, hidden], type [1 | 2, hidden], ln_w, ln_b; ids, positions (, types) [m];
+ *               form 0 launch_bert_embed_ln, 1 launch_bert_embed_typed_ln; out0 / out1 as LINEAR_LN
+ *   POOL        in: x [m, hidden]; offsets; launch_bert_pool: out0 = [n_docs, hidden] */
+#define FSGPU_LAB_BERT_ATTENTION 0
+#define FSGPU_LAB_BERT_LINEAR 1
+#define FSGPU_LAB_BERT_LINEAR_LN 2
+#define FSGPU_LAB_BERT_POST_ATTN 3
+#define FSGPU_LAB_BERT_EMBED_LN 4
+#define FSGPU_LAB_BERT_POOL 5
+typedef struct fsgpu_lab_bert_stage_args {
+    uint32_t stage, form, epilogue;
+    uint32_t m, n, k, hidden, inter, n_docs, vocab, max_pos;
+    float eps, scale;
+    const uint32_t *offsets;
+    const int32_t *ids, *positions, *types;
+    const float *in[12];
+    float *out0, *out1;
+} fsgpu_lab_bert_stage_args;
+fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_args *args);
 /* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,

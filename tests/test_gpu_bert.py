@@ -108,6 +108,25 @@ def test_batch_path_other_widths(fa, hidden, inter, layers):
         assert float(np.sum(m.embed_token_ids(batch[i]) * got[i])) > 0.9999
 
 
+@pytest.mark.parametrize("hidden,inter,layers", [(256, 768, 2), (384, 1024, 2), (128, 256, 2), (768, 3072, 2), (1024, 4096, 1), (384, 2048, 2)])
+def test_shapes_that_leave_the_fused_post_attention_block(fa, hidden, inter, layers):
+    """Shapes init() accepts that take other launchers than the usual ones: an intermediate tile too small to lend its LDS to the
+    output projection (256/768, 384/1024, 128/256: bert_gemm_ln_w + bert_ffn_w, chunks of two and of three tiles), hidden > 384
+    (unpacked: bert_gemm / bert_gemm_lds, bert_add_ln, the generic embedding kernel, the f32-operand attention, pooling with 64 KB of
+    LDS at 1024) and 384/2048 (unpacked with bert_gemm_ln).  A ragged batch with a 300-token document, and a short text alone."""
+    from oracle import bert_oracle
+    rng = np.random.default_rng(hidden + inter)
+    w = bert_oracle.random_weights(33, 3000, hidden, layers, inter)
+    m = fa.NativeEmbedder(w)
+    ref = bert_oracle.CForward(w, layers)
+    lens = [300, 1, 17, 64, 33, 0, 5]
+    batch = [[101] + rng.integers(1000, 3000, n - 1).tolist() if n else [] for n in lens]
+    assert sum(lens) > 256 and sum(lens) % 32 != 0
+    check(m.embed_batch_token_ids(batch), ref.run(batch, 8))
+    check(m.embed_token_ids(batch[2])[None, :], ref.run([batch[2]], 1))
+    m.close()
+
+
 def test_large_batch_equals_its_parts(fa):
     """A call too large for the pinned staging block and the graph cache (130 x 512 tokens: pageable H2D / D2H, eager
     launches) returns, text for text, the bits of the same texts embedded 26 at a time: every row's arithmetic is independent
