@@ -180,6 +180,11 @@ SIGNATURES = {
     "fsgpu_index_compute_query_hubness": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_sharded_compute_query_hubness": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_lab_index_query_hubness_topk": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "fsgpu_index_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
+    "fsgpu_sharded_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
+    "fsgpu_lab_index_knn_build_stats": (_i32, [_vp, _vp]),
+    "fsgpu_smooth_config_default": (_i32, [_vp]),
+    "fsgpu_neighbor_smooth": (_i32, [_vp, _u32, _vp, _u64, _u32, _vp, _i32, C.POINTER(C.c_uint8)]),
     "fsgpu_rrf_fuse": (_i32, [_vp, _u32, _vp, _u32, C.c_double, C.c_double, C.c_double, _i32, _u32, _u32, _vp,
                               C.POINTER(_u32)]),
     "fsgpu_blend_two_tier": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32)]),

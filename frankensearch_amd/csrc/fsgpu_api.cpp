@@ -1489,6 +1489,44 @@ fsgpu_status fsgpu_sharded_compute_query_hubness(fsgpu_sharded* sh, const float*
     });
 }
 
+// the k-NN graph: errors are reported before any work starts — m, then the device, then the handle and its range
+fsgpu_status fsgpu_index_build_knn_graph(fsgpu_index* idx, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows,
+                                         float* out_sims) {
+    if (m < 1 || m > fsgpu::kKnnMaxM) return fail(FSGPU_ERR_INVALID_CONFIG, "m must be 1 .. 63 (k = m + 1 stays inside the fused tiers)");
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        const uint64_t n = idx->impl.record_count();
+        if (first_row > n || n_rows > n - first_row) return fail(FSGPU_ERR_INVALID_CONFIG, "the source rows lie past record_count");
+        if (n_rows && !out_rows) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_rows is null");
+        return finish(idx->impl.build_knn_graph(first_row, n_rows, m, out_rows, out_sims));
+    });
+}
+
+fsgpu_status fsgpu_lab_index_knn_build_stats(fsgpu_index* idx, uint64_t* out4) {
+    if (!idx || !out4) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    const fsgpu::VectorIndex::KnnBuildStats& st = idx->impl.last_knn_build;
+    out4[0] = st.steps, out4[1] = st.sources, out4[2] = st.fallbacks, out4[3] = st.late_answers;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded* sh, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows,
+                                           float* out_sims) {
+    if (m < 1 || m > fsgpu::kKnnMaxM) return fail(FSGPU_ERR_INVALID_CONFIG, "m must be 1 .. 63 (k = m + 1 stays inside the fused tiers)");
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!sh) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(sh->impl.mutex());
+        const uint64_t n = sh->impl.record_count();
+        if (first_row > n || n_rows > n - first_row) return fail(FSGPU_ERR_INVALID_CONFIG, "the source rows lie past record_count");
+        if (n_rows && !out_rows) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_rows is null");
+        return finish(sh->impl.build_knn_graph(first_row, n_rows, m, out_rows, out_sims));
+    });
+}
+
 // The same pairing over two row-sharded handles: the walk runs over their catalogs (fsgpu_sharded_open_fsvi) — raw shards pair by
 // row —, the re-scoring gathers dot_query_at on the shards that own the quality rows (fsgpu_sharded_gather_dot).
 fsgpu_status fsgpu_sharded_alignment_create(fsgpu_sharded* fast, fsgpu_sharded* quality, fsgpu_alignment** out) {

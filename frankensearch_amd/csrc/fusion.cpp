@@ -673,3 +673,79 @@ extern "C" fsgpu_status fsgpu_apply_hubness_penalty(fsgpu_scored_doc* hits, uint
     if (out_applied) *out_applied = 1;
     return FSGPU_OK;
 }
+
+// ---- k-NN graph diffusion: neighbor_smooth / neighbor_smooth_ranked (crates/frankensearch-fusion/src/smooth.rs:84-153, 176-276) ----
+// The reference keys the pool and the graph by doc-id string; here both are keyed by ROW (hits[i].index, the table of
+// fsgpu_index_build_knn_graph): include/fsgpu.h states the deviation.
+
+extern "C" fsgpu_status fsgpu_smooth_config_default(fsgpu_smooth_config* config) {
+    if (!config) return FSGPU_ERR_NULL_ARGUMENT;
+    std::memset(config, 0, sizeof(*config));
+    config->alpha = 0.3f;   // SmoothConfig::default (smooth.rs:53-61)
+    config->m = 10;
+    config->mutual = 0;
+    return FSGPU_OK;
+}
+
+extern "C" fsgpu_status fsgpu_neighbor_smooth(fsgpu_scored_doc* hits, uint32_t n, const uint32_t* graph_rows, uint64_t graph_len,
+                                              uint32_t graph_width, const fsgpu_smooth_config* config, int32_t resort, uint8_t* out_applied) {
+    if (out_applied) *out_applied = 0;
+    if (n && !hits) return FSGPU_ERR_NULL_ARGUMENT;
+    fsgpu_smooth_config cfg;
+    fsgpu_smooth_config_default(&cfg);
+    if (config) {
+        for (uint32_t r : config->reserved)
+            if (r != 0) return FSGPU_ERR_INVALID_CONFIG;
+        cfg = *config;
+    }
+    // SmoothConfig::is_identity, an empty graph, an empty pool (smooth.rs:66-68, 89-91, 270-272): nothing is touched, nothing is sorted
+    if (!std::isfinite(cfg.alpha) || cfg.alpha <= 0.0f || cfg.m == 0) return FSGPU_OK;
+    if (!graph_rows || graph_len == 0 || graph_width == 0 || n == 0) return FSGPU_OK;
+    try {
+        // row -> score; a row that occurs twice counts with its last occurrence (the AHashMap insert of smooth.rs:101, 186-189)
+        std::unordered_map<uint32_t, float> pool;
+        pool.reserve((size_t)n * 2);
+        for (uint32_t i = 0; i < n; ++i) pool[hits[i].index] = hits[i].score;
+        const uint32_t walk = std::min(cfg.m, graph_width);
+        const float alpha = cfg.alpha, keep = 1.0f - alpha;
+        std::vector<float> smoothed(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t row = hits[i].index;
+            float sum = 0.0f;
+            uint32_t count = 0;
+            if (row < graph_len) {   // (beyond the table: a WAL virtual row or 0xffffffff — no edges, nobody's neighbour)
+                const uint32_t* list = graph_rows + (uint64_t)row * graph_width;
+                for (uint32_t e = 0; e < walk; ++e) {   // every walked entry counts as examined, in the pool or not
+                    const uint32_t nb = list[e];
+                    if (nb == 0xffffffffu) break;
+                    const auto it = pool.find(nb);
+                    if (it == pool.end()) continue;
+                    if (cfg.mutual) {   // reciprocity over the neighbour's WHOLE stored list (the reference's set is uncapped)
+                        if (nb >= graph_len) continue;
+                        const uint32_t* back = graph_rows + (uint64_t)nb * graph_width;
+                        bool mutual = false;
+                        for (uint32_t x = 0; x < graph_width && !mutual; ++x) mutual = back[x] == row;
+                        if (!mutual) continue;
+                    }
+                    sum = sum + it->second;
+                    ++count;
+                }
+            }
+            const float mean = count == 0 ? hits[i].score : sum / (float)count;
+            const float a = keep * hits[i].score, b = alpha * mean;
+            smoothed[i] = a + b;
+        }
+        for (uint32_t i = 0; i < n; ++i) hits[i].score = smoothed[i];
+        if (resort)   // VectorHit::cmp_rank, as fsgpu_apply_hubness_penalty sorts
+            std::stable_sort(hits, hits + n, [](const fsgpu_scored_doc& a, const fsgpu_scored_doc& b) {
+                const float inf = std::numeric_limits<float>::infinity();
+                const int32_t x = total_key32(std::isnan(a.score) ? -inf : a.score), y = total_key32(std::isnan(b.score) ? -inf : b.score);
+                if (x != y) return x > y;
+                return sv(a) < sv(b);
+            });
+    } catch (...) {
+        return FSGPU_ERR_DEVICE;   // host allocation failed (the ABI's status for a resource failure)
+    }
+    if (out_applied) *out_applied = 1;
+    return FSGPU_OK;
+}

@@ -134,6 +134,17 @@ fsgpu_status fshost_two_tier_set_hubness(fshost_two_tier* s, const float* table,
     return FSGPU_OK;
 }
 
+fsgpu_status fshost_two_tier_set_neighbor_smoothing(fshost_two_tier* s, const uint32_t* graph_rows, uint64_t graph_len, uint32_t graph_width,
+                                                    float alpha, uint32_t m, int32_t mutual) {
+    if (!s) return FSGPU_ERR_NULL_ARGUMENT;
+    try {
+        s->impl.set_neighbor_smoothing(graph_rows, graph_len, graph_width, alpha, m, mutual != 0);
+    } catch (const std::exception&) {
+        return FSGPU_ERR_DEVICE;   // host allocation failed
+    }
+    return FSGPU_OK;
+}
+
 fsgpu_status fshost_two_tier_batching_stats(fshost_two_tier* s, uint64_t* chunks, uint64_t* requests) {
     if (!s || !chunks || !requests) return FSGPU_ERR_NULL_ARGUMENT;
     s->impl.batching_stats(chunks, requests);

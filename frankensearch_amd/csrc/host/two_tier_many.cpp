@@ -111,6 +111,7 @@ struct ManyEngine::Chunk {
     std::vector<uint8_t> qpresent;     // ... and whether a hit has one
     std::vector<uint8_t> q_refinement_failed;   // ... per query: its scores could not be produced
     HubnessSnapshot hubness;           // the table this chunk's searches started with: every stage and task corrects with it
+    SmoothSnapshot smooth;             // ... and the k-NN graph, likewise
     bool quality_failed = false;       // the quality pool failed: RefinementFailed for the chunk's queries
     std::string quality_detail;
     Batch* batch = nullptr;
@@ -409,7 +410,7 @@ void ManyEngine::rescore_stage() {
             fsgpu_status st = FSGPU_OK;
             for (uint32_t i = 0; i < n && st == FSGPU_OK; ++i) {
                 st = s_.hits_from_rows(s_.fast_, c->f_rows.data() + (size_t)i * fetch, c->f_scores.data() + (size_t)i * fetch, c->f_counts[i], &all[i], &detail);
-                if (st == FSGPU_OK) st = s_.correct_phase1_pool(c->hubness.get(), &all[i], &detail);   // the pool the fusion threads will rebuild: same order
+                if (st == FSGPU_OK) st = s_.correct_phase1_pool(c->hubness.get(), c->smooth.get(), &all[i], &detail);   // the pool the fusion threads will rebuild: same order
                 for (const Hit& h : all[i]) flat.push_back(fsgpu_scored_doc{h.doc_id.data(), (uint32_t)h.doc_id.size(), h.score, h.index});
                 offs.push_back((uint32_t)flat.size());
             }
@@ -483,7 +484,7 @@ void ManyEngine::fusion_worker() {
                 st = s_.hits_from_rows(s_.fast_, c->f_rows.data() + (size_t)i * fetch, c->f_scores.data() + (size_t)i * fetch, c->f_counts[i], &fast_hits, &detail);
             else
                 detail = c->detail;
-            if (st == FSGPU_OK) st = s_.correct_phase1_pool(c->hubness.get(), &fast_hits, &detail);   // hubness demotion, before the first RRF (searcher.rs:1869-1873)
+            if (st == FSGPU_OK) st = s_.correct_phase1_pool(c->hubness.get(), c->smooth.get(), &fast_hits, &detail);   // hubness demotion, before the first RRF (searcher.rs:1869-1873)
             if (st == FSGPU_OK && !t.final) {
                 st = s_.fuse_initial(fast_hits, k, q.lexical, q.n_lexical, &fused, &detail);
                 if (st == FSGPU_OK) emit(q.initial_out, q.n_initial);
@@ -578,6 +579,7 @@ fsgpu_status ManyEngine::run_many(const SyncTwoTierSearcher::ManyArgs& a, fshost
     batch.chunks_left = n_chunks;
     batch.t_start = clk::now();
     const HubnessSnapshot hubness = s_.hubness_snapshot();   // one table for the whole call
+    const SmoothSnapshot smooth = s_.smooth_snapshot();      // ... and one graph
     for (uint32_t ci = 0; ci < n_chunks; ++ci) {
         const uint32_t q0 = ci * C, q1 = std::min(nq, q0 + C);
         std::unique_ptr<Chunk> c(new Chunk);
@@ -587,6 +589,7 @@ fsgpu_status ManyEngine::run_many(const SyncTwoTierSearcher::ManyArgs& a, fshost
         c->index = ci;
         c->batch = &batch;
         c->hubness = hubness;
+        c->smooth = smooth;
         c->q.resize(c->n);
         c->fast_offs.resize(c->n + 1);
         c->quality_offs.resize(c->n + 1);
@@ -687,6 +690,7 @@ void ManyEngine::collector() {
         if (slot < 0) continue;   // (shutting down: the loop's head answers the parked requests)
         std::unique_ptr<Chunk> c(new Chunk);
         c->hubness = s_.hubness_snapshot();   // at admission: the chunk's callers all see this table, in both of their lists
+        c->smooth = s_.smooth_snapshot();
         {
             std::unique_lock<std::mutex> lk(rmu_);
             const uint32_t cap = std::max<uint32_t>(max_chunk_, 1);

@@ -171,19 +171,50 @@ void SyncTwoTierSearcher::set_hubness(const float* table, uint64_t table_len, fl
     std::atomic_store(&hubness_, next);
 }
 
-fsgpu_status SyncTwoTierSearcher::correct_phase1_pool(const HubnessTable* t, std::vector<Hit>* fast_hits, std::string* detail) const {
-    if (!t || fast_hits->empty()) return FSGPU_OK;
+void SyncTwoTierSearcher::set_neighbor_smoothing(const uint32_t* graph_rows, uint64_t graph_len, uint32_t graph_width, float alpha, uint32_t m,
+                                                 bool mutual) {
+    SmoothSnapshot next;
+    // SmoothConfig::is_identity (smooth.rs:66-68) or an empty graph: detached
+    if (graph_rows && graph_len > 0 && graph_width > 0 && std::isfinite(alpha) && alpha > 0.0f && m > 0) {
+        auto g = std::make_shared<SmoothGraph>();
+        g->rows.assign(graph_rows, graph_rows + graph_len * graph_width);
+        g->len = graph_len;
+        g->width = graph_width;
+        fsgpu_smooth_config_default(&g->cfg);
+        g->cfg.alpha = alpha;
+        g->cfg.m = m;
+        g->cfg.mutual = mutual ? 1u : 0u;
+        next = std::move(g);
+    }
+    std::atomic_store(&smooth_, next);
+}
+
+fsgpu_status SyncTwoTierSearcher::correct_phase1_pool(const HubnessTable* t, const SmoothGraph* g, std::vector<Hit>* fast_hits,
+                                                      std::string* detail) const {
+    if ((!t && !g) || fast_hits->empty()) return FSGPU_OK;
     std::vector<fsgpu_scored_doc> pool;
     pool.reserve(fast_hits->size());
     for (const Hit& h : *fast_hits) pool.push_back(fsgpu_scored_doc{h.doc_id.data(), (uint32_t)h.doc_id.size(), h.score, h.index});
-    fsgpu_hubness_config cfg;
-    fsgpu_hubness_config_default(&cfg);
-    cfg.beta = t->beta;
     uint8_t applied = 0;
-    const fsgpu_status st = fsgpu_apply_hubness_penalty(pool.data(), (uint32_t)pool.size(), t->r_d.data(), t->r_d.size(), &cfg, 1, &applied);
-    if (st != FSGPU_OK) {
-        *detail = "fsgpu_apply_hubness_penalty failed";
-        return st;
+    if (t) {
+        fsgpu_hubness_config cfg;
+        fsgpu_hubness_config_default(&cfg);
+        cfg.beta = t->beta;
+        // with a graph the penalty does not sort: smoothing's values do not depend on the order, and it sorts once at the end
+        const fsgpu_status st = fsgpu_apply_hubness_penalty(pool.data(), (uint32_t)pool.size(), t->r_d.data(), t->r_d.size(), &cfg, g ? 0 : 1, &applied);
+        if (st != FSGPU_OK) {
+            *detail = "fsgpu_apply_hubness_penalty failed";
+            return st;
+        }
+    }
+    if (g) {
+        uint8_t smoothed = 0;
+        const fsgpu_status st = fsgpu_neighbor_smooth(pool.data(), (uint32_t)pool.size(), g->rows.data(), g->len, g->width, &g->cfg, 1, &smoothed);
+        if (st != FSGPU_OK) {
+            *detail = "fsgpu_neighbor_smooth failed";
+            return st;
+        }
+        applied = applied || smoothed;
     }
     if (!applied) return FSGPU_OK;
     std::vector<Hit> corrected;
@@ -222,6 +253,7 @@ fsgpu_status SyncTwoTierSearcher::search_unbatched(const uint32_t* fast_ids, uin
     out->refinement_failed = false;
     out->skip_reason.clear();
     const HubnessSnapshot hubness = hubness_snapshot();   // the table this search started with (fast_hits is corrected once, below)
+    const SmoothSnapshot smooth = smooth_snapshot();      // ... and the k-NN graph
     const auto t0 = clock::now();
     // quality embedding: needed by phase 1 only, optionally computed while phase 0 runs
     // (a vector has its EMBEDDER's dimension; an index of another dimension answers DimensionMismatch — search.rs:1602-1610 — which
@@ -264,7 +296,7 @@ fsgpu_status SyncTwoTierSearcher::search_unbatched(const uint32_t* fast_ids, uin
     std::vector<Hit> fast_hits;
     st = tier_hits(fast_, fast_vec, fetch, cfg_.fast_tier_int8_multiplier, &fast_hits, detail);
     if (st != FSGPU_OK) return st;
-    st = correct_phase1_pool(hubness.get(), &fast_hits, detail);   // shadows fast_hits for everything downstream (searcher.rs:1869-1873)
+    st = correct_phase1_pool(hubness.get(), smooth.get(), &fast_hits, detail);   // shadows fast_hits for everything downstream (searcher.rs:1869-1873)
     if (st != FSGPU_OK) return st;
     m.fast_search_ms = ms_since(t1);
     st = fuse_initial(fast_hits, k, lexical, n_lexical, &out->initial, detail);

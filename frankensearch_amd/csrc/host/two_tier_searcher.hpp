@@ -29,6 +29,15 @@ struct HubnessTable {
     float beta = 0.0f;
 };
 using HubnessSnapshot = std::shared_ptr<const HubnessTable>;
+// The fast tier's k-NN table and TwoTierConfig::neighbor_smoothing_* as one immutable snapshot (fshost_two_tier_set_neighbor_smoothing
+// swaps it whole).
+struct SmoothGraph {
+    std::vector<uint32_t> rows;   // [len, width], 0xffffffff padding
+    uint64_t len = 0;
+    uint32_t width = 0;
+    fsgpu_smooth_config cfg{};
+};
+using SmoothSnapshot = std::shared_ptr<const SmoothGraph>;
 
 struct Outcome {
     std::vector<fshost_hit> initial, final_results;
@@ -102,6 +111,10 @@ class SyncTwoTierSearcher {
     // on entry, search_many per call, a batched callers' chunk at admission) and every stage of it works on that snapshot.
     void set_hubness(const float* table, uint64_t table_len, float beta);
     HubnessSnapshot hubness_snapshot() const { return std::atomic_load(&hubness_); }
+    // with_document_graph + TwoTierConfig::neighbor_smoothing_* (searcher.rs:737-777): the graph is copied; an identity configuration
+    // or a NULL / empty graph detaches it.  The same snapshot discipline as the hubness table.
+    void set_neighbor_smoothing(const uint32_t* graph_rows, uint64_t graph_len, uint32_t graph_width, float alpha, uint32_t m, bool mutual);
+    SmoothSnapshot smooth_snapshot() const { return std::atomic_load(&smooth_); }
     void batching_stats(uint64_t* chunks, uint64_t* requests) const;
 
   private:
@@ -111,10 +124,12 @@ class SyncTwoTierSearcher {
     void init();
     fsgpu_status tier_hits(const Tier& tier, const std::vector<float>& vec, uint32_t fetch, uint32_t int8_multiplier,
                            std::vector<Hit>* hits, std::string* detail) const;
-    // correct_phase1_pool (searcher.rs:737-777) on the fast tier's pool: apply_hubness_penalty by Hit::index, one sort by cmp_rank.
+    // correct_phase1_pool (searcher.rs:737-777) on the fast tier's pool: apply_hubness_penalty by Hit::index, then — with a graph —
+    // neighbor_smooth by Hit::index, ONE sort by cmp_rank at the end.
     // Every consumer of the fast pool (both RRFs, the blend, quality_scores_for_hits, the rank maps) sees the corrected pool.
-    // `table`: the search's snapshot (null: no correction) — never re-read from the searcher in mid-search.
-    fsgpu_status correct_phase1_pool(const HubnessTable* table, std::vector<Hit>* fast_hits, std::string* detail) const;
+    // `table` / `graph`: the search's snapshots (null: that correction is off) — never re-read from the searcher in mid-search.
+    fsgpu_status correct_phase1_pool(const HubnessTable* table, const SmoothGraph* graph, std::vector<Hit>* fast_hits,
+                                     std::string* detail) const;
     fsgpu_status hits_from_rows(const Tier& tier, const uint32_t* rows, const float* scores, uint32_t count, std::vector<Hit>* hits,
                                 std::string* detail) const;
     fsgpu_status fuse_initial(const std::vector<Hit>& fast_hits, uint32_t k, const fsgpu_scored_doc* lexical, uint32_t n_lexical,
@@ -139,6 +154,7 @@ class SyncTwoTierSearcher {
     mutable std::unique_ptr<ManyEngine> engine_;
     std::atomic<bool> batching_{false};
     HubnessSnapshot hubness_;   // null: no correction (read and swapped with std::atomic_load / _store)
+    SmoothSnapshot smooth_;     // null: no smoothing (likewise)
 };
 
 // The many-queries engine (two_tier_many.cpp): four stage threads + a fusion pool over the searcher's handles.

@@ -511,4 +511,32 @@ struct CompactArgs {
 };
 hipError_t launch_compact_runs(const CompactArgs& args, bool nt_stores, hipStream_t stream);
 
+// knn_graph_kernels.hip: the two ends of a k-NN graph build step (vector_index_knn.cpp; include/fsgpu.h).  The step in between is
+// the batched search itself: the staged block is its query block, the emit kernel reads its hits.
+constexpr uint32_t kKnnChunk = 1024;      // source rows per step
+constexpr uint32_t kKnnMaxM = 63;         // k = m + 1 stays inside the fused tiers
+constexpr uint32_t kKnnPadRow = 0xffffffffu;
+struct KnnStageArgs {
+    const void* slab;            // the index's rows (f16 or f32)
+    uint32_t row_stride;         // bytes between rows
+    uint32_t dim;
+    uint32_t slab_f32;
+    uint32_t row_base;           // added to the local rows in src_out
+    const uint32_t* src_local;   // [n] live source rows of this chunk, local (device-visible)
+    uint32_t n;
+    float* queries;              // out: [n, dim] f32, row i = slab row src_local[i] widened
+    uint32_t* src_out;           // out: [n] global source rows
+};
+hipError_t launch_knn_stage_rows(const KnnStageArgs& args, hipStream_t stream);
+struct KnnEmitArgs {
+    const uint32_t* hit_rows;    // [n, m + 1] global rows of the searches, best first
+    const float* hit_scores;     // [n, m + 1]
+    const uint32_t* hit_counts;  // [n]
+    const uint32_t* src;         // [n] global source rows
+    uint32_t n, m;
+    uint32_t* out_rows;          // [n, m], padded with kKnnPadRow
+    float* out_sims;             // nullable: [n, m], padded with 0.0f
+};
+hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
+
 }  // namespace fsgpu

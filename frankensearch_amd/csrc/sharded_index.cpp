@@ -941,4 +941,124 @@ SearchError ShardedIndex::compute_query_hubness(const float* queries, uint32_t n
     return SearchError{};
 }
 
+// The k-NN graph over a row-sharded index (include/fsgpu.h, fsgpu_sharded_build_knn_graph): every row shard's live rows are the
+// queries of batched searches over ALL shards, in global row order.  The sources are staged THROUGH THE HOST: the owning shard widens
+// a chunk to f32 (knn_stage_rows_kernel) and copies it up, begin() sends it to every shard like any host batch, and the self rule
+// runs on the host over the merged hits.  That is one [chunk, dim] f32 round trip per step beside a scan of every shard's slab; two
+// steps are in flight (the handle's two tickets), so the staging of step c + 1 overlaps the scans of step c.
+SearchError ShardedIndex::build_knn_graph(uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows, float* out_sims) {
+    if (m < 1 || m > kKnnMaxM) return make_err(FSGPU_ERR_INVALID_CONFIG, "m must be 1 .. 63 (k = m + 1 stays inside the fused tiers)");
+    if (first_row > nrows_ || n_rows > nrows_ - first_row)
+        return make_err(FSGPU_ERR_INVALID_CONFIG, "source rows " + std::to_string(first_row) + " .. " + std::to_string(first_row + n_rows) +
+                                                      " lie past record_count " + std::to_string(nrows_));
+    if (n_rows == 0) return SearchError{};
+    for (const RootSlot& r : root_)
+        if (r.pending) return make_err(FSGPU_ERR_INVALID_CONFIG, "a search is in flight on this handle: end it first (the build takes both tickets)");
+    const uint32_t k = m + 1;
+    struct Step {
+        std::vector<uint32_t> src;      // global source rows
+        std::vector<float> queries;
+        std::vector<uint32_t> rows, counts;
+        std::vector<float> scores;
+        uint64_t ticket = 0;
+        bool begun = false;
+    } steps[2];
+    auto pad = [&](uint64_t row) {
+        const size_t at = (size_t)(row - first_row) * m;
+        for (uint32_t x = 0; x < m; ++x) out_rows[at + x] = kKnnPadRow;
+        if (out_sims)
+            for (uint32_t x = 0; x < m; ++x) out_sims[at + x] = 0.0f;
+    };
+    auto abandon = [&](SearchError e) {
+        for (Step& s : steps)
+            if (s.begun) {
+                (void)end(s.ticket, s.rows.data(), s.scores.data(), s.counts.data(), nullptr);
+                s.begun = false;
+            }
+        return e;
+    };
+    auto finish = [&](Step& s) -> SearchError {
+        s.begun = false;
+        SH_TRY(end(s.ticket, s.rows.data(), s.scores.data(), s.counts.data(), nullptr));
+        for (size_t i = 0; i < s.src.size(); ++i) {
+            const uint32_t cnt = std::min(s.counts[i], k);
+            const uint32_t* hr = s.rows.data() + i * k;
+            const float* hs = s.scores.data() + i * k;
+            uint32_t p = m;   // the self entry's position; absent: the last entry is dropped
+            for (uint32_t x = 0; x < cnt; ++x)
+                if (hr[x] == s.src[i]) {
+                    p = x;
+                    break;
+                }
+            const size_t at = (size_t)(s.src[i] - first_row) * m;
+            for (uint32_t x = 0; x < m; ++x) {
+                const uint32_t from = x < p ? x : x + 1;
+                out_rows[at + x] = from < cnt ? hr[from] : kKnnPadRow;
+                if (out_sims) out_sims[at + x] = from < cnt ? hs[from] : 0.0f;
+            }
+        }
+        return SearchError{};
+    };
+    const uint64_t last = first_row + n_rows;
+    uint64_t c = 0;
+    std::vector<uint32_t> local;
+    const uint32_t nshards = std::min<uint32_t>(row_shards_, (uint32_t)shards_.size());
+    for (uint32_t r = 0; r < nshards; ++r) {
+        Shard& sh = *shards_[r];
+        uint64_t next = std::max(first_row, sh.lo);
+        const uint64_t stop = std::min(last, sh.lo + sh.rows);
+        if (next >= stop) continue;
+        {
+            std::lock_guard<std::mutex> lock(sh.index.mutex());
+            const SearchError e = sh.index.fetch_live_host();
+            if (!e.ok()) return abandon(e);
+        }
+        while (next < stop) {
+            Step& s = steps[c & 1];
+            if (s.begun) {
+                const SearchError e = finish(s);
+                if (!e.ok()) return abandon(e);
+            }
+            s.src.clear();
+            local.clear();
+            while (next < stop && local.size() < kKnnChunk) {
+                if (sh.index.row_tombstoned(next - sh.lo)) pad(next);
+                else {
+                    s.src.push_back((uint32_t)next);
+                    local.push_back((uint32_t)(next - sh.lo));
+                }
+                ++next;
+            }
+            if (local.empty()) continue;
+            const uint32_t n = (uint32_t)local.size();
+            s.queries.resize((size_t)n * dim_);
+            s.rows.resize((size_t)n * k);
+            s.scores.resize((size_t)n * k);
+            s.counts.resize(n);
+            {
+                std::lock_guard<std::mutex> lock(sh.index.mutex());
+                const SearchError e = sh.index.knn_stage_rows_host(local.data(), n, s.queries.data());
+                if (!e.ok()) return abandon(e);
+            }
+            Request rq;
+            rq.queries = s.queries.data();
+            rq.nq = n;
+            rq.k = k;
+            rq.mode = kBatched;
+            const SearchError e = begin(rq, dim_, &s.ticket);
+            if (!e.ok()) return abandon(e);
+            s.begun = true;
+            ++c;
+        }
+    }
+    for (uint64_t x = c; x < c + 2; ++x) {   // in ticket order
+        Step& s = steps[x & 1];
+        if (s.begun) {
+            const SearchError e = finish(s);
+            if (!e.ok()) return abandon(e);
+        }
+    }
+    return SearchError{};
+}
+
 }  // namespace fsgpu

@@ -99,6 +99,9 @@ class ShardedIndex {
     SearchError gather_dot(const float* query, uint32_t query_len, const uint32_t* rows, uint32_t n, float* out);
     // the query-hubness table of every row (VectorIndex::compute_query_hubness per row shard, concatenated in global row order)
     SearchError compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out);
+    // the k-NN graph of the sources first_row .. first_row + n_rows over ALL shards' rows (VectorIndex::build_knn_graph's definition and
+    // layout; equal to the unsharded graph for every layout).  The sources are staged through the host.
+    SearchError build_knn_graph(uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows, float* out_sims);
 
     uint64_t record_count() const { return nrows_; }
     uint32_t dimension() const { return dim_; }

@@ -202,6 +202,18 @@ class VectorIndex {
     // rows; else the host restatement over rows fetched in blocks (same bits).  out_topk (nullable): [record_count(), k] selected
     // sims, greatest first.  Host pointers; blocks; own workspaces on the index's stream.
     SearchError compute_query_hubness(const float* queries, uint32_t nq, uint32_t query_dim, uint32_t kq, float* out, float* out_topk);
+    // The exact k-NN graph over the main slab (include/fsgpu.h, fsgpu_index_build_knn_graph; vector_index_knn.cpp): for the sources
+    // first_row .. first_row + n_rows the first m live rows j != i of the row-level search for "row i widened to f32".  The live
+    // sources are staged in chunks of kKnnChunk (knn_graph_kernels.hip) and answered by search_top_k_batched_device_begin / _end, two
+    // steps in flight; rows, queries and hits stay in HBM.  out_rows [n_rows, m] (kKnnPadRow padding), out_sims nullable.  Host
+    // pointers; blocks; takes both tickets.
+    SearchError build_knn_graph(uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows, float* out_sims);
+    struct KnnBuildStats {   // of the last build_knn_graph: what the ridden search reported, summed over the steps
+        uint64_t steps = 0, sources = 0, fallbacks = 0, late_answers = 0;
+    };
+    KnnBuildStats last_knn_build;
+    // ... a row shard's half of the sharded build: n live local rows (src_local) widened to f32 into a host block [n, dim]
+    SearchError knn_stage_rows_host(const uint32_t* src_local, uint32_t n, float* out);
 
     // VectorIndex::append_batch (lib.rs:2546-2720): every entry validated before anything changes, last-wins dedup inside the batch,
     // resident copies superseded, the first live main row of each doc id tombstoned, ONE live-bitmap upload.  wal_append is a batch of one.
@@ -408,6 +420,7 @@ class VectorIndex {
     DeviceBuffer ws_out_;   // rows | scores | counts of a blocking batched search (one block: one copy up)
     DeviceBuffer ws_mmr_in_, ws_mmr_out_, ws_mmr_sims_, ws_mmr_vec_;   // mmr_rerank_rows: inputs (one copy down), order | counts, matrix, staged rows
     DeviceBuffer ws_hub_q_, ws_hub_out_, ws_hub_topk_;   // compute_query_hubness: the sample, the table, the selected sims (lab)
+    DeviceBuffer ws_knn_[2];   // build_knn_graph: per step in flight  queries | sources | hit rows | hit scores | counts | out rows | out sims
     bool i8_ready_ = false, n4_ready_ = false, i8_stats_ready_ = false, n4u_ready_ = false;
     bool quant_max_ready_ = false;   // i8_max_ holds a corpus-wide max-abs handed in by a sharded index: the quantisers keep it
     u64* tp_approx_out_ = nullptr;   // two_pass_candidates_device: where the batch in flight leaves its candidate pairs

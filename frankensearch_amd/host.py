@@ -71,7 +71,7 @@ class _ManyResult(C.Structure):
 
 
 SYMBOLS = ("fshost_two_tier_create", "fshost_two_tier_create_sharded", "fshost_two_tier_destroy", "fshost_two_tier_search",
-           "fshost_two_tier_search_many", "fshost_run_load_many", "fshost_two_tier_set_batching", "fshost_two_tier_set_hubness", "fshost_two_tier_batching_stats", "fshost_run_load", "fshost_embed_search_stream", "fshost_embed_search_stream_dp")
+           "fshost_two_tier_search_many", "fshost_run_load_many", "fshost_two_tier_set_batching", "fshost_two_tier_set_hubness", "fshost_two_tier_set_neighbor_smoothing", "fshost_two_tier_batching_stats", "fshost_run_load", "fshost_embed_search_stream", "fshost_embed_search_stream_dp")
 _handle = None
 
 
@@ -106,6 +106,8 @@ def lib() -> C.CDLL:
         h.fshost_two_tier_set_batching.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         h.fshost_two_tier_set_hubness.restype = C.c_int32
         h.fshost_two_tier_set_hubness.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float]
+        h.fshost_two_tier_set_neighbor_smoothing.restype = C.c_int32
+        h.fshost_two_tier_set_neighbor_smoothing.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_int32]
         h.fshost_two_tier_batching_stats.restype = C.c_int32
         h.fshost_two_tier_batching_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         h.fshost_run_load_many.restype = C.c_int32
@@ -252,6 +254,19 @@ class NativeTwoTierSearcher:
             return
         t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
         check(lib().fshost_two_tier_set_hubness(self._h, t.ctypes.data_as(C.c_void_p), t.size, float(beta)))
+
+    def set_neighbor_smoothing(self, graph_rows, alpha: float = 0.3, m: int = 10, mutual: bool = False) -> None:
+        """fshost_two_tier_set_neighbor_smoothing: attach the fast tier's k-NN table [rows, width] (copied; VectorIndex.build_knn_graph
+        builds it); None / empty, alpha <= 0 or m == 0 detaches it.  The fast pool is then de-hubbed (if a table is attached),
+        smoothed and sorted once before the first RRF (searcher.rs:737-777)."""
+        if graph_rows is None:
+            check(lib().fshost_two_tier_set_neighbor_smoothing(self._h, None, 0, 0, float(alpha), int(m), int(bool(mutual))))
+            return
+        g = np.ascontiguousarray(graph_rows, dtype=np.uint32)
+        if g.ndim != 2:
+            raise ValueError("graph_rows must be [rows, width]")
+        check(lib().fshost_two_tier_set_neighbor_smoothing(self._h, g.ctypes.data_as(C.c_void_p) if g.size else None, g.shape[0], g.shape[1],
+                                                           float(alpha), min(max(int(m), 0), 0xFFFFFFFF), int(bool(mutual))))
 
     def batching_stats(self):
         a, b = C.c_uint64(), C.c_uint64()

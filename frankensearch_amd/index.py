@@ -446,6 +446,18 @@ class VectorIndex:
                                                             _ptr(topk)))
         return out, topk
 
+    def build_knn_graph(self, m: int = 10, first_row: int = 0, n_rows=None, want_sims: bool = False):
+        """fsgpu_index_build_knn_graph: the exact k-NN lists of the main rows first_row .. first_row + n_rows (default: to the end),
+        [n_rows, m] uint32 global row ids, nearest first, 0xffffffff padding (and the [n_rows, m] f32 similarities with want_sims).
+        Defined by this index's own row-level search; rides the batched search on the device."""
+        if n_rows is None:
+            n_rows = max(self.record_count() - int(first_row), 0)
+        rows = np.full((int(n_rows), max(int(m), 0)), 0xFFFFFFFF, dtype=np.uint32)
+        sims = np.zeros((int(n_rows), max(int(m), 0)), dtype=np.float32) if want_sims else None
+        check(_lib.lib().fsgpu_index_build_knn_graph(self._h, int(first_row), int(n_rows), min(max(int(m), 0), 0xFFFFFFFF),
+                                                     _ptr(rows) if rows.size else None, _ptr(sims) if want_sims and sims.size else None))
+        return (rows, sims) if want_sims else rows
+
     def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
         """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes
         into `rows` (and the pool x pool f64 similarity matrix with want_sims)."""
@@ -791,6 +803,17 @@ class NativeShardedIndex:
         out = np.zeros(n, dtype=np.float32)
         check(_lib.lib().fsgpu_sharded_compute_query_hubness(self._h, _ptr(q) if nq else None, nq, qdim, kq, _ptr(out) if n else None))
         return out
+
+    def build_knn_graph(self, m: int = 10, first_row: int = 0, n_rows=None, want_sims: bool = False):
+        """fsgpu_sharded_build_knn_graph: VectorIndex.build_knn_graph over all shards' rows, in global row order (the sources are
+        staged through the host)."""
+        if n_rows is None:
+            n_rows = max(self.record_count() - int(first_row), 0)
+        rows = np.full((int(n_rows), max(int(m), 0)), 0xFFFFFFFF, dtype=np.uint32)
+        sims = np.zeros((int(n_rows), max(int(m), 0)), dtype=np.float32) if want_sims else None
+        check(_lib.lib().fsgpu_sharded_build_knn_graph(self._h, int(first_row), int(n_rows), min(max(int(m), 0), 0xFFFFFFFF),
+                                                       _ptr(rows) if rows.size else None, _ptr(sims) if want_sims and sims.size else None))
+        return (rows, sims) if want_sims else rows
 
     def set_coalescing(self, max_batch: int, max_wait_us: int) -> None:
         """Concurrent single-query searches ride one search of the shards (fsgpu_sharded_set_coalescing)."""

@@ -157,7 +157,8 @@ fsgpu_status fsgpu_index_wal_append_batch(fsgpu_index *idx, uint32_t n, const ch
  *     the call returns;
  *   - an fsgpu_allow_bitmap made before is refused (FSGPU_ERR_INVALID_CONFIG): make a new one;
  *   - the CALLER rebuilds what it derived: alignments (fsgpu_alignment_create), hubness tables (fsgpu_index_compute_query_hubness),
- *     allow bitmaps from fsgpu_index_allow_bitmap_for_hashes, and any fshost_two_tier searcher built over the index (libfshost does
+ *     k-NN graphs (fsgpu_index_build_knn_graph: after a compaction or a vacuum the rows are renumbered, so every entry of the table
+ *     and every list's position names another row), allow bitmaps from fsgpu_index_allow_bitmap_for_hashes, and any fshost_two_tier searcher built over the index (libfshost does
  *     not follow a compaction);
  *   - doc-id pointers handed out by fsgpu_index_doc_id before the call are invalid. */
 typedef struct fsgpu_compaction_stats { /* wal::CompactionStats (wal.rs:111) */
@@ -873,6 +874,70 @@ fsgpu_status fsgpu_index_compute_query_hubness(fsgpu_index *idx, const float *qu
  * collective: a row's value does not depend on the layout. */
 fsgpu_status fsgpu_sharded_compute_query_hubness(fsgpu_sharded *sh, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
                                                  float *out);
+
+/* ---- the k-NN graph over the main slab and the phase-1 neighbour smoothing ---- */
+/* The reference's k-NN graph diffusion (crates/frankensearch-fusion/src/smooth.rs; second step of correct_phase1_pool,
+ * searcher.rs:737-777) walks the `Similar` edges of a DocumentGraph, "nearest-first, as a k-NN builder produces" (smooth.rs:126-129);
+ * the reference has no such builder.  This is one, exact, on the device.
+ * THE GRAPH IS DEFINED BY THE INDEX'S OWN SEARCH.  For a main row i, knn(i, m) is the first m live main rows j != i under the
+ * reference's total order — key(score) descending with NaN as -inf, row ascending — where score(i, j) is what a row-level exact
+ * search of this index returns for the query q = row i widened to f32 (exact for an F16 slab; an F32 slab uses its own values):
+ * dot_product_f16_bytes_f32 / dot_product_f32_bytes_f32 in the index's current hreduce order.  Equivalently: take the row-level
+ * top-(m + 1) of that query, remove the entry whose row is i if it is there, otherwise drop the last entry (which happens when more
+ * than m lower-numbered duplicates of row i exist).
+ *   - tombstoned rows are never targets; as sources they get an empty list.  No search is run for them.
+ *   - resident WAL entries take no part: the graph is over the main slab.  There is no doc-id dedup.
+ *   - a list shorter than m (fewer than m + 1 live rows, a tombstoned source) is padded with 0xffffffff rows and 0.0f similarities.
+ *   - row ids are global: row_base is added, as in every search.
+ * The call covers the sources first_row .. first_row + n_rows: out_rows [n_rows, m] u32 and out_sims [n_rows, m] f32 (may be NULL)
+ * are HOST arrays, list r at offset (r - first_row) * m; the call blocks.  1 <= m <= 63, so that k = m + 1 stays inside the fused
+ * tiers of the batched search; anything else, or a range past record_count, is FSGPU_ERR_INVALID_CONFIG.  n_rows == 0 is OK and does
+ * nothing.  Without a device: FSGPU_ERR_NO_DEVICE.  Errors are reported before any work starts.
+ * HOW IT RUNS.  No second scan: the live sources are staged from the slab, up to 1,024 per step, into an f32 query block in HBM
+ * (knn_stage_rows_kernel), answered by the batched search unchanged — int8 filter under its proven bound, finish in the reference's
+ * order, fallbacks as they are (fsgpu_search_topk_batched_device_begin / _end_late) — and turned into lists by knn_emit_kernel, which
+ * finds the self entry with a ballot and shifts the tail up.  Rows, queries and hits stay in HBM; the lists come up through a pinned
+ * block, one copy per step, underneath the next step's search.  Two steps are in flight: the call uses BOTH search tickets of the
+ * handle and holds the index for its whole duration, so searches on the same handle wait behind it, and it is refused
+ * (FSGPU_ERR_INVALID_CONFIG) while a begun search is outstanding.  The range arguments let a caller build in slices between
+ * searches and resume a partial build; slices concatenate to the whole-graph call.  Which path answers the searches is the batched
+ * search's own choice (slabs under 32,768 rows, F32 slabs and dimensions outside 64 / 128 / 256 / 384 take the exact kernels): the
+ * graph is the same by definition on every path. */
+fsgpu_status fsgpu_index_build_knn_graph(fsgpu_index *idx, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t *out_rows,
+                                         float *out_sims);
+/* The same over a row-sharded handle: every row shard's live rows are the queries of sharded batched searches over ALL shards, in
+ * global row order; the result equals the unsharded graph over the same rows for every layout.  The sources are STAGED THROUGH THE
+ * HOST here: the owning shard widens a step's rows to f32 and copies them up ([1,024, dim] f32, 1.5 MB at 384 dimensions), the
+ * sharded search sends them to every shard like any host batch, and the self rule runs on the host over the merged hits — one
+ * round trip of the query block per step beside a scan of every shard's slab, overlapped with the step before (two tickets).  The
+ * sharded search's own limits apply (dimension a multiple of 8). */
+fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded *sh, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t *out_rows,
+                                           float *out_sims);
+/* SmoothConfig (smooth.rs:38-69): defaults alpha = 0.3, m = 10, mutual = 0; the reserved words must be 0. */
+typedef struct fsgpu_smooth_config {
+    float alpha;
+    uint32_t m;
+    uint32_t mutual;
+    uint32_t reserved[5]; /* must be 0 */
+} fsgpu_smooth_config;
+fsgpu_status fsgpu_smooth_config_default(fsgpu_smooth_config *config);
+/* neighbor_smooth / neighbor_smooth_ranked (smooth.rs:84-153, 176-276) in place, on the host.  graph_rows [graph_len, graph_width] is
+ * a table of fsgpu_index_build_knn_graph (its out_rows).
+ * DEVIATION, deliberate: the reference keys the pool and the graph by doc-id STRING; this function keys both by ROW (hits[i].index),
+ * which is what the device builds and what a search returns.  Two rows with the same doc id are two nodes here.  A hit with
+ * index >= graph_len — a WAL virtual row, or 0xffffffff — has no edges and is nobody's neighbour: WAL documents are isolated.
+ *   identity (*out_applied = 0, nothing touched, nothing sorted): alpha non-finite or <= 0, m == 0, a NULL or empty graph, n == 0.
+ *   pool: row -> score; a row that occurs twice counts with its LAST occurrence (the AHashMap insert).
+ *   walk: for each hit the first min(m, graph_width) entries of its list, stopping at the first 0xffffffff; every walked entry
+ *     counts as examined, in the pool or not; the in-pool neighbours' scores are summed into ONE f32 accumulator in list order;
+ *     mean = sum / (float)count, or the hit's own score when no neighbour is in the pool;
+ *     score' = (1.0f - alpha) * score + alpha * mean as two multiplies and an add, none of it fused.
+ *   mutual != 0: a walked in-pool neighbour counts only if the hit's row occurs ANYWHERE in that neighbour's stored list — all
+ *     graph_width columns, not the first m (the reference's reciprocity set is uncapped).
+ *   resort != 0 sorts by VectorHit::cmp_rank, as fsgpu_apply_hubness_penalty does.  A NULL config means the defaults; non-zero
+ *   reserved words are FSGPU_ERR_INVALID_CONFIG. */
+fsgpu_status fsgpu_neighbor_smooth(fsgpu_scored_doc *hits, uint32_t n, const uint32_t *graph_rows, uint64_t graph_len,
+                                   uint32_t graph_width, const fsgpu_smooth_config *config, int32_t resort, uint8_t *out_applied);
 
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */

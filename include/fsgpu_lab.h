@@ -85,6 +85,10 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
                                                 float *out, float *out_topk);
+/* What the batched search reported to the last fsgpu_index_build_knn_graph on this handle, summed over its steps: out[0] steps,
+ * out[1] live sources searched, out[2] queries answered by the exact kernels (fallbacks), out[3] queries answered in a step's end
+ * half (fallbacks + queries the int8 filter handed to the f16 filter). */
+fsgpu_status fsgpu_lab_index_knn_build_stats(fsgpu_index *idx, uint64_t *out4);
 /* ---- compaction (fsgpu_index_compact / _vacuum) ---- */
 /* Destination rows one launch of the segmented-copy kernel covers (0 = the default, 2^20): lets a test cross launch boundaries with a
  * few thousand rows. */

@@ -151,6 +151,20 @@ fsgpu_status fshost_two_tier_batching_stats(fshost_two_tier *s, uint64_t *chunks
  * table it started with. */
 fsgpu_status fshost_two_tier_set_hubness(fshost_two_tier *s, const float *table, uint64_t table_len, float beta);
 
+/* The k-NN graph diffusion of phase 1: TwoTierSearcher::with_document_graph + TwoTierConfig::neighbor_smoothing_* in one call
+ * (searcher.rs:737-777; smooth.rs).  graph_rows [graph_len, graph_width] is the FAST tier's k-NN table, indexed by the hit's row
+ * (fsgpu_index_build_knn_graph / fsgpu_sharded_build_knn_graph build it); it is copied and held as one immutable snapshot that is
+ * swapped whole, like the hubness table.  An identity configuration (alpha non-finite or <= 0, m == 0) or a NULL / empty graph
+ * detaches it, and every search returns what it returned before the call was ever made.  When active, correct_phase1_pool is the
+ * reference's: the hubness penalty WITHOUT its own sort (if a table is attached), then fsgpu_neighbor_smooth, then ONE sort by
+ * VectorHit::cmp_rank; the corrected pool replaces the fast pool everywhere downstream (both RRFs, the blend,
+ * quality_scores_for_hits, the rank maps) — in fshost_two_tier_search, in fshost_two_tier_search_many (on the fusion threads) and
+ * over sharded tiers alike.  Keyed by ROW, not by doc id (fsgpu.h states the deviation): a hit of a resident WAL entry has no edges
+ * and is nobody's neighbour.  May be called between searches or beside them: a search in flight keeps the snapshot it started
+ * with.  Hubness-only and uncorrected searches are byte-identical to what they were. */
+fsgpu_status fshost_two_tier_set_neighbor_smoothing(fshost_two_tier *s, const uint32_t *graph_rows, uint64_t graph_len,
+                                                    uint32_t graph_width, float alpha, uint32_t m, int32_t mutual);
+
 /* Closed-loop load generator: `threads` native threads each issue fshost_two_tier_search calls back to back on
  * synthetic queries (SURVEY §8d config 5 shapes: fast ids uniform in [0, fast_vocab), 4-23 tokens; quality ids
  * [CLS] + uniform [1000, quality_vocab) + [SEP], 8-32 tokens; stub lexical list of 3k "doc-%08u" ids), the way a
