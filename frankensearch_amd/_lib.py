@@ -148,6 +148,7 @@ SIGNATURES = {
     "fsgpu_bert_linear_format": (_u32, [_vp]),
     "fsgpu_lab_linear_int8_dynamic": (_i32, [_i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_lab_bert_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_stage_args: BertStageArgs below)
+    "fsgpu_lab_bert_short_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_short_args: BertShortArgs below)
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
@@ -224,6 +225,13 @@ class BertStageArgs(C.Structure):
     _fields_ = [(name, _u32) for name in ("stage", "form", "epilogue", "m", "n", "k", "hidden", "inter", "n_docs", "vocab", "max_pos")] + [
         ("eps", C.c_float), ("scale", C.c_float), ("offsets", _vp), ("ids", _vp), ("positions", _vp), ("types", _vp),
         ("in_", _vp * 12), ("out0", _vp), ("out1", _vp)]
+
+
+class BertShortArgs(C.Structure):
+    """fsgpu_lab_bert_short_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("stage", "form", "m", "n_docs", "hidden", "inter", "heads", "layers", "vocab", "max_pos")] + [
+        ("eps", C.c_float), ("scale", C.c_float), ("offsets", _vp), ("ids", _vp), ("positions", _vp),
+        ("in_", _vp * 8), ("layer_in", _vp), ("out0", _vp), ("out1", _vp)]
 
 
 _lib = None

@@ -609,13 +609,12 @@ bool NativeEmbedder::docs_path(uint32_t tokens, uint32_t max_seq) const {
     return !off && !int8_ && docs_ready_ && tokens > 32 && max_seq <= 32 && (long)tokens <= max_tokens;
 }
 
-// Every text at most 32 tokens long (a batch of queries): ONE launch for the whole forward (bert_docs_w.hip).  Consecutive texts
-// are packed greedily into row blocks of at most 32 tokens; a block never splits a text.  ids: this call's tokens; offs: the
-// call's offsets rebased to 0.
-SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out,
-                                       float* out_dev) {
-    const size_t H = cfg_.hidden;
-    std::vector<uint32_t> blk_tok, blk_doc;
+// Consecutive texts are packed greedily into row blocks of at most 32 tokens; a block never splits a text.
+BertDocsPacking bert_docs_pack(const int32_t* ids, const uint32_t* offs, uint32_t n, uint32_t total) {
+    BertDocsPacking p;
+    p.n = n;
+    std::vector<uint32_t>& blk_tok = p.blk_tok;
+    std::vector<uint32_t>& blk_doc = p.blk_doc;
     blk_tok.reserve(n + 1);
     blk_doc.reserve(n + 1);
     blk_tok.push_back(0);
@@ -633,10 +632,13 @@ SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uin
     blk_tok.push_back(total);
     blk_doc.push_back(n);
     const uint32_t nblocks = (uint32_t)blk_tok.size() - 1;
+    p.nblocks = nblocks;
     // the blocks' rows, laid out so that a block needs ONE read of the inputs before its embedding gather: token id (-1 = padding),
     // rows of the block << 16 | position inside the text << 8 | the text's index among the block's non-empty texts
-    std::vector<int32_t> row_id((size_t)nblocks * 32, -1);
-    std::vector<uint32_t> row_meta((size_t)nblocks * 32, 0u);
+    p.row_id.assign((size_t)nblocks * 32, -1);
+    p.row_meta.assign((size_t)nblocks * 32, 0u);
+    std::vector<int32_t>& row_id = p.row_id;
+    std::vector<uint32_t>& row_meta = p.row_meta;
     for (uint32_t b = 0; b < nblocks; ++b) {
         const uint32_t t0 = blk_tok[b], nrows = blk_tok[b + 1] - t0;
         uint32_t local = 0;
@@ -651,9 +653,38 @@ SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uin
         }
     }
     // one input block: [offsets | blk_tok | blk_doc | row_id | row_meta]
-    const size_t o_tok = (size_t)(n + 1) * 4, o_doc = o_tok + (size_t)(nblocks + 1) * 4, o_rid = o_doc + (size_t)(nblocks + 1) * 4,
-                 o_rmeta = o_rid + (size_t)nblocks * 32 * 4;
-    const size_t in_bytes = (o_rmeta + (size_t)nblocks * 32 * 4 + 255) & ~(size_t)255;
+    p.o_tok = (size_t)(n + 1) * 4;
+    p.o_doc = p.o_tok + (size_t)(nblocks + 1) * 4;
+    p.o_rid = p.o_doc + (size_t)(nblocks + 1) * 4;
+    p.o_rmeta = p.o_rid + (size_t)nblocks * 32 * 4;
+    p.in_bytes = (p.o_rmeta + (size_t)nblocks * 32 * 4 + 255) & ~(size_t)255;
+    return p;
+}
+
+void BertDocsPacking::fill(unsigned char* dst, const uint32_t* offs) const {
+    std::memcpy(dst, offs, (size_t)(n + 1) * 4);
+    std::memcpy(dst + o_tok, blk_tok.data(), (size_t)(nblocks + 1) * 4);
+    std::memcpy(dst + o_doc, blk_doc.data(), (size_t)(nblocks + 1) * 4);
+    std::memcpy(dst + o_rid, row_id.data(), row_id.size() * 4);
+    std::memcpy(dst + o_rmeta, row_meta.data(), row_meta.size() * 4);
+}
+
+void BertDocsPacking::point(BertDocsArgs& a, const unsigned char* base) const {
+    a.offsets = reinterpret_cast<const uint32_t*>(base);
+    a.blk_tok = reinterpret_cast<const uint32_t*>(base + o_tok);
+    a.blk_doc = reinterpret_cast<const uint32_t*>(base + o_doc);
+    a.row_id = reinterpret_cast<const int32_t*>(base + o_rid);
+    a.row_meta = reinterpret_cast<const uint32_t*>(base + o_rmeta);
+}
+
+// Every text at most 32 tokens long (a batch of queries): ONE launch for the whole forward (bert_docs_w.hip) over the row blocks of
+// bert_docs_pack.  ids: this call's tokens; offs: the call's offsets rebased to 0.
+SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out,
+                                       float* out_dev) {
+    const size_t H = cfg_.hidden;
+    const BertDocsPacking pk = bert_docs_pack(ids, offs.data(), n, total);
+    const uint32_t nblocks = pk.nblocks;
+    const size_t in_bytes = pk.in_bytes;
     const size_t out_bytes = (size_t)n * H * 4;
     const bool pinned = in_bytes + out_bytes <= kDocsIoBytes;
     if (pinned && !docs_io_ && !docs_io_failed_ && hipHostMalloc(&docs_io_, kDocsIoBytes, hipHostMallocMapped) != hipSuccess) {
@@ -671,20 +702,8 @@ SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uin
     a.nlayers = (int)cfg_.layers;
     a.eps = cfg_.ln_eps;
     a.attn_scale = 0.17677669f;  // ATTN_SCALE_F32 = 1/sqrt(32) (native.rs:44)
-    auto fill = [&](unsigned char* dst) {
-        std::memcpy(dst, offs.data(), (size_t)(n + 1) * 4);
-        std::memcpy(dst + o_tok, blk_tok.data(), (size_t)(nblocks + 1) * 4);
-        std::memcpy(dst + o_doc, blk_doc.data(), (size_t)(nblocks + 1) * 4);
-        std::memcpy(dst + o_rid, row_id.data(), row_id.size() * 4);
-        std::memcpy(dst + o_rmeta, row_meta.data(), row_meta.size() * 4);
-    };
-    auto point = [&](const unsigned char* base) {
-        a.offsets = reinterpret_cast<const uint32_t*>(base);
-        a.blk_tok = reinterpret_cast<const uint32_t*>(base + o_tok);
-        a.blk_doc = reinterpret_cast<const uint32_t*>(base + o_doc);
-        a.row_id = reinterpret_cast<const int32_t*>(base + o_rid);
-        a.row_meta = reinterpret_cast<const uint32_t*>(base + o_rmeta);
-    };
+    auto fill = [&](unsigned char* dst) { pk.fill(dst, offs.data()); };
+    auto point = [&](const unsigned char* base) { pk.point(a, base); };
     if (pinned && docs_io_) {
         // the blocks read their rows in place from the pinned block (mapped into the device's address
         // space) and the pooled vectors land in it: no copy in either direction

@@ -33,6 +33,21 @@ struct BertBlob {
 };
 SearchError parse_bert_safetensors(const void* blob, uint64_t blob_len, float ln_eps, BertBlob* out);
 
+// The row blocks of the one-launch forward of short texts (bert_docs_w.hip): consecutive texts packed greedily into blocks of at most
+// 32 tokens, a block never splitting a text, and each block's 32 rows laid out so that it needs ONE read of the inputs: token id (-1 =
+// padding), rows of the block << 16 | position inside the text << 8 | the text's index among the block's non-empty texts.  The call's
+// single input block is [offsets | blk_tok | blk_doc | row_id | row_meta], in_bytes long (a multiple of 256).
+struct BertDocsPacking {
+    uint32_t n = 0, nblocks = 0;
+    std::vector<uint32_t> blk_tok, blk_doc, row_meta;
+    std::vector<int32_t> row_id;
+    size_t o_tok = 0, o_doc = 0, o_rid = 0, o_rmeta = 0, in_bytes = 0;
+    void fill(unsigned char* dst, const uint32_t* offs) const;           // the input block, for the offsets it was packed from
+    void point(BertDocsArgs& a, const unsigned char* base) const;        // the kernel's five input pointers into a copy at `base`
+};
+// ids: the call's tokens; offs [n + 1]: the call's offsets rebased to 0, every text at most 32 tokens; total = offs[n]
+BertDocsPacking bert_docs_pack(const int32_t* ids, const uint32_t* offs, uint32_t n, uint32_t total);
+
 class NativeEmbedder {
   public:
     ~NativeEmbedder();

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -1874,14 +1875,15 @@ fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float* x, const
 }
 
 namespace {
-// Device side of fsgpu_lab_bert_stage: uploads (as f32, as f16 through launch_bert_to_half, as fragment-order f16 through
-// launch_bert_pack_w) and outputs that sit between two guard bands of 64 rows.  The first failure sticks; every later step is skipped.
+// Device side of fsgpu_lab_bert_stage and fsgpu_lab_bert_short_stage: uploads (as f32, as f16 through launch_bert_to_half, as
+// fragment-order f16 through launch_bert_pack_w) and outputs that sit between two guard bands of 64 rows.  The first failure sticks; every later step is skipped.
 struct LabStage {
     static constexpr size_t kGuardRows = 64;
     static constexpr int kGuardByte = 0xA5;
     struct Out {
         unsigned char* base = nullptr;
         size_t rows = 0, cols = 0, elem = 0;
+        size_t slab_rows = 0;   // non-zero: rows is slabs x 32 workspace rows of which the first slab_rows of each slab go to the host
         float* host = nullptr;
         void* ptr() const { return base + kGuardRows * cols * elem; }
     };
@@ -1934,6 +1936,18 @@ struct LabStage {
         outs.push_back(o);
         return ok() ? o.ptr() : nullptr;
     }
+    // an input workspace of `slabs` x 32 rows of f32 (f16: rounded on the device) whose rows m..31 hold NaN: host [slabs][m][cols]
+    void* workspace(const float* src, size_t slabs, size_t m, size_t cols, bool half) {
+        std::vector<float> h(slabs * 32 * cols, std::numeric_limits<float>::quiet_NaN());
+        for (size_t sl = 0; sl < slabs; ++sl) std::memcpy(h.data() + sl * 32 * cols, src + sl * m * cols, m * cols * 4);
+        return half ? f16(h.data(), h.size()) : const_cast<float*>(f32(h.data(), h.size()));
+    }
+    // the four-slab output: [slabs][32][cols] f32, all of it guard bytes beforehand; rows m..31 of each slab must keep them
+    void* out_slabs(size_t slabs, size_t m, size_t cols, float* host) {
+        void* p = out(slabs * 32, cols, 4, host);
+        outs.back().slab_rows = m;
+        return p;
+    }
     void collect() {
         hip(hipStreamSynchronize(nullptr));
         for (const Out& o : outs) {
@@ -1944,7 +1958,15 @@ struct LabStage {
             if (!ok()) return;
             for (size_t i = 0; i < band; ++i)
                 if (h[i] != kGuardByte || h[band + body + i] != kGuardByte) guard_hit = true;
-            if (o.elem == 4) {
+            if (o.slab_rows) {
+                const size_t row = o.cols * o.elem;
+                for (size_t sl = 0; sl < o.rows / 32; ++sl) {
+                    const unsigned char* slab = h.data() + band + sl * 32 * row;
+                    std::memcpy(reinterpret_cast<unsigned char*>(o.host) + sl * o.slab_rows * row, slab, o.slab_rows * row);
+                    for (size_t i = o.slab_rows * row; i < 32 * row; ++i)
+                        if (slab[i] != kGuardByte) guard_hit = true;
+                }
+            } else if (o.elem == 4) {
                 std::memcpy(o.host, h.data() + band, body);
             } else {
                 const _Float16* s = reinterpret_cast<const _Float16*>(h.data() + band);
@@ -2134,6 +2156,158 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
         if (!s.e.ok()) return finish(s.e);
         if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
         if (s.guard_hit) return fail(FSGPU_ERR_DEVICE, "bert stage: a kernel wrote into a guard band of its output");
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_lab_bert_short_stage(int32_t device, const fsgpu_lab_bert_short_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_bert_short_args& a = *args;
+    const uint32_t st = a.stage, form = a.form;
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    if (st > FSGPU_LAB_BERT_DOCS) return bad("bert short stage: unknown stage");
+    const bool docs = st == FSGPU_LAB_BERT_DOCS;
+    if (form > (st == FSGPU_LAB_BERT_Q_ATTN ? 1u : st == FSGPU_LAB_BERT_Q_GEMM ? 2u : 0u)) return bad("bert short stage: unknown form");
+    if (!(docs ? fsgpu::bert_docs_w_supported((int)a.hidden, (int)a.inter, (int)a.heads)
+               : fsgpu::bert_query_path_supported((int)a.hidden, (int)a.inter, (int)a.heads)))
+        return bad("bert short stage: the short-text kernels are built for hidden 384, inter 1536, 12 heads");
+    const bool embeds = docs || (st == FSGPU_LAB_BERT_Q_ATTN && form == 0);
+    static const int n_in[4][3] = {{7, 7, 0}, {2, 7, 2}, {5, 0, 0}, {5, 0, 0}};
+    for (int i = 0; i < n_in[st][form]; ++i)
+        if (!a.in[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert short stage: missing input");
+    if (!a.out0) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert short stage: out0 is null");
+    const bool two_outs = st == FSGPU_LAB_BERT_Q_ATTN || (st == FSGPU_LAB_BERT_Q_GEMM && form == 1);
+    if (two_outs && !a.out1) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert short stage: out1 is null");
+    if (a.m == 0 || a.m > (docs ? (1u << 20) : 32u)) return bad("bert short stage: m must be in 1..=32 (DOCS: 1..=2^20)");
+    uint32_t max_seq = 0, min_seq = 0;
+    if (!lab_offsets(a.offsets, a.n_docs, a.m, &max_seq, &min_seq)) return bad("bert short stage: offsets must run from 0 to m");
+    if (docs && (max_seq > 32 || a.layers == 0 || a.layers > 6)) return bad("bert short stage: DOCS takes texts of at most 32 tokens and 1..=6 layers");
+    if (docs) {
+        if (!a.layer_in) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert short stage: layer_in is null");
+        for (uint32_t i = 0; i < a.layers * 12; ++i)
+            if (!a.layer_in[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert short stage: missing layer tensor");
+    }
+    if (embeds) {
+        if (!a.ids || (!docs && !a.positions) || a.vocab == 0 || a.max_pos == 0 || a.max_pos > 512)
+            return bad("bert short stage: embedding needs ids (, positions), vocab and max_pos in 1..=512");
+        for (uint32_t t = 0; t < a.m; ++t)
+            if (a.ids[t] < 0 || (uint32_t)a.ids[t] >= a.vocab || (!docs && (a.positions[t] < 0 || (uint32_t)a.positions[t] >= a.max_pos)))
+                return bad("bert short stage: token id or position out of range");
+        if (docs && max_seq > a.max_pos) return bad("bert short stage: text longer than max_pos");
+    }
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        const size_t m = a.m, H = a.hidden, I = a.inter;
+        const uint32_t* offs = static_cast<const uint32_t*>(s.raw(a.offsets, ((size_t)a.n_docs + 1) * 4));
+        if (!docs) {
+            // the argument block as NativeEmbedder::forward_query fills it
+            fsgpu::BertQueryArgs q{};
+            q.tokens = (int)a.m;
+            q.n_docs = (int)a.n_docs;
+            q.offsets = offs;
+            q.eps = a.eps;
+            q.attn_scale = a.scale;
+            // the pending add + LayerNorm of `slabs` partial slabs: in[0..4]
+            auto pending = [&](int slabs) {
+                q.x_in = static_cast<const float*>(s.workspace(a.in[0], 1, m, H, false));
+                q.parts = static_cast<const float*>(s.workspace(a.in[1], (size_t)slabs, m, H, false));
+                q.n_parts = slabs;
+                q.prev_bias = s.f32(a.in[2], H);
+                q.lnw = s.f32(a.in[3], H);
+                q.lnb = s.f32(a.in[4], H);
+            };
+            if (st == FSGPU_LAB_BERT_Q_ATTN) {
+                if (form == 0) {
+                    q.ids = static_cast<const int32_t*>(s.raw(a.ids, m * 4));
+                    q.positions = static_cast<const int32_t*>(s.raw(a.positions, m * 4));
+                    q.word = s.f32(a.in[0], (size_t)a.vocab * H);
+                    q.pos = s.f32(a.in[1], (size_t)a.max_pos * H);
+                    q.type0 = s.f32(a.in[2], H);
+                    q.lnw = s.f32(a.in[3], H);
+                    q.lnb = s.f32(a.in[4], H);
+                } else {
+                    pending(4);
+                }
+                q.w = static_cast<const _Float16*>(s.f16(a.in[5], 3 * H * H));
+                q.ldw = (int)H;
+                q.bias = s.f32(a.in[6], 3 * H);
+                q.out_h = static_cast<_Float16*>(s.out(m, H, 2, a.out0));
+                q.x_out = static_cast<float*>(s.out(m, H, 4, a.out1));
+                if (s.ok()) s.hip(fsgpu::launch_bert_q_qkv_attn(q, (int)a.heads, nullptr));
+            } else if (st == FSGPU_LAB_BERT_Q_GEMM && form == 0) {
+                q.a_h = static_cast<const _Float16*>(s.workspace(a.in[0], 1, m, H, true));
+                q.lda = (int)H;
+                q.w = static_cast<const _Float16*>(s.f16(a.in[1], H * H));
+                q.ldw = (int)H;
+                q.n = (int)H;
+                q.out_f32 = static_cast<float*>(s.out(m, H, 4, a.out0));
+                if (s.ok()) s.hip(fsgpu::launch_bert_q_gemm(q, 0, nullptr));
+            } else if (st == FSGPU_LAB_BERT_Q_GEMM && form == 1) {
+                pending(1);
+                q.w = static_cast<const _Float16*>(s.f16(a.in[5], I * H));
+                q.ldw = (int)H;
+                q.n = (int)I;
+                q.bias = s.f32(a.in[6], I);
+                q.out_h = static_cast<_Float16*>(s.out(m, I, 2, a.out0));
+                q.x_out = static_cast<float*>(s.out(m, H, 4, a.out1));
+                if (s.ok()) s.hip(fsgpu::launch_bert_q_gemm(q, 1, nullptr));
+            } else if (st == FSGPU_LAB_BERT_Q_GEMM) {
+                q.a_h = static_cast<const _Float16*>(s.workspace(a.in[0], 1, m, I, true));
+                q.lda = (int)I;
+                q.w = static_cast<const _Float16*>(s.f16(a.in[1], H * I));
+                q.ldw = (int)I;
+                q.n = (int)H;
+                q.out_f32 = static_cast<float*>(s.out_slabs(4, m, H, a.out0));
+                if (s.ok()) s.hip(fsgpu::launch_bert_q_gemm(q, 2, nullptr));
+            } else {
+                pending(4);
+                float* pooled = static_cast<float*>(s.out(a.n_docs, H, 4, a.out0));
+                if (s.ok()) s.hip(fsgpu::launch_bert_q_pool(q, pooled, nullptr));
+            }
+        } else {
+            // the argument block as NativeEmbedder::embed_docs fills it, over the embedder's own row blocks
+            const fsgpu::BertDocsPacking pk = fsgpu::bert_docs_pack(a.ids, a.offsets, a.n_docs, a.m);
+            std::vector<unsigned char> host(pk.in_bytes);
+            pk.fill(host.data(), a.offsets);
+            fsgpu::BertDocsArgs d{};
+            pk.point(d, static_cast<const unsigned char*>(s.raw(host.data(), host.size())));
+            d.word = s.f32(a.in[0], (size_t)a.vocab * H);
+            d.pos = s.f32(a.in[1], (size_t)a.max_pos * H);
+            d.type0 = s.f32(a.in[2], H);
+            d.emb_lnw = s.f32(a.in[3], H);
+            d.emb_lnb = s.f32(a.in[4], H);
+            std::vector<fsgpu::BertDocsLayer> table(a.layers);
+            for (uint32_t l = 0; l < a.layers; ++l) {
+                const float* const* t = a.layer_in + (size_t)l * 12;
+                fsgpu::BertDocsLayer& L = table[l];
+                L.qkv_wp = s.packed(t[0], 3 * (int)H, (int)H);
+                L.qkv_b = s.f32(t[1], 3 * H);
+                L.ao_wp = s.packed(t[2], (int)H, (int)H);
+                L.ao_b = s.f32(t[3], H);
+                L.ln1_w = s.f32(t[4], H);
+                L.ln1_b = s.f32(t[5], H);
+                L.i_wp = s.packed(t[6], (int)I, (int)H);
+                L.i_b = s.f32(t[7], I);
+                L.o_wp = s.packed(t[8], (int)H, (int)I);
+                L.o_b = s.f32(t[9], H);
+                L.ln2_w = s.f32(t[10], H);
+                L.ln2_b = s.f32(t[11], H);
+            }
+            d.layers = static_cast<const fsgpu::BertDocsLayer*>(s.raw(table.data(), table.size() * sizeof(fsgpu::BertDocsLayer)));
+            d.nlayers = (int)a.layers;
+            d.eps = a.eps;
+            d.attn_scale = a.scale;
+            d.out = static_cast<float*>(s.out(a.n_docs, H, 4, a.out0));
+            if (s.ok()) s.hip(fsgpu::launch_bert_docs_w(d, pk.nblocks, nullptr));
+        }
+        s.collect();
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (s.guard_hit) return fail(FSGPU_ERR_DEVICE, "bert short stage: a kernel wrote into a guard band of its output");
         return FSGPU_OK;
     });
 }

@@ -81,6 +81,41 @@ typedef struct fsgpu_lab_bert_stage_args {
     float *out0, *out1;
 } fsgpu_lab_bert_stage_args;
 fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_args *args);
+/* ONE stage of the two short-text forwards on host arrays, through the launcher the embedder calls and with the argument block filled
+ * as NativeEmbedder::forward_query / embed_docs fill it: for kernel-level tests against tests/encoder_short_ref.py.  MiniLM-L6 shape
+ * only (hidden 384, inter 1536, heads 12; anything else is FSGPU_ERR_INVALID_CONFIG, nothing launched; arguments are checked before a
+ * device is looked for).  f16 operands are rounded on the device, f16 outputs come back widened, every output lies between guard bands
+ * as for fsgpu_lab_bert_stage.
+ * Query stages (bert_query_kernels.hip): m tokens in 1..32, offsets [n_docs + 1] from 0 to m (empty texts allowed).  Workspaces are laid
+ * out as the product's: X [32][384], slabs [slab][32][384], ctx / inter [tokens][n]; rows m..31 of every INPUT workspace hold NaN; an
+ * output is its m rows; the four-slab output's whole 4 x 32-row region is prefilled with the guard byte and rows m..31 of each slab must
+ * keep it (else FSGPU_ERR_DEVICE, "guard band").
+ *   Q_ATTN  launch_bert_q_qkv_attn.  form 0 (embedding prologue): ids, positions [m]; in: word [vocab, 384], pos [max_pos, 384],
+ *           type0 [384], ln_w, ln_b, wqkv [1152, 384], bqkv [1152].  form 1 (pending add + LayerNorm of four slabs): in: x_in [m, 384],
+ *           parts [4, m, 384], prev_bias, ln_w, ln_b, wqkv, bqkv.  out0 = ctx [m, 384] (f16), out1 = x_out [m, 384] (f32)
+ *   Q_GEMM  launch_bert_q_gemm, form = its mode.  0: in: a [m, 384], w [384, 384]; out0 = one slab [m, 384] (f32, no bias).
+ *           1: in: x_in, slab [m, 384], prev_bias, ln_w, ln_b, w [1536, 384], bias [1536]; out0 = GELU tile [m, 1536] (f16), out1 = x_out.
+ *           2: in: a [m, 1536], w [384, 1536]; out0 = the four slabs [4, m, 384]
+ *   Q_POOL  launch_bert_q_pool.  in: x_in, parts [4, m, 384], prev_bias, ln_w, ln_b; out0 = [n_docs, 384]
+ * DOCS (bert_docs_w.hip): launch_bert_docs_w over `layers` in 1..6 layers; ids [m], offsets of texts of at most 32 tokens each (m >= 1),
+ * packed into row blocks by the embedder's own bert_docs_pack.  in: word, pos, type0, emb_ln_w, emb_ln_b; layer_in [layers][12]: wqkv
+ * [1152, 384], bqkv, wao [384, 384], bao, ln1_w, ln1_b, wi [1536, 384], bi, wo [384, 1536], bo, ln2_w, ln2_b (matrices rounded to f16
+ * and re-laid in fragment order as at model load).  out0 = pooled [n_docs, 384] */
+#define FSGPU_LAB_BERT_Q_ATTN 0
+#define FSGPU_LAB_BERT_Q_GEMM 1
+#define FSGPU_LAB_BERT_Q_POOL 2
+#define FSGPU_LAB_BERT_DOCS 3
+typedef struct fsgpu_lab_bert_short_args {
+    uint32_t stage, form;
+    uint32_t m, n_docs, hidden, inter, heads, layers, vocab, max_pos;
+    float eps, scale;
+    const uint32_t *offsets;
+    const int32_t *ids, *positions;
+    const float *in[8];
+    const float *const *layer_in;
+    float *out0, *out1;
+} fsgpu_lab_bert_short_args;
+fsgpu_status fsgpu_lab_bert_short_stage(int32_t device, const fsgpu_lab_bert_short_args *args);
 /* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,

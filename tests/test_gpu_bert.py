@@ -221,6 +221,50 @@ def test_one_launch_path_outlier_weights_and_large_calls(fa):
     check(whole[:16], ref.run(many[:16], 8))
 
 
+def short_text(rng, n):
+    if n == 0:
+        return []
+    if n == 1:
+        return [101]
+    return [101] + rng.integers(1000, 3000, n - 2).tolist() + [102]
+
+
+@pytest.mark.parametrize("family", ["random_weights", "heavy_tailed_weights"])
+def test_query_path_multi_text_calls_with_empty_texts(fa, family):
+    """Calls of at most 32 tokens in all (bert_query_kernels.hip) that hold several texts, empty ones at the start, in the middle and at
+    the end among them: the attention's text mask and the pooling's offsets, against the f32 C oracle; empty texts give zeros."""
+    from oracle import bert_oracle
+    rng = np.random.default_rng(61)
+    w = getattr(bert_oracle, family)(45, 3000, 384, 6, 1536)
+    m = fa.NativeEmbedder(w)
+    ref = bert_oracle.CForward(w, 6)
+    for lens in ([0, 5, 0, 27, 0], [0, 0, 1, 0, 31], [16, 0, 16], [15, 17, 0], [0, 17, 15], [3] + [0] * 17 + [1] + [0] * 20 + [7], [1] * 32):
+        batch = [short_text(rng, n) for n in lens]
+        assert sum(lens) <= 32 and len(lens) > 1
+        got = m.embed_batch_token_ids(batch)
+        check(got, ref.run(batch, 4))
+        assert np.all(got[[i for i, n in enumerate(lens) if n == 0]] == 0)
+    m.close()
+
+
+def test_one_launch_path_blocks_of_more_than_95_texts(fa):
+    """A row block keeps 96 text boundaries in LDS and reads further ones in place from the call's input block (bert_docs_w.hip, DOFF):
+    blocks of 95, 97, 202, 97 and 257 texts — empty texts next to non-empty ones — against the f32 C oracle."""
+    from oracle import bert_oracle
+    rng = np.random.default_rng(67)
+    w = bert_oracle.random_weights(29, 3000, 384, 6, 1536)
+    m = fa.NativeEmbedder(w)
+    ref = bert_oracle.CForward(w, 6)
+    for lens in ([32] + [0] * 94 + [10, 10, 10] + [0] * 5, [32] + [0] * 96 + [20, 12], [32] + [3] + [0] * 200 + [29],
+                 [32, 2] + [0] * 93 + [10, 10, 10], [32, 2] + [0] * 255 + [30]):
+        batch = [short_text(rng, n) for n in lens]
+        assert sum(lens) > 32 and max(lens) <= 32
+        got = m.embed_batch_token_ids(batch)
+        check(got, ref.run(batch, 4))
+        assert np.all(got[[i for i, n in enumerate(lens) if n == 0]] == 0)
+    m.close()
+
+
 def test_model_file_blob_gives_the_same_embedder_as_the_tensor_struct(fa, tmp_path):
     """fsgpu_bert_create_safetensors (NativeEmbedder::load -> parse_weights, native.rs:1359-1602): a safetensors file in the bare
     sentence-transformers key layout and one in the `bert.`-prefixed cross-encoder layout (with position_ids, pooler tensors and
