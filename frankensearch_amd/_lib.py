@@ -132,6 +132,10 @@ SIGNATURES = {
     "fsgpu_search_topk_classified": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), C.POINTER(_i32)]),
     "fsgpu_search_topk_int8_two_pass": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, C.POINTER(_u32)]),
     "fsgpu_search_hits": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_search_hits_batched": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_search_hits_batched_device_queries": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_search_hits_two_pass_batched": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_lab_index_wal_scores": (_i32, [_vp, _vp, _u32, _vp]),
     "fsgpu_gather_dot": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp]),
     "fsgpu_lab_sort_keys_desc": (_i32, [_i32, _vp, _u64, _u64, _vp]),
     "fsgpu_bench_fixture_device": (_i32, [_i32, _u64, _u64, _u32, _u32, C.c_float, _u64, _i32, _vp, _vp]),

@@ -1039,6 +1039,49 @@ fsgpu_status fsgpu_search_hits(fsgpu_index* idx, const float* query, uint32_t qu
     });
 }
 
+// search_hits for a batch: WAL merge, shadowing and dedup on the device (vector_index_hits.cpp, search_hits_kernels.hip)
+fsgpu_status fsgpu_search_hits_batched(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                       uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* out_fallbacks) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (nq && (!queries || !out_counts || (k && (!out_rows || !out_scores)))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.search_hits_batched(queries, nq, query_len, k, out_rows, out_scores, out_counts, out_fallbacks));
+    });
+}
+
+fsgpu_status fsgpu_search_hits_batched_device_queries(fsgpu_index* idx, const float* queries_dev, uint32_t nq, uint32_t query_len,
+                                                      uint32_t k, uint32_t* out_rows, float* out_scores, uint32_t* out_counts,
+                                                      uint32_t* out_fallbacks) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (nq && (!queries_dev || !out_counts || (k && (!out_rows || !out_scores)))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.search_hits_batched(queries_dev, nq, query_len, k, out_rows, out_scores, out_counts, out_fallbacks, true));
+    });
+}
+
+fsgpu_status fsgpu_search_hits_two_pass_batched(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                                uint32_t candidate_multiplier, uint32_t bits, uint32_t* out_rows, float* out_scores,
+                                                uint32_t* out_counts, uint32_t* out_fallbacks) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (nq && (!queries || !out_counts || (k && (!out_rows || !out_scores)))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.search_hits_two_pass_batched(queries, nq, query_len, k, candidate_multiplier, (int)bits, out_rows, out_scores,
+                                                             out_counts, out_fallbacks));
+    });
+}
+
+fsgpu_status fsgpu_lab_index_wal_scores(fsgpu_index* idx, const float* queries, uint32_t nq, float* out) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if (nq && (!queries || !out)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.lab_wal_scores(queries, nq, out));
+    });
+}
+
 fsgpu_status fsgpu_search_topk_int8_two_pass_batched(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_len,
                                                      uint32_t k, uint32_t candidate_multiplier, uint32_t* out_rows,
                                                      float* out_scores, uint32_t* out_counts, uint32_t* out_fallbacks) {

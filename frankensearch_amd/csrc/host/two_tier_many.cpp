@@ -133,14 +133,20 @@ ManyEngine::ManyEngine(const SyncTwoTierSearcher& s, uint32_t fusion_threads) : 
     qdim_ = fsgpu_bert_dimension(s_.bert_);
     // which calls answer a tier for a chunk: the batched forms of what search() calls per query (tier_hits): row-level searches when
     // the ids are synthetic or the fast tier runs the int8 two-pass; with doc-id tables the exact searches go through search_hits
-    // (WAL merge, shadowing, dedup) query by query, as search() does
+    // (WAL merge, shadowing, dedup): batched on a single index (fsgpu_search_hits_batched / _two_pass_batched), query by query on a
+    // sharded tier, as search() does
     fast_rowlevel_ = s_.cfg_.fast_tier_int8_multiplier != 0 || s_.cfg_.doc_id_mode != 0;
     quality_rowlevel_ = s_.cfg_.doc_id_mode != 0;
     // embeddings stay in device memory when the embedder sits on the tier's (root) device
     const int32_t fast_dev = s_.fast_.index ? fsgpu_index_device(s_.fast_.index) : fsgpu_sharded_device(s_.fast_.sharded, 0);
     const int32_t quality_dev = s_.quality_.index ? fsgpu_index_device(s_.quality_.index) : fsgpu_sharded_device(s_.quality_.sharded, 0);
-    fast_dev_ok_ = fast_rowlevel_ && fast_dev >= 0 && fsgpu_m2v_device(s_.m2v_) == fast_dev;
-    quality_dev_ok_ = !rescored_ && quality_rowlevel_ && quality_dev >= 0 && fsgpu_bert_device(s_.bert_) == quality_dev;
+    // a single-index tier with doc-id tables: the batched search_hits (fsgpu_search_hits_batched: device queries; the two-pass form
+    // fsgpu_search_hits_two_pass_batched takes host queries); a sharded tier keeps the per-query loop
+    fast_hits_batched_ = s_.cfg_.doc_id_mode == 0 && s_.fast_.index != nullptr;
+    quality_hits_batched_ = s_.cfg_.doc_id_mode == 0 && s_.quality_.index != nullptr;
+    const bool fast_takes_dev = fast_hits_batched_ ? s_.cfg_.fast_tier_int8_multiplier == 0 : fast_rowlevel_;
+    fast_dev_ok_ = fast_takes_dev && fast_dev >= 0 && fsgpu_m2v_device(s_.m2v_) == fast_dev;
+    quality_dev_ok_ = !rescored_ && (quality_rowlevel_ || quality_hits_batched_) && quality_dev >= 0 && fsgpu_bert_device(s_.bert_) == quality_dev;
     fast_dev_ = fast_dev;
     quality_dev_ = quality_dev;
     for (int i = 0; i < kSlots; ++i) free_slots_.push_back(i);
@@ -303,11 +309,17 @@ void ManyEngine::embed_stage(bool fast) {
 }
 
 // One tier's answer for a chunk: rows / scores / counts [n, fetch] from device or host vectors.
-fsgpu_status ManyEngine::tier_search(const Tier& tier, bool rowlevel, uint32_t int8_mult, const float* vec_dev, const float* vec_host, uint32_t n,
+fsgpu_status ManyEngine::tier_search(const Tier& tier, bool rowlevel, bool hits_batched, uint32_t int8_mult, const float* vec_dev, const float* vec_host, uint32_t n,
                                      uint32_t dim, uint32_t fetch, uint32_t* rows, float* scores, uint32_t* counts, uint32_t* fb, std::string* detail) {
     fsgpu_status st = FSGPU_OK;
     *fb = 0;
-    if (!rowlevel) {   // doc-id tables + an exact search: search_hits per query (WAL merge, shadowing, dedup), as search() does
+    if (hits_batched) {   // doc-id tables on one index: WAL merge, shadowing and dedup for the whole chunk on the device
+        if (int8_mult)
+            st = fsgpu_search_hits_two_pass_batched(tier.index, vec_host, n, dim, fetch, int8_mult, 8, rows, scores, counts, fb);
+        else
+            st = vec_dev ? fsgpu_search_hits_batched_device_queries(tier.index, vec_dev, n, dim, fetch, rows, scores, counts, fb)
+                         : fsgpu_search_hits_batched(tier.index, vec_host, n, dim, fetch, rows, scores, counts, fb);
+    } else if (!rowlevel) {   // doc-id tables + an exact search on a sharded tier: search_hits per query, as search() does
         for (uint32_t i = 0; i < n && st == FSGPU_OK; ++i)
             st = tier.search_hits(vec_host + (size_t)i * dim, dim, fetch, rows + (size_t)i * fetch, scores + (size_t)i * fetch, &counts[i]);
     } else if (tier.index) {
@@ -335,9 +347,9 @@ void ManyEngine::search_stage(bool fast) {
         fsgpu_status st = FSGPU_OK;
         const auto b0 = clk::now();
         if (c->status.load() == FSGPU_OK) {
-            st = fast ? tier_search(s_.fast_, fast_rowlevel_, s_.cfg_.fast_tier_int8_multiplier, c->fast_on_dev ? slots_[c->slot].f : nullptr,
+            st = fast ? tier_search(s_.fast_, fast_rowlevel_, fast_hits_batched_, s_.cfg_.fast_tier_int8_multiplier, c->fast_on_dev ? slots_[c->slot].f : nullptr,
                                     c->fvec.data(), c->n, fdim_, c->fetch, c->f_rows.data(), c->f_scores.data(), c->f_counts.data(), &fb, &detail)
-                      : tier_search(s_.quality_, quality_rowlevel_, 0, c->quality_on_dev ? slots_[c->slot].q : nullptr, c->qvec.data(), c->n, qdim_,
+                      : tier_search(s_.quality_, quality_rowlevel_, quality_hits_batched_, 0, c->quality_on_dev ? slots_[c->slot].q : nullptr, c->qvec.data(), c->n, qdim_,
                                     c->fetch, c->q_rows.data(), c->q_scores.data(), c->q_counts.data(), &fb, &detail);
         }
         const auto b1 = clk::now();

@@ -187,7 +187,7 @@ class ManyEngine {
     void embed_stage(bool fast);
     void search_stage(bool fast);
     void rescore_stage();
-    fsgpu_status tier_search(const Tier& tier, bool rowlevel, uint32_t int8_mult, const float* vec_dev, const float* vec_host, uint32_t n, uint32_t dim,
+    fsgpu_status tier_search(const Tier& tier, bool rowlevel, bool hits_batched, uint32_t int8_mult, const float* vec_dev, const float* vec_host, uint32_t n, uint32_t dim,
                              uint32_t fetch, uint32_t* rows, float* scores, uint32_t* counts, uint32_t* fb, std::string* detail);
     void push_tasks(Chunk* c, bool final);
     void final_part_ready(Chunk* c);
@@ -199,6 +199,7 @@ class ManyEngine {
     const SyncTwoTierSearcher& s_;
     uint32_t n_workers_ = 0, fdim_ = 0, qdim_ = 0;
     bool rescored_ = false, fast_rowlevel_ = false, quality_rowlevel_ = false, fast_dev_ok_ = false, quality_dev_ok_ = false;
+    bool fast_hits_batched_ = false, quality_hits_batched_ = false;   // doc-id tables on a single index: the batched search_hits answers the tier
     int32_t fast_dev_ = -1, quality_dev_ = -1;
     Slot slots_[kSlots];
     // stage queues + free slots

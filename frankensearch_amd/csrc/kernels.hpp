@@ -539,4 +539,35 @@ struct KnnEmitArgs {
 };
 hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
 
+// search_hits_kernels.hip: the WAL half and the resolve step of the batched search_hits (vector_index_hits.cpp)
+constexpr uint32_t kHitsMaxK = 256;
+struct WalTopkArgs {
+    const float* wal;        // [W, dim] f32 mirror of the resident WAL embeddings
+    const float* queries;    // [nq, dim] f32
+    uint32_t nq, W, dim;
+    uint32_t kw;             // entries kept per query: min(k, W), 1 .. kHitsMaxK
+    uint32_t nrows;          // WAL entry w is packed as (score, nrows + w): it sorts behind every main row of equal score
+    int32_t hreduce;         // FSGPU_HREDUCE_*
+    u64* out_packed;         // nullable: [nq, kw] best first, kEmpty padded; non-finite scores are skipped (search.rs:1466-1470)
+    float* out_scores;       // nullable (lab): [nq, W] every score as computed
+};
+// false: one query of this dimension and its candidate buffers do not fit the LDS (the caller takes the per-query path)
+bool wal_topk_supported(uint32_t dim, uint32_t kw);
+hipError_t launch_wal_topk(const WalTopkArgs& args, hipStream_t stream);
+struct ResolveHitsArgs {
+    const uint32_t* main_rows;    // [nq, k] best first (the batched search's device output)
+    const float* main_scores;     // [nq, k]
+    const uint32_t* main_counts;  // [nq]
+    const u64* wal_packed;        // [nq, kw]; unused when kw == 0
+    const u64* live;              // nullable: bit r set = main row r live
+    const u64* shadowed;          // nullable: bit r set = main row r's doc id has a resident WAL entry
+    const uint32_t* main_class;   // [nrows] doc-id class of a main row: the first row with the same id bytes
+    const uint32_t* wal_class;    // [W] ... of a WAL entry: its main row's class, else nrows + the first WAL index with the id
+    uint32_t nq, k, kw, nrows;
+    uint32_t* out_rows;           // [nq, k] compacted, zero padded
+    float* out_scores;            // [nq, k]
+    uint32_t* out_counts;         // [nq]
+};
+hipError_t launch_resolve_hits(const ResolveHitsArgs& args, hipStream_t stream);
+
 }  // namespace fsgpu

@@ -67,7 +67,7 @@ VectorIndex::~VectorIndex() {
                             &ws_counts_, &ws_keys_a_, &ws_keys_b_, &ws_sort_tmp_, &ws_gather_rows_, &ws_gather_out_,
                             &i8_slab_, &n4_slab_, &i8_max_, &ws_i8_query_, &ws_cand_packed_, &ws_cand_rows_, &ws_cand_scores_,
                             &mf_max_norm_, &mf_qh_, &mf_delta_, &mf_tau_, &mf_cand_, &mf_dense_, &mf_sel_,
-                            &mf_fallback_, &mf_fallback2_, &mf_spill_, &mf_io_, &mf_io2_, &ws_out_, &i8_stats_, &n4u_slab_, &mf_cand_count_, &ws_pairs_,
+                            &mf_fallback_, &mf_fallback2_, &mf_spill_, &mf_io_, &mf_io2_, &ws_out_, &hits_main_class_, &hits_wal_, &hits_wal_class_, &hits_shadow_, &ws_hits_, &i8_stats_, &n4u_slab_, &mf_cand_count_, &ws_pairs_,
                             &i8f_slab_, &i8f_max_, &i8f_stats_, &rot_mat_, &rot_q_, &ws_mmr_in_, &ws_mmr_out_, &ws_mmr_sims_, &ws_mmr_vec_, &ws_hub_q_, &ws_hub_out_, &ws_hub_topk_, &ws_knn_[0], &ws_knn_[1]})
         b->release();
     if (mf_flags_host_) (void)hipHostFree(mf_flags_host_);
@@ -128,6 +128,7 @@ SearchError VectorIndex::init_device(int device, uint32_t dim, uint64_t nrows, c
 SearchError VectorIndex::set_live_bitmap(const uint64_t* live) {
     if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
+    invalidate_hits_state(false);
     if (!live) {
         live_dev_ = nullptr;
         live_host_.clear();
@@ -622,6 +623,7 @@ SearchError VectorIndex::soft_delete(const char* doc_id, uint32_t len, int32_t* 
                               [&](const WalEntry& e) { return e.doc_id.size() == len && std::memcmp(e.doc_id.data(), doc_id, len) == 0; }),
                wal_.end());
     if (wal_.size() != before) *deleted = 1;
+    invalidate_hits_state(false);   // (erased entries shift the WAL indices search_hits_batched's tables are keyed by)
     return ok();
 }
 

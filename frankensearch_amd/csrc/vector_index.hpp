@@ -142,6 +142,18 @@ class VectorIndex {
     // rows, host merge of the resident WAL entries, WAL shadowing and doc-id dedup.  Needs a doc-id table.
     SearchError search_hits(const float* query, uint32_t query_len, uint32_t k, uint32_t* out_rows, float* out_scores,
                             uint32_t* out_count);
+    // search_hits for nq queries (vector_index_hits.cpp, search_hits_kernels.hip): the batched search's main rows stay on the device,
+    // wal_topk_kernel scores a device mirror of the WAL, resolve_hits_kernel merges, shadows and dedups by doc-id class.  Same rows,
+    // score bits and counts as search_hits per query.  *fallbacks: queries answered per query (k = 0, k > 256, >= 2^32 rows + WAL
+    // entries) or whose main rows the batched search took from the exact kernels.
+    SearchError search_hits_batched(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t* out_rows,
+                                    float* out_scores, uint32_t* out_counts, uint32_t* fallbacks, bool queries_on_device = false);
+    // search_top_k_{int8,4bit}_two_pass for nq queries on an index with a doc-id table: search_hits_batched when the per-query call
+    // takes the exact search (resident WAL, F32 slab, k = 0, no rows), else the row-level batched two-pass + the dedup on the device
+    SearchError search_hits_two_pass_batched(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t multiplier,
+                                             int bits, uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* fallbacks);
+    // lab: wal_topk_kernel's score of every resident WAL entry, out [nq, wal_record_count()]
+    SearchError lab_wal_scores(const float* queries, uint32_t nq, float* out);
     // VectorIndex::search_top_k_int8_two_pass (search.rs:514-661): int8 pass-1 over the lazily built int8 slab,
     // exact f16 rescore of the k*multiplier candidates; falls back to the exact search when a WAL is resident.
     SearchError search_top_k_int8_two_pass(const float* query, uint32_t query_len, uint32_t k, uint32_t multiplier,
@@ -421,6 +433,18 @@ class VectorIndex {
     DeviceBuffer ws_mmr_in_, ws_mmr_out_, ws_mmr_sims_, ws_mmr_vec_;   // mmr_rerank_rows: inputs (one copy down), order | counts, matrix, staged rows
     DeviceBuffer ws_hub_q_, ws_hub_out_, ws_hub_topk_;   // compute_query_hubness: the sample, the table, the selected sims (lab)
     DeviceBuffer ws_knn_[2];   // build_knn_graph: per step in flight  queries | sources | hit rows | hit scores | counts | out rows | out sims
+    // search_hits_batched: the doc-id classes of the main rows (dropped with the record table: compact / vacuum); the f32 mirror of
+    // the WAL, its entries' classes and the shadowed-row bitmap (dropped by every change of the WAL or the tombstones); one block
+    // for a call's  queries | main rows | scores | counts | WAL lists | out rows | scores | counts
+    DeviceBuffer hits_main_class_, hits_wal_, hits_wal_class_, hits_shadow_, ws_hits_;
+    bool hits_main_ready_ = false, hits_wal_ready_ = false;
+    void invalidate_hits_state(bool main_too) {
+        hits_wal_ready_ = false;
+        if (main_too) hits_main_ready_ = false;
+    }
+    SearchError ensure_hits_state();
+    SearchError hits_per_query(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t* out_rows, float* out_scores,
+                               uint32_t* out_counts, uint32_t* fallbacks, bool queries_on_device, uint32_t multiplier, int bits);
     bool i8_ready_ = false, n4_ready_ = false, i8_stats_ready_ = false, n4u_ready_ = false;
     bool quant_max_ready_ = false;   // i8_max_ holds a corpus-wide max-abs handed in by a sharded index: the quantisers keep it
     u64* tp_approx_out_ = nullptr;   // two_pass_candidates_device: where the batch in flight leaves its candidate pairs

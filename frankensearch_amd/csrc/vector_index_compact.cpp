@@ -138,6 +138,7 @@ SearchError VectorIndex::wal_append_batch(uint32_t n, const char* const* doc_ids
         const float* v = vectors + (size_t)e * dim_;
         wal_.push_back(WalEntry{std::move(id), std::vector<float>(v, v + dim_)});
     }
+    invalidate_hits_state(false);   // the WAL mirror, its classes and the shadowed rows of search_hits_batched
     return ok();
 }
 
@@ -496,6 +497,7 @@ SearchError VectorIndex::lab_attach_synthetic_doc_ids() {
     }
     doc_offsets_[(size_t)nrows_] = nrows_ * kLen;
     embedder_id_ = "bench";
+    invalidate_hits_state(true);
     return ok();
 }
 
@@ -513,6 +515,7 @@ void VectorIndex::drop_derived_state() {
     mf_pass_parity_ = 0;
     views_.clear();
     replicas_.clear();
+    invalidate_hits_state(true);   // search_hits_batched: the classes number rows of the old record table
 }
 
 }  // namespace fsgpu

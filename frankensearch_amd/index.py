@@ -321,6 +321,46 @@ class VectorIndex:
         rows, scores, counts = self.search_batch(q, limit, filter)
         return [VectorHit(int(rows[0, i]), float(scores[0, i])) for i in range(int(counts[0]))]
 
+    def search_hits_batched_raw(self, queries, limit: int, two_pass: Optional[Tuple[int, int]] = None, queries_ptr: Optional[int] = None,
+                                nq: Optional[int] = None):
+        """fsgpu_search_hits_batched (two_pass = (candidate_multiplier, bits): fsgpu_search_hits_two_pass_batched; queries_ptr: the
+        queries are nq rows in device memory, fsgpu_search_hits_batched_device_queries) -> (rows [nq, limit], scores, counts, fallbacks)."""
+        L = _lib.lib()
+        if queries_ptr is None:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            if q.ndim == 1:
+                q = q[None, :]
+            nq, qlen, qp = q.shape[0], q.shape[1], _ptr(q)
+        else:
+            qlen, qp = self.dimension(), queries_ptr
+        rows = np.full((nq, max(limit, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.full((nq, max(limit, 1)), np.nan, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        fb = C.c_uint32()
+        if two_pass is not None:
+            check(L.fsgpu_search_hits_two_pass_batched(self._h, qp, nq, qlen, limit, two_pass[0], two_pass[1], _ptr(rows), _ptr(scores),
+                                                       _ptr(counts), C.byref(fb)))
+        elif queries_ptr is not None:
+            check(L.fsgpu_search_hits_batched_device_queries(self._h, qp, nq, qlen, limit, _ptr(rows), _ptr(scores), _ptr(counts), C.byref(fb)))
+        else:
+            check(L.fsgpu_search_hits_batched(self._h, qp, nq, qlen, limit, _ptr(rows), _ptr(scores), _ptr(counts), C.byref(fb)))
+        return rows[:, :limit], scores[:, :limit], counts, fb.value
+
+    def _hit_lists(self, rows, scores, counts) -> List[List[VectorHit]]:
+        return [[VectorHit(int(rows[q, i]), float(scores[q, i]), self.doc_id_at(int(rows[q, i]))) for i in range(int(counts[q]))]
+                for q in range(rows.shape[0])]
+
+    def search_hits_batched(self, queries: np.ndarray, limit: int) -> List[List[VectorHit]]:
+        """search_top_k (resident WAL, shadowing, doc-id dedup) for a batch of queries in one call: per query the hits of
+        search_top_k(query, limit).  Needs a doc-id table."""
+        rows, scores, counts, _ = self.search_hits_batched_raw(queries, limit)
+        return self._hit_lists(rows, scores, counts)
+
+    def search_hits_two_pass_batched(self, queries: np.ndarray, k: int, candidate_multiplier: int = 3, bits: int = 8) -> List[List[VectorHit]]:
+        """search_top_k_int8_two_pass (bits = 8) / search_top_k_4bit_two_pass (bits = 4) for a batch on an index with a doc-id table."""
+        rows, scores, counts, _ = self.search_hits_batched_raw(queries, k, two_pass=(candidate_multiplier, bits))
+        return self._hit_lists(rows, scores, counts)
+
     def search_top_k_classified(self, query: Sequence[float], limit: int) -> ClassifiedHits:
         """search.rs:227-261"""
         q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)

@@ -355,6 +355,31 @@ fsgpu_status fsgpu_search_topk_classified(fsgpu_index *idx, const float *query, 
  * record_count + wal index.  out_* hold up to k entries. */
 fsgpu_status fsgpu_search_hits(fsgpu_index *idx, const float *query, uint32_t query_len, uint32_t k,
                                uint32_t *out_rows, float *out_scores, uint32_t *out_count);
+/* fsgpu_search_hits for nq queries: out_rows / out_scores [nq, k], out_counts [nq] (<= k; may be shorter after shadowing / dedup,
+ * exactly as the per-query call).  WAL hits report the virtual row record_count + wal index.  The main rows come from the batched
+ * matrix-core search and stay in device memory; the resident WAL is scored by wal_topk_kernel against a device mirror of its
+ * embeddings (dot_product_f32_f32, the handle's hreduce mode) and resolve_hits_kernel merges, shadows and dedups by doc-id CLASS
+ * (doc ids are compared as bytes once, when the tables are built; any change of the WAL, the tombstones or the slab rebuilds them).
+ * Rows, score bits and counts equal the per-query call's.  *out_fallbacks (may be NULL) counts the queries answered through the
+ * per-query call — ALL of them for k = 0, k > 256, record_count + wal count >= 2^32, a dimension whose single query does not fit the
+ * WAL kernel's LDS (beyond ~32,000), and a handle whose main rows are not its own slab from row 0 (the catalog of a row-sharded
+ * index, a shard with a row base) — else those the batched search itself answered by fallback (their main rows came from the exact
+ * kernels: same bits; the WAL and resolve steps still ran on the device).  A failed kernel launch is FSGPU_ERR_DEVICE, never a
+ * fallback.  An index without a doc-id table is FSGPU_ERR_INVALID_CONFIG, as in fsgpu_search_hits.  Refused while a begun batched
+ * search is outstanding. */
+fsgpu_status fsgpu_search_hits_batched(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                       uint32_t *out_rows, float *out_scores, uint32_t *out_counts, uint32_t *out_fallbacks);
+/* the same with the queries in device memory (where fsgpu_bert_embed_device / fsgpu_m2v_embed_device left them); host results */
+fsgpu_status fsgpu_search_hits_batched_device_queries(fsgpu_index *idx, const float *queries_dev, uint32_t nq, uint32_t query_len,
+                                                      uint32_t k, uint32_t *out_rows, float *out_scores, uint32_t *out_counts,
+                                                      uint32_t *out_fallbacks);
+/* search_top_k_int8_two_pass / _4bit_two_pass (search.rs:514-661, 876-946) for a batch on an index WITH a doc-id table: with a
+ * resident WAL the reference falls back to the exact search (search.rs:579-585) -> fsgpu_search_hits_batched; otherwise the
+ * row-level batched two-pass, then resolve_hits' dedup on the device.  bits = 8 or 4.  Identical per query to
+ * fsgpu_search_topk_{int8,4bit}_two_pass. */
+fsgpu_status fsgpu_search_hits_two_pass_batched(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                                uint32_t candidate_multiplier, uint32_t bits, uint32_t *out_rows, float *out_scores,
+                                                uint32_t *out_counts, uint32_t *out_fallbacks);
 /* VectorIndex::search_top_k_int8_two_pass(query, k, candidate_multiplier) (search.rs:514-661) — the reference's
  * production default for the fast tier (two_tier.rs:1332-1337, multiplier 3): pass 1 scans a lazily built int8
  * slab (one corpus-wide max-abs scale, simd.rs:1865-1886) with the integer-exact dot and keeps the top

@@ -136,6 +136,10 @@ fsgpu_status fsgpu_lab_index_last_rewrite(fsgpu_index *idx, double *out_ms5, uin
 /* Gives an index made from a bare slab (fsgpu_index_create / _create_device) a doc-id table: the ids "doc-000000000", ... assigned so
  * that the rows as they stand are in (hash, doc id) order.  For measurements of the write path on a generated corpus. */
 fsgpu_status fsgpu_lab_index_attach_synthetic_doc_ids(fsgpu_index *idx);
+/* The arithmetic of wal_topk_kernel (fsgpu_search_hits_batched) on its own: out[q * W + w] = the kernel's dot_product_f32_f32 of
+ * resident WAL entry w with host query q, W = fsgpu_index_wal_record_count, non-finite scores included.  Builds the device
+ * mirror of the WAL if need be. */
+fsgpu_status fsgpu_lab_index_wal_scores(fsgpu_index *idx, const float *queries, uint32_t nq, float *out);
 /* The yardstick of the copy kernel: `reps` hipMemcpyDtoD of `bytes` between two fresh buffers, each timed by events (ms). */
 fsgpu_status fsgpu_lab_device_copy_ms(int32_t device, uint64_t bytes, uint32_t reps, double *out_ms);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */

@@ -108,7 +108,10 @@ fsgpu_status fshost_two_tier_search(fshost_two_tier *s, const uint32_t *fast_tok
  * Results: those of fshost_two_tier_search on the same tier answers; the tier answers are bit-identical to the per-query searches'
  * for identical query vectors; the Model2Vec vectors are bit-identical whatever the batch; a text's MiniLM vector is within the
  * encoder's tolerance (cos >= 0.999, 2e-3) of its single-text embedding (the encoder picks kernels by batch shape).
- * doc_id_mode 0 (FSVI doc-id tables): exact tier searches go through fsgpu_search_hits query by query, as the per-query flow does.
+ * doc_id_mode 0 (FSVI doc-id tables): a single-index tier is answered by fsgpu_search_hits_batched (exact) or
+ * fsgpu_search_hits_two_pass_batched (fast_tier_int8_multiplier != 0) — WAL merge, shadowing and dedup for the whole chunk on the
+ * device, the answers of fsgpu_search_hits per query; a sharded tier goes through fsgpu_sharded_search_hits query by query.
+ * fast_fallbacks / quality_fallbacks report those calls' fallback counts.
  * quality_pool FSHOST_POOL_RESCORED: phase 1 is the gather of quality_scores_for_hits per query on the fusion threads. */
 typedef struct fshost_many_result {
     double wall_seconds, queries_per_sec;
