@@ -9,12 +9,14 @@ from .errors import (DeviceError, DimensionMismatch, IndexCorrupted, IndexVersio
                      ModelLoadFailed, NoDevice, SearchError)
 from .index import (ClassifiedHits, CompactionStats, VacuumStats, NativeShardedIndex, VectorHit, VectorIndex, encode_f32_to_f16, pack_bitmap, widen_f16_to_f32,
                     write_fsvi)
+from .index_builder import IndexBuilder, IndexBuildStats
+from .two_tier import TwoTierIndexBuilder
 from .hubness import HubnessConfig, apply_hubness_penalty, compute_query_hubness
 from .smooth import SmoothConfig, neighbor_smooth, neighbor_smooth_ranked
 from .mmr import MmrConfig, mmr_rerank, mmr_step
 from .rerank import PURE_REORDER, RRF_COMBINE, NativeReranker, RerankCandidate, RerankScore, rerank_step
 
-__all__ = ["write_fsvi", "VectorIndex", "NativeShardedIndex", "VectorHit", "ClassifiedHits", "CompactionStats", "VacuumStats", "Model2VecEmbedder", "NativeEmbedder", "NativeReranker",
+__all__ = ["write_fsvi", "IndexBuilder", "IndexBuildStats", "TwoTierIndexBuilder", "VectorIndex", "NativeShardedIndex", "VectorHit", "ClassifiedHits", "CompactionStats", "VacuumStats", "Model2VecEmbedder", "NativeEmbedder", "NativeReranker",
            "RerankCandidate", "RerankScore", "rerank_step", "MmrConfig", "mmr_rerank", "mmr_step", "HubnessConfig", "compute_query_hubness", "apply_hubness_penalty", "SmoothConfig", "neighbor_smooth", "neighbor_smooth_ranked", "PURE_REORDER", "RRF_COMBINE", "SearchError", "DimensionMismatch",
            "InvalidConfig", "IndexCorrupted", "IndexVersionMismatch", "IoError", "DeviceError", "NoDevice", "ModelLoadFailed",
            "encode_f32_to_f16", "widen_f16_to_f32", "pack_bitmap", "_lib"]

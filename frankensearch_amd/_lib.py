@@ -171,6 +171,14 @@ SIGNATURES = {
     "fsgpu_reranker_device": (_i32, [_vp]),
     "fsgpu_reranker_max_length": (_u32, [_vp]),
     "fsgpu_reranker_score": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "fsgpu_index_builder_create": (_i32, [_i32, _u32, C.c_char_p, C.c_char_p, _vp, C.POINTER(_vp)]),   # (options: index_builder._Options)
+    "fsgpu_index_builder_destroy": (None, [_vp]),
+    "fsgpu_index_builder_record_count": (_u64, [_vp]),
+    "fsgpu_index_builder_add": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_u64)]),
+    "fsgpu_index_builder_add_device": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, C.POINTER(_u64)]),
+    "fsgpu_index_builder_add_bert": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "fsgpu_index_builder_add_m2v": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "fsgpu_index_builder_finish": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), _vp]),   # (stats: index_builder._Stats)
     "fsgpu_rerank_apply": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, C.c_float, _vp]),
     "fsgpu_mmr_config_default": (_i32, [_vp]),
     "fsgpu_mmr_rerank": (_i32, [_vp, _vp, _vp, _u32, _u32, C.c_double, _u32, _vp, C.POINTER(_u32), _vp]),

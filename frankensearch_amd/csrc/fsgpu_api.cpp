@@ -19,6 +19,7 @@
 #include "bert_embedder.hpp"
 #include "bert_reranker.hpp"
 #include "coalescer.hpp"
+#include "index_builder.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
 #include "two_tier_index.hpp"
@@ -94,6 +95,9 @@ struct fsgpu_bert {
 
 struct fsgpu_reranker {
     fsgpu::NativeReranker impl;
+};
+struct fsgpu_index_builder {
+    fsgpu::IndexBuilder impl;
 };
 namespace {
 
@@ -2528,6 +2532,102 @@ fsgpu_status fsgpu_reranker_score(fsgpu_reranker* m, const int32_t* ids, const i
                                   float* out_logits, float* out_scores) {
     if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "reranker is null");
     return guarded([&]() -> fsgpu_status { return finish(m->impl.score(ids, type_ids, offsets, n, out_logits, out_scores)); });
+}
+
+// ---- the index builder (index_builder.cpp): VectorIndexWriter::write_record + finish, lib.rs:3607-3672, 3752-3943 ----
+
+fsgpu_status fsgpu_index_builder_create(int32_t device, uint32_t dim, const char* embedder_id, const char* embedder_revision,
+                                        const fsgpu_index_builder_options* options, fsgpu_index_builder** out) {
+    if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    *out = nullptr;
+    fsgpu::IndexBuilder::Options o;
+    if (options) {   // (judged before a device is looked for)
+        if (options->quantization > 1) return fail(FSGPU_ERR_INVALID_CONFIG, "quantization must be 0 (F32) or 1 (F16)");
+        if (options->compaction_gen > 255) return fail(FSGPU_ERR_INVALID_CONFIG, "compaction_gen must fit in a byte");
+        if (options->reject_duplicates > 1) return fail(FSGPU_ERR_INVALID_CONFIG, "reject_duplicates must be 0 or 1");
+        for (uint32_t r : options->reserved)
+            if (r != 0) return fail(FSGPU_ERR_INVALID_CONFIG, "reserved option words must be 0");
+        o.quantization = (uint8_t)options->quantization;
+        o.compaction_gen = (uint8_t)options->compaction_gen;
+        o.reject_duplicates = options->reject_duplicates == 1;
+        o.chunk_rows = options->chunk_rows;
+        o.reserve_rows = options->reserve_rows;
+    }
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_index_builder>();
+        fsgpu::SearchError e = h->impl.init(device, dim, embedder_id, embedder_revision, o);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_index_builder_destroy(fsgpu_index_builder* b) { delete b; }
+uint64_t fsgpu_index_builder_record_count(const fsgpu_index_builder* b) { return b ? b->impl.record_count() : 0; }
+
+fsgpu_status fsgpu_index_builder_add(fsgpu_index_builder* b, uint64_t n, const char* const* doc_ids, const uint32_t* doc_id_lens,
+                                     const float* vectors, uint32_t vector_len, uint64_t* out_bad_row) {
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    return guarded([&]() -> fsgpu_status {
+        return finish(b->impl.add(n, doc_ids, doc_id_lens, vectors, vector_len, false, nullptr, out_bad_row));
+    });
+}
+
+fsgpu_status fsgpu_index_builder_add_device(fsgpu_index_builder* b, uint64_t n, const char* const* doc_ids, const uint32_t* doc_id_lens,
+                                            const float* vectors_dev, uint32_t vector_len, void* hip_stream, uint64_t* out_bad_row) {
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    return guarded([&]() -> fsgpu_status {
+        return finish(b->impl.add(n, doc_ids, doc_id_lens, vectors_dev, vector_len, true, static_cast<hipStream_t>(hip_stream), out_bad_row));
+    });
+}
+
+fsgpu_status fsgpu_index_builder_add_bert(fsgpu_index_builder* b, fsgpu_bert* m, const int32_t* ids, const uint32_t* offsets, uint32_t n,
+                                          const char* const* doc_ids, const uint32_t* doc_id_lens, uint64_t* out_bad_row) {
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
+    return guarded([&]() -> fsgpu_status {
+        // (the call fsgpu_bert_embed_device makes, into the builder's own buffer)
+        auto embed = [&](float* out_dev) { return m->impl.embed_batch(ids, offsets, n, nullptr, out_dev); };
+        return finish(b->impl.add_embedded(embed, m->impl.device(), m->impl.dimension(), n, doc_ids, doc_id_lens, out_bad_row));
+    });
+}
+
+fsgpu_status fsgpu_index_builder_add_m2v(fsgpu_index_builder* b, fsgpu_m2v* m, const uint32_t* ids, const uint32_t* offsets, uint32_t n,
+                                         const char* const* doc_ids, const uint32_t* doc_id_lens, uint64_t* out_bad_row) {
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
+    return guarded([&]() -> fsgpu_status {
+        auto embed = [&](float* out_dev) { return m->impl.embed_batch(ids, offsets, n, nullptr, out_dev); };
+        return finish(b->impl.add_embedded(embed, m->impl.device(), m->impl.dimension(), n, doc_ids, doc_id_lens, out_bad_row));
+    });
+}
+
+fsgpu_status fsgpu_index_builder_finish(fsgpu_index_builder* b, const char* path, fsgpu_index** out_index, fsgpu_index_build_stats* stats) {
+    if (!out_index) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_index is null");
+    *out_index = nullptr;
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_index>();
+        fsgpu::IndexBuilder::Stats st;
+        fsgpu::SearchError e = b->impl.finish(path, &h->impl, &st);
+        if (!e.ok()) return finish(e);
+        if (stats) {
+            stats->rows = st.rows;
+            stats->chunks = st.chunks;
+            stats->ingest_launches = st.ingest_launches;
+            stats->permute_launches = st.permute_launches;
+            stats->ingest_ms = st.ingest_ms;
+            stats->sort_ms = st.sort_ms;
+            stats->permute_ms = st.permute_ms;
+            stats->tables_ms = st.tables_ms;
+            stats->file_ms = st.file_ms;
+            stats->ingest_device_ms = st.ingest_device_ms;
+            stats->permute_device_ms = st.permute_device_ms;
+            stats->peak_device_bytes = st.peak_device_bytes;
+        }
+        *out_index = h.release();
+        return FSGPU_OK;
+    });
 }
 
 }  // extern "C"

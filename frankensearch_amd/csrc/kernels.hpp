@@ -570,4 +570,33 @@ struct ResolveHitsArgs {
 };
 hipError_t launch_resolve_hits(const ResolveHitsArgs& args, hipStream_t stream);
 
+// index_build_kernels.hip: the two device passes of the index builder (index_builder.cpp).  Staged rows live in chunks of
+// chunk_rows rows behind a device table of chunk pointers: staged position p is row p % chunk_rows of chunks[p / chunk_rows].
+constexpr uint32_t kBuildLaunchRows = 1u << 20;    // rows per launch: no single launch holds a shared card for long
+constexpr uint32_t kBuildTileRows = 64;            // ingest: rows per wave, one per lane
+constexpr uint32_t kBuildTileCols = 64;            // ingest: columns per LDS tile
+constexpr u64 kBuildVerdictNone = ~0ull;           // IngestArgs::verdict when every row passed
+constexpr uint32_t kBuildNonFinite = 1, kBuildBadNorm = 2;   // low byte of the verdict word: which rule the row broke
+struct IngestArgs {
+    const float* src;              // [n, dim] f32 rows of this launch
+    unsigned char* const* chunks;  // the staging chunks
+    uint32_t chunk_rows;
+    uint32_t dim;
+    uint32_t n;                    // rows of this launch, <= kBuildLaunchRows and n * dim < 2^31
+    uint32_t to_f16;               // 1: rows are staged as round-to-nearest-even f16; 0: as raw f32
+    u64 first_pos;                 // staged position of row 0
+    u64 first_row;                 // index of row 0 in its add call (for the verdict)
+    u64* verdict;                  // atomicMin of (row in call << 8 | rule) over the offending rows
+};
+hipError_t launch_build_ingest(const IngestArgs& args, hipStream_t stream);
+struct PermuteArgs {
+    unsigned char* const* chunks;  // the staging chunks
+    uint32_t chunk_rows;
+    uint32_t row_bytes;            // 2 .. : dim * 2 or dim * 4
+    const uint32_t* perm;          // [slab rows]: staged position of every slab row
+    unsigned char* out;            // the slab in file order
+    u64 row_begin, row_end;        // this launch's slab rows
+};
+hipError_t launch_build_permute(const PermuteArgs& args, hipStream_t stream);
+
 }  // namespace fsgpu

@@ -52,6 +52,12 @@ class VectorIndex {
     SearchError init_device(int device, uint32_t dim, uint64_t nrows, const void* slab_dev, const uint64_t* live_dev,
                             uint64_t row_base);
     SearchError open_fsvi(const char* path, int device);
+    // What open_fsvi leaves behind, from parts that never were a file (index_builder.cpp): the slab is a device allocation that
+    // becomes this index's own, the tables are the file's record table in memory (hashes [nrows], offsets [nrows + 1] into blob).
+    // On failure nothing was taken.
+    SearchError adopt_built(int device, uint32_t dim, uint64_t nrows, DeviceBuffer* slab, bool f32_rows, std::vector<uint64_t>* hashes,
+                            std::vector<uint64_t>* offsets, std::string* blob, const std::string& embedder_id,
+                            const std::string& embedder_revision, uint8_t compaction_gen);
     // catalog of a row-sharded index: the file's tables stay here (doc ids, tombstones, WAL, hit resolution), the slab is handed
     // back in `image` for the shards; topk_override replaces this object's own scan inside search_hits
     struct FsviImage {

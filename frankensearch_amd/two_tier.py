@@ -21,7 +21,7 @@ import numpy as np
 import ctypes as C
 
 from . import _lib, fusion
-from .errors import check
+from .errors import DimensionMismatch, InvalidConfig, check
 
 POOL_RETRIEVED = 0   # SyncQualityPool::Retrieved: attested quality tier (FSVI v2 admission) — independent retrieval
 POOL_RESCORED = 1    # SyncQualityPool::RescoredFastPool: legacy / unattested pair (every FSVI v1 artifact)
@@ -49,6 +49,9 @@ class TwoTierIndex:
         from .index import NativeShardedIndex
         self.fast, self.quality = fast_index, quality_index
         self.sharded = isinstance(fast_index, NativeShardedIndex)
+        if quality_index is None:   # a fast-only build (TwoTierIndexBuilder.finish without quality records): nothing to align
+            self._a = None
+            return
         if self.sharded != isinstance(quality_index, NativeShardedIndex):
             raise TypeError("a fast / quality pair is either two indexes or two sharded handles")
         h = C.c_void_p()
@@ -67,17 +70,30 @@ class TwoTierIndex:
         except Exception:
             pass
 
+    def has_quality_index(self) -> bool:
+        """False for a fast-only pair (TwoTierIndex::has_quality_index, two_tier.rs): only alignment_kind (NONE) and close apply."""
+        return self.quality is not None
+
+    def _need_quality(self, what: str) -> None:
+        if self._a is None:
+            raise InvalidConfig(f"{what}: the pair has no quality tier (a fast-only build)")
+
     def alignment_kind(self) -> int:
+        if self._a is None:
+            return self.NONE
         return int(_lib.lib().fsgpu_alignment_kind(self._a))
 
     def quality_row(self, fast_row: int) -> Optional[int]:
+        self._need_quality("quality_row")
         r = int(_lib.lib().fsgpu_alignment_quality_row(self._a, fast_row))
         return None if r < 0 else r
 
     def unmatched_quality_docs(self) -> int:
+        self._need_quality("unmatched_quality_docs")
         return int(_lib.lib().fsgpu_alignment_unmatched_quality_docs(self._a))
 
     def quality_scores_for_hits(self, query: Sequence[float], hits: Sequence[Tuple[str, float, int]]) -> List[Optional[float]]:
+        self._need_quality("quality_scores_for_hits")
         q = np.ascontiguousarray(query, dtype=np.float32)
         arr, keep = fusion._pack(hits)
         scores = np.zeros(max(len(hits), 1), dtype=np.float32)
@@ -90,6 +106,7 @@ class TwoTierIndex:
     def mmr_rerank(self, hits: Sequence[Tuple], config) -> Tuple[List[int], bool]:
         """fsgpu_two_tier_mmr_rerank: the searcher's MMR stage over (doc_id, score[, fast row]) in rank order — quality-tier vectors
         first, the fast tier's for a document without one.  Returns (order over the whole list, applied)."""
+        self._need_quality("mmr_rerank")
         if self.sharded:
             raise TypeError("MMR over row-sharded handles is not supported: a pool's rows sit on several GPUs")
         cfg = config._c()
@@ -102,6 +119,7 @@ class TwoTierIndex:
 
     def quality_scores_for_hits_batched(self, queries: np.ndarray, hit_lists: Sequence[Sequence[Tuple[str, float, int]]]) -> List[List[Optional[float]]]:
         """fsgpu_quality_scores_for_hits_batched: quality_scores_for_hits for a chunk of queries, ONE gather launch (unsharded pairs)."""
+        self._need_quality("quality_scores_for_hits_batched")
         q = np.ascontiguousarray(queries, dtype=np.float32)
         nq = len(hit_lists)
         assert q.ndim == 2 and q.shape[0] == nq and not self.sharded
@@ -194,3 +212,101 @@ class SyncTwoTierSearcher:
             final, _ = mmr_step([(h.doc_id, h.rrf_score, h) for h in final], pair, mmr, row_of=lambda t: t[2].semantic_index)
             final = [h[2] for h in final]
         return SearchOutcome(initial, final, fast_hits, quality_hits, blended, m)
+
+
+class TwoTierIndexBuilder:
+    """TwoTierIndexBuilder (crates/frankensearch-index/src/two_tier.rs:2003-2331) over the device-resident index builder
+    (index_builder.IndexBuilder, fsgpu_index_builder_*): add_fast_record / add_quality_record / add_record, per-tier duplicate
+    rejection (:2125-2132), "at least one fast-tier record is required" (:2241-2247), default embedder ids `fast-tier` /
+    `quality-tier`, and finish() -> TwoTierIndex, writing vector.fast.idx / vector.quality.idx when a directory is given.
+
+    As in the reference, dimension and duplicate errors are raised by the add that causes them, and the vectors themselves are
+    judged by the writer: records are handed to the device builder in batches (`batch` records, and at finish), so a non-finite or
+    zero-norm vector is refused there (InvalidConfig with `.bad_row` relative to that batch).  A refused batch is dropped whole:
+    its records are forgotten, their ids may be added again, and the builder goes on with what was staged before it.
+    add_*_records take a whole block.  Without a quality record finish() returns a fast-only pair (has_quality_index() is False):
+    alignment_kind() is NONE and the calls that need a quality tier raise InvalidConfig.
+    The files carry publication nonce 0, as write_fsvi writes it: the successor-nonce and install protocol of publish_tier
+    (:2277-2301) is not part of this builder."""
+    FAST_FILENAME, QUALITY_FILENAME = "vector.fast.idx", "vector.quality.idx"
+
+    def __init__(self, device: int = 0, quantization: int = 1, chunk_rows: int = 0, batch: int = 4096):
+        self.device, self.quantization, self.chunk_rows, self.batch = device, quantization, chunk_rows, batch
+        self._ids = {"fast": "fast-tier", "quality": "quality-tier"}
+        self._dim = {"fast": None, "quality": None}
+        self._seen = {"fast": set(), "quality": set()}
+        self._pending = {"fast": ([], []), "quality": ([], [])}
+        self._builder = {"fast": None, "quality": None}
+
+    def set_fast_embedder_id(self, embedder_id: str) -> "TwoTierIndexBuilder":
+        self._ids["fast"] = embedder_id
+        return self
+
+    def set_quality_embedder_id(self, embedder_id: str) -> "TwoTierIndexBuilder":
+        self._ids["quality"] = embedder_id
+        return self
+
+    def _flush(self, tier: str) -> None:
+        ids, vecs = self._pending[tier]
+        if not ids:
+            return
+        if self._builder[tier] is None:
+            from .index_builder import IndexBuilder
+            self._builder[tier] = IndexBuilder(self._dim[tier], self._ids[tier], "", device=self.device, quantization=self.quantization,
+                                               reject_duplicates=True, chunk_rows=self.chunk_rows)
+        self._pending[tier] = ([], [])
+        try:
+            self._builder[tier].add(ids, np.concatenate(vecs, axis=0))
+        except Exception:
+            self._seen[tier].difference_update(ids)   # all-or-nothing below: none of the batch was staged
+            raise
+
+    def _add(self, tier: str, doc_ids: Sequence[str], vectors) -> None:
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        v = v.reshape(len(doc_ids), -1)
+        expected = self._dim[tier] if self._dim[tier] is not None else v.shape[1]
+        if v.shape[1] != expected:
+            raise DimensionMismatch(f"expected {expected}, found {v.shape[1]}")
+        fresh = set()
+        for d in doc_ids:
+            if d in self._seen[tier] or d in fresh:
+                raise InvalidConfig(f"duplicate doc_id in {tier} tier; each document must have a unique id")
+            fresh.add(d)
+        self._dim[tier] = expected
+        self._seen[tier] |= fresh
+        ids, vecs = self._pending[tier]
+        ids.extend(doc_ids)
+        vecs.append(v.copy())
+        if len(ids) >= self.batch:
+            self._flush(tier)
+
+    def add_fast_record(self, doc_id: str, embedding: Sequence[float]) -> None:
+        self._add("fast", [doc_id], np.asarray(embedding, dtype=np.float32)[None, :])
+
+    def add_quality_record(self, doc_id: str, embedding: Sequence[float]) -> None:
+        self._add("quality", [doc_id], np.asarray(embedding, dtype=np.float32)[None, :])
+
+    def add_record(self, doc_id: str, fast_embedding: Sequence[float], quality_embedding: Optional[Sequence[float]] = None) -> None:
+        self.add_fast_record(doc_id, fast_embedding)
+        if quality_embedding is not None:
+            self.add_quality_record(doc_id, quality_embedding)
+
+    def add_fast_records(self, doc_ids: Sequence[str], vectors) -> None:
+        self._add("fast", list(doc_ids), vectors)
+
+    def add_quality_records(self, doc_ids: Sequence[str], vectors) -> None:
+        self._add("quality", list(doc_ids), vectors)
+
+    def finish(self, dir: Optional[str] = None) -> TwoTierIndex:
+        import os
+        if self._dim["fast"] is None:
+            raise InvalidConfig("at least one fast-tier record is required")
+        built = {}
+        for tier, name in (("fast", self.FAST_FILENAME), ("quality", self.QUALITY_FILENAME)):
+            if self._dim[tier] is None:
+                built[tier] = None
+                continue
+            self._flush(tier)
+            built[tier] = self._builder[tier].finish(None if dir is None else os.path.join(str(dir), name))
+            self._builder[tier].close()
+        return TwoTierIndex(built["fast"], built["quality"])

@@ -685,6 +685,82 @@ int32_t fsgpu_bert_device(const fsgpu_bert *m);
 int32_t fsgpu_m2v_device(const fsgpu_m2v *m);
 int32_t fsgpu_index_device(const fsgpu_index *idx);
 
+/* ---- device-resident hand-off: encoder -> index without the vectors crossing PCIe ---- */
+/* VectorIndexWriter::write_record + finish (crates/frankensearch-index/src/lib.rs:3607-3672, 3752-3943), TwoTierIndexBuilder
+ * (two_tier.rs:2003-2331), the facade's IndexBuilder (frankensearch/src/index_builder.rs:168-264) and RefreshWorker's rebuild
+ * (fusion/src/refresh.rs) for vectors that sit in device memory: a builder takes (doc id, vector) batches from host memory, from
+ * device memory or straight from an encoder handle, validates and encodes them on the device into a staging area, and at finish
+ * leaves the sorted slab in device memory as a ready fsgpu_index, and the FSVI v1 file when a path is given.
+ *
+ * The contract is an equivalence.  After any sequence of successful adds, fsgpu_index_builder_finish(b, path, &idx, ...) leaves at
+ * `path` the bytes fsgpu_fsvi_write_quant(path, embedder_id, embedder_revision, dim, n, all doc ids in arrival order, all vectors in
+ * arrival order, compaction_gen, device, quantization) writes, and in `idx` a handle that behaves as fsgpu_index_open_fsvi(path,
+ * device) of that file does: counts, doc ids, generation byte, slab bits, search rows and score bits, and later WAL appends, soft
+ * deletes, compact and vacuum.  With path == NULL the handle is the same and no file is touched.  Zero records behave as
+ * fsgpu_fsvi_write(n = 0) followed by fsgpu_index_open_fsvi.  The publication nonce is 0, as fsgpu_fsvi_write writes it.
+ *
+ * Validation (write_record_with_flags, lib.rs:3635-3673; vector_signal_usable, lib.rs:6133-6142) is per call and all-or-nothing, as
+ * append_batch validates everything before anything changes.  vector_len != dim is FSGPU_ERR_DIMENSION_MISMATCH.  A row with a
+ * non-finite element ("all embedding values must be finite"), a row whose norm_sq is not > 0 and finite ("embedding norm must be
+ * non-zero and finite; a zero vector can never match any query": lib.rs:3658 in full, where fsgpu_fsvi_write stops at the
+ * semicolon), a doc id longer than 65,535 bytes ("doc_id byte length must fit in u16"; an empty id is allowed) and, with
+ * reject_duplicates, a doc id already staged or repeated inside the call ("duplicate doc_id; each document must have a unique id",
+ * two_tier.rs:2125-2132) are FSGPU_ERR_INVALID_CONFIG.  The call then stages nothing, *out_bad_row (nullable) is the index in the
+ * call of the first offending row, and the message is that row's first broken rule in the order above.  norm_sq is the
+ * reference's: one f32 accumulator, the elements in order, a separate multiply and add, f32 subnormals kept; the check runs on the
+ * device for host-memory adds too.  Values beyond the f16 range are legal and encode to +-inf, as f16::from_f32 encodes them.
+ *
+ * Staging grows in chunks of chunk_rows rows (nothing staged is ever copied to make room; an add refused for want of device memory,
+ * FSGPU_ERR_DEVICE, stages nothing, keeps no allocation of its own and may be repeated with fewer rows); peak device memory at finish is the
+ * staging + the final slab + the permutation (fsgpu_index_build_stats::peak_device_bytes).  The sort by (FNV-1a, doc id bytes)
+ * stays on the host (lib.rs:3753-3762: stable, so duplicate ids keep their arrival order).  Calls on one builder are serialised
+ * inside the library.  No device: FSGPU_ERR_NO_DEVICE; unknown option values or non-zero reserved words: FSGPU_ERR_INVALID_CONFIG
+ * before a device is looked for. */
+typedef struct fsgpu_index_builder fsgpu_index_builder;
+typedef struct fsgpu_index_builder_options {
+    uint32_t quantization;       /* 1 = F16 (default), 0 = F32 */
+    uint32_t compaction_gen;     /* header byte, 0..255 */
+    uint32_t reject_duplicates;  /* 0: VectorIndexWriter (duplicates kept, stable); 1: TwoTierIndexBuilder (two_tier.rs:2125-2132) */
+    uint32_t chunk_rows;         /* staging chunk, 0 = library default (65,536 rows) */
+    uint64_t reserve_rows;       /* hint: staging for this many rows is allocated at create; 0 = none */
+    uint32_t reserved[6];        /* must be 0 */
+} fsgpu_index_builder_options;
+typedef struct fsgpu_index_build_stats {
+    uint64_t rows, chunks;                      /* records in the index; staging chunks that were allocated */
+    uint64_t ingest_launches, permute_launches; /* each covers at most 2^20 rows */
+    double ingest_ms;                           /* all adds: first launch to verdict, host clock (uploads of host-memory adds included) */
+    double sort_ms, permute_ms, tables_ms, file_ms;   /* finish: host sort, device gather, record + string tables, file (0 without a path) */
+    double ingest_device_ms, permute_device_ms; /* the same two between events on the stream: the launches alone (and, for host-memory adds, the uploads between them) */
+    uint64_t peak_device_bytes;                 /* staging + final slab + permutation + chunk table */
+} fsgpu_index_build_stats;
+/* options == NULL: {quantization 1, everything else 0}.  NULL embedder_id / embedder_revision are FSGPU_ERR_NULL_ARGUMENT. */
+fsgpu_status fsgpu_index_builder_create(int32_t device, uint32_t dim, const char *embedder_id, const char *embedder_revision,
+                                        const fsgpu_index_builder_options *options_or_null, fsgpu_index_builder **out);
+void fsgpu_index_builder_destroy(fsgpu_index_builder *b);
+uint64_t fsgpu_index_builder_record_count(const fsgpu_index_builder *b);   /* records staged so far; after finish: in the index */
+/* doc_ids [n] pointers; doc_id_lens NULL = NUL-terminated ids.  vectors: [n, vector_len] f32 in host memory. */
+fsgpu_status fsgpu_index_builder_add(fsgpu_index_builder *b, uint64_t n, const char *const *doc_ids, const uint32_t *doc_id_lens_or_null,
+                                     const float *vectors, uint32_t vector_len, uint64_t *out_bad_row);
+/* ... in memory of the builder's device.  The ingest is enqueued behind hip_stream (NULL = the default stream), the stream that
+ * produced the vectors; the call returns when the verdict is known. */
+fsgpu_status fsgpu_index_builder_add_device(fsgpu_index_builder *b, uint64_t n, const char *const *doc_ids,
+                                            const uint32_t *doc_id_lens_or_null, const float *vectors_dev, uint32_t vector_len,
+                                            void *hip_stream, uint64_t *out_bad_row);
+/* ... embedded into a builder-owned device buffer by the very calls fsgpu_bert_embed_device / fsgpu_m2v_embed_device make, then
+ * ingested.  An embedder on another device or of another dimension is FSGPU_ERR_INVALID_CONFIG / FSGPU_ERR_DIMENSION_MISMATCH; an
+ * encoder error is returned as it is, with nothing staged.  An empty text embeds to zeros and is refused by the norm rule, naming
+ * its row, as write_record would refuse it. */
+fsgpu_status fsgpu_index_builder_add_bert(fsgpu_index_builder *b, fsgpu_bert *m, const int32_t *ids, const uint32_t *offsets, uint32_t n,
+                                          const char *const *doc_ids, const uint32_t *doc_id_lens_or_null, uint64_t *out_bad_row);
+fsgpu_status fsgpu_index_builder_add_m2v(fsgpu_index_builder *b, fsgpu_m2v *m, const uint32_t *ids, const uint32_t *offsets, uint32_t n,
+                                         const char *const *doc_ids, const uint32_t *doc_id_lens_or_null, uint64_t *out_bad_row);
+/* VectorIndexWriter::finish (lib.rs:3752-3943).  The file, when path is given, is written to `path`.tmp and renamed over `path`, as
+ * fsgpu_index_compact writes its image.  A finished builder is spent, as finish(self) consumes the reference's: only destroy and
+ * record_count remain valid (anything else is FSGPU_ERR_INVALID_CONFIG).  A finish that fails (I/O, allocation) leaves the builder
+ * whole and may be called again.  *out_index is the caller's to destroy. */
+fsgpu_status fsgpu_index_builder_finish(fsgpu_index_builder *b, const char *path_or_null, fsgpu_index **out_index,
+                                        fsgpu_index_build_stats *stats_or_null);
+
 /* ---- host-side rank fusion (O(k), CPU, no GPU needed) ---- */
 /* One ranked hit: ScoredResult / VectorHit as the fusion code reads them
  * (crates/frankensearch-core/src/types.rs:88-134): doc id (not NUL-terminated), score, vector row index. */
