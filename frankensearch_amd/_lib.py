@@ -153,6 +153,9 @@ SIGNATURES = {
     "fsgpu_lab_linear_int8_dynamic": (_i32, [_i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_lab_bert_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_stage_args: BertStageArgs below)
     "fsgpu_lab_bert_short_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_short_args: BertShortArgs below)
+    "fsgpu_lab_scan_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_scan_stage_args: ScanStageArgs below)
+    "fsgpu_lab_scan_stage_check": (_i32, [_vp]),
+    "fsgpu_lab_scan_planner_shape": (_i32, [_i32, _i32]),
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
@@ -244,6 +247,15 @@ class BertShortArgs(C.Structure):
     _fields_ = [(name, _u32) for name in ("stage", "form", "m", "n_docs", "hidden", "inter", "heads", "layers", "vocab", "max_pos")] + [
         ("eps", C.c_float), ("scale", C.c_float), ("offsets", _vp), ("ids", _vp), ("positions", _vp),
         ("in_", _vp * 8), ("layer_in", _vp), ("out0", _vp), ("out1", _vp)]
+
+
+class ScanStageArgs(C.Structure):
+    """fsgpu_lab_scan_stage_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("kernel", "variant", "stage", "elem_bytes", "dim", "nrows", "row_stride", "row_base",
+                                          "grid", "groups", "side_by_side", "reverse", "group_stride", "group_count", "slots", "spill_cap",
+                                          "nq_pad", "want_counts", "nq", "max_norm_bits", "bits", "reserved")] + [
+        (name, _vp) for name in ("slab", "live", "allow", "queries", "tau", "queries_f32", "cand", "cand_count", "spill", "spill_count",
+                                 "overflow", "dense", "prepared", "delta")]
 
 
 _lib = None

@@ -2359,6 +2359,200 @@ fsgpu_status fsgpu_lab_bert_short_stage(int32_t device, const fsgpu_lab_bert_sho
     });
 }
 
+namespace {
+// What fsgpu_lab_scan_stage derives from its arguments once they have passed: queries per group, groups, row pitch, output sizes.
+struct ScanStageGeom {
+    uint32_t group_q = 0, groups = 1;
+    bool sample = false, lists = false, counts = false;
+    size_t pitch = 0, cand_n = 0, count_n = 0, spill_n = 0, dense_n = 0;
+};
+
+fsgpu_status scan_stage_check(const fsgpu_lab_scan_stage_args& a, ScanStageGeom* geom) {
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    auto null = [](const char* what) { return fail(FSGPU_ERR_NULL_ARGUMENT, what); };
+    ScanStageGeom g;
+    if (a.kernel > FSGPU_LAB_SCAN_PREPARE) return bad("scan stage: unknown kernel");
+    if (a.elem_bytes != 1 && a.elem_bytes != 2) return bad("scan stage: elem_bytes must be 1 or 2");
+    if (a.kernel == FSGPU_LAB_SCAN_PREPARE) {
+        if (a.dim == 0 || a.dim > 4096) return bad("scan stage: prepare takes dim in 1..=4096");
+        if (a.nq_pad == 0 || a.nq_pad > 4096 || a.nq > a.nq_pad) return bad("scan stage: prepare takes nq <= nq_pad in 1..=4096");
+        if (a.elem_bytes == 1 && a.bits != 8 && a.bits != 4) return bad("scan stage: the int8 prepare takes bits 8 or 4");
+        if ((a.nq && !a.queries_f32) || !a.prepared || !a.delta) return null("scan stage: prepare needs queries_f32, prepared and delta");
+        if (geom) *geom = g;
+        return FSGPU_OK;
+    }
+    const int dim = (int)a.dim, eb = (int)a.elem_bytes;
+    if (a.nrows == 0 || a.nrows > (1u << 24)) return bad("scan stage: nrows must be in 1..=2^24");
+    if (a.grid == 0 || a.grid > 4096 || a.groups > 8) return bad("scan stage: grid must be in 1..=4096 and groups at most 8");
+    if (a.spill_cap > (1u << 20) || a.group_count > (1u << 16) || a.side_by_side > 1 || a.reverse > 1 || a.want_counts > 1)
+        return bad("scan stage: spill_cap, group_count or a flag out of range");
+    g.groups = a.groups ? a.groups : 1;
+    if (a.kernel == FSGPU_LAB_SCAN_LDS) {
+        if (!fsgpu::scan_mfma_supported(dim)) return bad("scan stage: scan_mfma_supported refuses the dimension");
+        if (a.variant > 5 || !fsgpu::scan_mfma_shape_built((int)a.variant) || (a.variant == 4 && eb != 1))
+            return bad("scan stage: the shape is not compiled into this build");
+        if (a.stage > 2) return bad("scan stage: the LDS-query kernel has stages 0, 1 and 2");
+        if (a.want_counts || a.side_by_side) return bad("scan stage: list lengths and side-by-side groups are the register-query kernel's");
+        if (a.stage != 0 && (a.slots == 0 || (int)a.slots > fsgpu::scan_mfma_max_slots((int)a.variant))) return bad("scan stage: slots beyond scan_mfma_max_slots");
+        g.group_q = (uint32_t)fsgpu::scan_mfma_query_tiles((int)a.variant) * 16;
+        g.sample = a.stage < 2;
+        if (a.group_stride == 0) return bad("scan stage: group_stride must be at least 1");
+    } else {
+        if (!fsgpu::scan_wide_supported(dim, eb)) return bad("scan stage: scan_wide_supported refuses the row length");
+        if (a.variant < 2 || (int)a.variant > fsgpu::scan_wide_max_query_tiles(dim, eb)) return bad("scan stage: query tiles beyond scan_wide_max_query_tiles");
+        if (a.stage < 1 || a.stage > 3) return bad("scan stage: the register-query kernel has stages 1, 2 and 3");
+        if (a.stage == 3 && (eb != 1 || !fsgpu::scan_wide_group_maxima_supported(dim, (int)a.variant)))
+            return bad("scan stage: scan_wide_group_maxima_supported refuses the shape");
+        if (a.stage == 3 && a.want_counts) return bad("scan stage: the group-maxima stage writes no lists");
+        if (a.stage != 3 && (a.slots == 0 || a.slots > fsgpu::kWideSlots)) return bad("scan stage: slots beyond kWideSlots");
+        g.group_q = 128 * a.variant;
+        g.sample = a.stage != 2;
+        if (a.stage == 2 && a.group_count != 0) return bad("scan stage: the register-query main pass visits every row (group_count must be 0)");
+        // (the kernel's list offsets are 32-bit byte offsets inside a group's lists)
+        if ((uint64_t)g.group_q * a.grid * (a.stage == 3 ? 4 : a.slots) * 8 > 0xffffffffull) return bad("scan stage: a group's lists exceed 4 GB");
+    }
+    if (g.sample) {
+        if (a.group_count == 0 || a.group_stride == 0) return bad("scan stage: a sample stage needs group_count and group_stride");
+        if ((uint64_t)(a.group_count - 1) * a.group_stride * 64 >= a.nrows) return bad("scan stage: a sample group begins past the last row");
+    }
+    if (a.nq_pad != g.groups * g.group_q) return bad("scan stage: nq_pad must be groups x the kernel's query group");
+    g.pitch = a.row_stride ? a.row_stride : (size_t)dim * eb;
+    if (g.pitch < (size_t)dim * eb || (g.pitch & 15) || g.pitch > (1u << 16)) return bad("scan stage: row_stride must be a multiple of 16 bytes that holds a row");
+    if ((uint64_t)a.nrows * g.pitch > (1ull << 31)) return bad("scan stage: the slab exceeds 2 GB");
+    const bool gmax = a.kernel == FSGPU_LAB_SCAN_REG && a.stage == 3;
+    const bool dense = a.kernel == FSGPU_LAB_SCAN_LDS && a.stage == 0;
+    g.lists = !dense && !gmax;
+    g.counts = a.want_counts != 0;
+    g.cand_n = dense ? 0 : (size_t)a.nq_pad * a.grid * (gmax ? 4 : a.slots);
+    g.count_n = g.counts ? (size_t)a.nq_pad * a.grid : 0;
+    g.spill_n = g.lists ? (size_t)a.nq_pad * a.spill_cap : 0;
+    g.dense_n = dense ? (size_t)a.nq_pad * a.group_count * 64 : 0;
+    if ((g.cand_n | g.dense_n) > (1ull << 28)) return bad("scan stage: an output exceeds 2 GB");
+    if (!a.slab || !a.queries) return null("scan stage: slab or queries is null");
+    if (!dense && !gmax && !a.tau) return null("scan stage: tau is null");
+    if (dense ? !a.dense : !a.cand) return null("scan stage: the stage's output is null");
+    if (g.lists && (!a.spill_count || !a.overflow || (a.spill_cap && !a.spill))) return null("scan stage: spill, spill_count or overflow is null");
+    if (g.counts && !a.cand_count) return null("scan stage: cand_count is null");
+    if (geom) *geom = g;
+    return FSGPU_OK;
+}
+}  // namespace
+
+fsgpu_status fsgpu_lab_scan_stage_check(const fsgpu_lab_scan_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return scan_stage_check(*args, nullptr);
+}
+
+int32_t fsgpu_lab_scan_planner_shape(int32_t requested, int32_t elem_bytes) { return fsgpu::scan_mfma_planner_shape(requested, elem_bytes); }
+
+fsgpu_status fsgpu_lab_scan_stage(int32_t device, const fsgpu_lab_scan_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_scan_stage_args& a = *args;
+    ScanStageGeom g;
+    if (const fsgpu_status st = scan_stage_check(a, &g); st != FSGPU_OK) return st;
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        // outputs: [band | body | band], the bands of kGuardByte, the body prefilled with `fill`
+        constexpr size_t kBand = 4096;
+        struct Out {
+            unsigned char* base;
+            size_t bytes;
+            void* host;
+        };
+        std::vector<Out> outs;
+        auto out = [&](size_t bytes, int fill, void* host) -> void* {
+            if (bytes == 0 || !host) return nullptr;
+            unsigned char* base = static_cast<unsigned char*>(s.alloc(bytes + 2 * kBand));
+            if (s.ok()) s.hip(hipMemset(base, LabStage::kGuardByte, bytes + 2 * kBand));
+            if (s.ok()) s.hip(hipMemset(base + kBand, fill, bytes));
+            outs.push_back({base, bytes, host});
+            return s.ok() ? base + kBand : nullptr;
+        };
+        if (a.kernel == FSGPU_LAB_SCAN_PREPARE) {
+            const size_t qn = (size_t)a.nq * a.dim;
+            const float* q = a.nq ? s.f32(a.queries_f32, qn) : static_cast<const float*>(s.alloc(16));
+            void* prepared = out((size_t)a.nq_pad * a.dim * a.elem_bytes, 0xCD, a.prepared);
+            float* delta = static_cast<float*>(out((size_t)a.nq_pad * 4, 0xCD, a.delta));
+            if (a.elem_bytes == 2) {
+                const unsigned int* mx = static_cast<const unsigned int*>(s.raw(&a.max_norm_bits, 4));
+                if (s.ok()) s.hip(fsgpu::launch_prepare_queries(q, a.nq, a.nq_pad, a.dim, 0, mx, prepared, delta, nullptr));
+            } else if (s.ok()) {
+                s.hip(fsgpu::launch_prepare_queries_i8(q, a.nq, a.nq_pad, a.dim, prepared, delta, nullptr, (int)a.bits));
+            }
+        } else {
+            // the slab, with guard rows behind its last row: NaN halves / 0x7f bytes
+            constexpr size_t kSlabGuardRows = 256;
+            const size_t body = (size_t)a.nrows * g.pitch, tail = kSlabGuardRows * g.pitch;
+            unsigned char* slab = static_cast<unsigned char*>(s.alloc(body + tail));
+            if (s.ok()) s.hip(hipMemcpy(slab, a.slab, body, hipMemcpyHostToDevice));
+            if (s.ok()) {
+                std::vector<unsigned char> guard(tail, 0x7f);
+                if (a.elem_bytes == 2)
+                    for (size_t i = 0; i < tail; i += 2) guard[i] = 0x00, guard[i + 1] = 0x7e;
+                s.hip(hipMemcpy(slab + body, guard.data(), tail, hipMemcpyHostToDevice));
+            }
+            const size_t words = ((size_t)a.nrows + 63) / 64;
+            auto bitmap = [&](const uint64_t* src) -> const fsgpu::u64* {
+                if (!src) return nullptr;
+                std::vector<uint64_t> w(words + 2, 0);   // (two zero words behind the last)
+                std::memcpy(w.data(), src, words * 8);
+                return static_cast<const fsgpu::u64*>(s.raw(w.data(), w.size() * 8));
+            };
+            fsgpu::MfmaScanArgs m{};
+            m.slab = slab;
+            m.live = bitmap(a.live);
+            m.allow = bitmap(a.allow);
+            m.queries = s.raw(a.queries, (size_t)a.nq_pad * a.dim * a.elem_bytes);
+            if (a.tau) m.tau = static_cast<const float*>(s.raw(a.tau, (size_t)a.nq_pad * 4));
+            m.cand = static_cast<fsgpu::u64*>(out(g.cand_n * 8, 0xCD, a.cand));
+            m.cand_count = static_cast<uint32_t*>(out(g.count_n * 4, 0xCD, a.cand_count));
+            m.dense = static_cast<fsgpu::u64*>(out(g.dense_n * 8, 0xCD, a.dense));
+            if (g.lists) {
+                m.spill = static_cast<fsgpu::u64*>(out(g.spill_n * 8, 0xCD, a.spill));
+                m.spill_count = static_cast<uint32_t*>(out((size_t)a.nq_pad * fsgpu::kMfmaSpillCountStride * 4, 0, a.spill_count));
+                m.overflow = static_cast<uint32_t*>(out((size_t)a.nq_pad * 4, 0, a.overflow));
+            }
+            m.spill_cap = a.spill_cap;
+            m.nrows = a.nrows;
+            m.stage = a.stage;
+            m.group_stride = a.group_stride;
+            m.group_count = a.group_count;
+            m.dim = a.dim;
+            m.slots = a.kernel == FSGPU_LAB_SCAN_REG && a.stage == 3 ? 4 : a.slots;
+            m.row_base = a.row_base;
+            m.elem_bytes = a.elem_bytes;
+            m.reverse = a.reverse;
+            m.row_stride = a.row_stride;
+            m.groups = a.groups;
+            m.side_by_side = a.side_by_side;
+            if (s.ok()) {
+                if (a.kernel == FSGPU_LAB_SCAN_LDS) s.hip(fsgpu::launch_scan_mfma(m, (int)a.variant, (int)a.grid, nullptr, nullptr));
+                else s.hip(fsgpu::launch_scan_wide(m, (int)a.variant, (int)a.grid, nullptr, nullptr));
+            }
+        }
+        s.hip(hipStreamSynchronize(nullptr));
+        bool guard_hit = false;
+        for (const Out& o : outs) {
+            if (!s.ok()) break;
+            std::vector<unsigned char> h(o.bytes + 2 * kBand);
+            s.hip(hipMemcpy(h.data(), o.base, h.size(), hipMemcpyDeviceToHost));
+            if (!s.ok()) break;
+            for (size_t i = 0; i < kBand; ++i)
+                if (h[i] != LabStage::kGuardByte || h[kBand + o.bytes + i] != LabStage::kGuardByte) guard_hit = true;
+            std::memcpy(o.host, h.data() + kBand, o.bytes);
+        }
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he == hipErrorInvalidValue) return fail(FSGPU_ERR_INVALID_CONFIG, "scan stage: the launcher refused the shape");
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (guard_hit) return fail(FSGPU_ERR_DEVICE, "scan stage: a kernel wrote into a guard band of its output");
+        return FSGPU_OK;
+    });
+}
+
 fsgpu_status fsgpu_bert_embed_device(fsgpu_bert* m, const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out_dev) {
     if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
     if (n && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_dev is null");

@@ -253,6 +253,10 @@ int scan_mfma_waves_per_block(int shape);
 int scan_mfma_rows_per_tile(int shape);
 int scan_mfma_query_tiles(int shape);
 int scan_mfma_max_slots(int shape);  // LDS staging capacity per (query, block)
+bool scan_mfma_shape_built(int shape);   // the shape is compiled into THIS build (a shipped build: 0 and 2; shapes 1, 3, 4, 5 are experiments only)
+// the 128-query shape the batched planner runs for a requested one (FSGPU_MFMA_SHAPE / FSGPU_MFMA_SHAPE_I8; 0 = none asked for): the
+// request when it is a shape of this element size that this build contains, else shape 2
+int scan_mfma_planner_shape(int requested, int elem_bytes);
 hipError_t launch_scan_mfma(const MfmaScanArgs& args, int shape, int grid, hipStream_t stream, int* occupancy);
 hipError_t launch_max_row_norm(const void* slab, uint32_t nrows, uint32_t dim, uint32_t row_stride_bytes, unsigned int* out_bits,
                                hipStream_t stream);

@@ -1081,6 +1081,17 @@ int scan_mfma_waves_per_block(int shape) { return shape == 0 || shape == 3 ? 4 :
 int scan_mfma_rows_per_tile(int shape) { return shape == 4 ? 64 : (shape >= 2 ? 32 : 16); }  // shape 5: 32
 int scan_mfma_query_tiles(int shape) { return shape == 0 ? 4 : (shape == 5 ? 10 : 8); }
 int scan_mfma_max_slots(int shape) { return shape == 5 ? 16 : (int)kMfmaMaxSlots; }
+bool scan_mfma_shape_built(int shape) {   // (the cases of launch_mfma_d)
+#ifdef FSGPU_EXPERIMENTS
+    return shape >= 0 && shape <= 5;
+#else
+    return shape == 0 || shape == 2;
+#endif
+}
+int scan_mfma_planner_shape(int requested, int elem_bytes) {
+    const int last = elem_bytes == 1 ? 4 : 3;   // (shape 4 is int8 only; 0 and 5 are the planner's own choices, not a request's)
+    return requested >= 1 && requested <= last && scan_mfma_shape_built(requested) ? requested : 2;
+}
 
 template <int DIM, int EB>
 static hipError_t launch_mfma_d(const MfmaScanArgs& args, int shape, int grid, hipStream_t stream, int* occupancy) {

@@ -655,9 +655,9 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     FSGPU_TRY(mf_dense_.reserve((size_t)QCAP * RA_MAX * 8));
     FSGPU_TRY(mf_sel_.reserve((size_t)QCAP * KC * 8));
     if (mf_shape_ < 0) {
-        mf_shape_ = 2;                // 128-query kernel shape (mfma_scan.hip)
-        if (knobs().mfma_shape) mf_shape_ = knobs().mfma_shape;  // tuning experiments only
-        if (mf_shape_ < 1 || mf_shape_ > 3) mf_shape_ = 2;
+        // 128-query kernel shape (mfma_scan.hip): 2; a request (tuning experiments only) for a shape this build does not contain is
+        // not followed — its launches would all fail, and with them every batched search
+        mf_shape_ = scan_mfma_planner_shape(knobs().mfma_shape, 2);
         MfmaScanArgs probe{};
         probe.dim = dim_;
         probe.stage = 2;  // the main-pass instantiation
@@ -667,14 +667,12 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
         // (rounds 3-5 ran int8 rows on shape 4 — 64-row tiles, 24 KB in flight per wave — whose main-pass instantiation spills inside
         // its tile loop; round 6 measured shape 2 against it at 10M rows, 100..255 queries: 8-12 % faster on 256-dimension rows, 0-4 % on
         // 384 — profiles/r06/lds_query_shape_ab.txt)
-        mf_shape_i8_ = 2;
-        if (knobs().mfma_shape_i8) mf_shape_i8_ = knobs().mfma_shape_i8;  // tuning experiments only
-        if (mf_shape_i8_ < 1 || mf_shape_i8_ > 4) mf_shape_i8_ = 2;
+        mf_shape_i8_ = scan_mfma_planner_shape(knobs().mfma_shape_i8, 1);  // (a request: tuning experiments only)
         FSGPU_HIP(launch_scan_mfma(probe, 0, 1, stream, &mf_per_cu_narrow_i8_));
         FSGPU_HIP(launch_scan_mfma(probe, mf_shape_i8_, 1, stream, &mf_per_cu_wide_i8_));
         // 160-query shape: measured 1.49 ms per pass at 10M x 384 (0.64 of HBM peak) against 1.26 ms at 128 queries
         // (0.75) — 7 % more queries per second, but the pass is no longer HBM-bound; opt-in (FSGPU_USE_160=1)
-        mf_use_160_ = knobs().use_160;
+        mf_use_160_ = knobs().use_160 && scan_mfma_shape_built(5);
         if (mf_use_160_) {   // (experiments builds only: the shipped library does not carry the shape)
             FSGPU_HIP(launch_scan_mfma(probe, 5, 1, stream, &mf_per_cu_160_i8_));
             probe.elem_bytes = 2;

@@ -116,6 +116,51 @@ typedef struct fsgpu_lab_bert_short_args {
     float *out0, *out1;
 } fsgpu_lab_bert_short_args;
 fsgpu_status fsgpu_lab_bert_short_stage(int32_t device, const fsgpu_lab_bert_short_args *args);
+/* ONE stage of the batched scan on host arrays, through the launcher the product calls (launch_scan_mfma, launch_scan_wide,
+ * launch_prepare_queries, launch_prepare_queries_i8) with an MfmaScanArgs filled from this struct: for kernel-level tests against
+ * tests/scan_stage_ref.py.  One launch on the default stream, fresh device buffers, no kernel of its own.
+ *   kernel  LDS (queries in LDS, mfma_scan.hip): variant = shape, stage 0 dense sample / 1 thresholded sample / 2 main pass (every
+ *           64-row group outside the sample {j group_stride : j < group_count}; group_stride >= 1).
+ *           REG (queries in registers, mfma_wide.hip): variant = query tiles per wave, stage 1 thresholded sample / 2 main pass (every
+ *           row) / 3 group maxima (int8 rows: cand is [nq_pad][grid][4], no tau, no spill).
+ *           PREPARE: queries_f32 [nq, dim] -> prepared [nq_pad, dim] (f16 bits for elem_bytes 2 with max_norm_bits, int8 levels for
+ *           elem_bytes 1 with bits 8 or 4) and delta [nq_pad]; nothing else is read.
+ *   A launch answers `groups` (0 means 1) query groups of the kernel's size (16 x the shape's query tiles; 128 x variant): nq_pad must be
+ *   groups x that size.  A sample's groups must all begin below nrows.  slab: nrows rows of row_stride (0: dim x elem_bytes) bytes; live /
+ *   allow: ceil(nrows / 64) words or NULL; queries: nq_pad x dim elements as the kernel reads them; tau [nq_pad].
+ *   Outputs (those the stage writes must not be NULL): cand [nq_pad][grid][slots], cand_count [nq_pad][grid] (REG, want_counts = 1: the
+ *   lists are then NOT padded), spill [nq_pad][spill_cap], spill_count [nq_pad x 16] (the product's counter stride), overflow [nq_pad],
+ *   dense [nq_pad][group_count x 64].  List, spill and dense areas are prefilled with bytes 0xCD, the counters and flags with zero.
+ * Arguments are checked before a device is looked for (fsgpu_lab_scan_stage_check does only that: FSGPU_OK = it would be launched); what
+ * the launchers' own predicates refuse, and a shape this build does not contain, is FSGPU_ERR_INVALID_CONFIG with nothing launched.
+ * Every output lies between guard bands of a fixed pattern (FSGPU_ERR_DEVICE, "guard band", if one is touched); behind the slab's last
+ * row lie guard rows of NaN (f16) or 0x7f (int8), so a read past nrows that reaches a score shows in the answers.  The grid need not
+ * fit the chip: the kernels' blocks are independent. */
+#define FSGPU_LAB_SCAN_LDS 0
+#define FSGPU_LAB_SCAN_REG 1
+#define FSGPU_LAB_SCAN_PREPARE 2
+typedef struct fsgpu_lab_scan_stage_args {
+    uint32_t kernel, variant, stage, elem_bytes, dim, nrows, row_stride, row_base;
+    uint32_t grid, groups, side_by_side, reverse, group_stride, group_count, slots, spill_cap, nq_pad, want_counts;
+    uint32_t nq, max_norm_bits, bits, reserved;
+    const void *slab;
+    const uint64_t *live, *allow;
+    const void *queries;
+    const float *tau;
+    const float *queries_f32;
+    uint64_t *cand;
+    uint32_t *cand_count;
+    uint64_t *spill;
+    uint32_t *spill_count, *overflow;
+    uint64_t *dense;
+    void *prepared;
+    float *delta;
+} fsgpu_lab_scan_stage_args;
+fsgpu_status fsgpu_lab_scan_stage_check(const fsgpu_lab_scan_stage_args *args);
+fsgpu_status fsgpu_lab_scan_stage(int32_t device, const fsgpu_lab_scan_stage_args *args);
+/* The 128-query shape of the LDS-query kernel the batched planner runs when FSGPU_MFMA_SHAPE (elem_bytes 2) or FSGPU_MFMA_SHAPE_I8
+ * (elem_bytes 1) asks for `requested` (0: nothing asked): a shape this build does not contain is never chosen. */
+int32_t fsgpu_lab_scan_planner_shape(int32_t requested, int32_t elem_bytes);
 /* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
