@@ -46,6 +46,8 @@ SIGNATURES = {
     "fsgpu_last_main_pass_kernel": (C.c_char_p, []),
     "fsgpu_index_create": (_i32, [_i32, _u32, _u64, _vp, _vp, _u64, C.POINTER(_vp)]),
     "fsgpu_index_create_device": (_i32, [_i32, _u32, _u64, _vp, _vp, _u64, C.POINTER(_vp)]),
+    "fsgpu_index_create_f32": (_i32, [_i32, _u32, _u64, _vp, _vp, _u64, C.POINTER(_vp)]),
+    "fsgpu_index_create_f32_device": (_i32, [_i32, _u32, _u64, _vp, _vp, _u64, C.POINTER(_vp)]),
     "fsgpu_index_open_fsvi": (_i32, [C.c_char_p, _i32, C.POINTER(_vp)]),
     "fsgpu_index_destroy": (None, [_vp]),
     "fsgpu_index_record_count": (_u64, [_vp]),

@@ -11,6 +11,9 @@
 // Mapping: a quad of lanes per row; lane a owns accumulator a, i.e. elements [32 g + 8 a, 32 g + 8 a + 8) of every
 // group — the four lanes of a quad read 128 contiguous bytes.  The combine is two DPP quad butterflies (IEEE add is
 // commutative, so all four lanes end with the same bits); leftovers and tail are computed redundantly by the quad.
+// The per-row arithmetic is stated once, in scan_common.hpp (quad_dot_f32): dot_rows_f32_kernel here and the F32-row re-score of
+// the batched search's selections (mfma_scan.hip) call it; the fused scan below keeps its own multi-query loop (one load of a
+// row's elements against up to four queries), whose bits the suite holds to the same oracle.
 #include "kernels.hpp"
 #include "scan_common.hpp"
 
@@ -39,41 +42,7 @@ __global__ __launch_bounds__(256) void dot_rows_f32_kernel(ScanArgs args, const 
     const unsigned char* base = reinterpret_cast<const unsigned char*>(args.slab) + (size_t)row * args.row_stride;
     const float* w = reinterpret_cast<const float*>(base);
     const bool vec = (args.row_stride & 15u) == 0;  // 16-byte aligned rows: dwordx4 loads
-    const int chunks = dim >> 3, groups = chunks >> 2;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    for (int g = 0; g < groups; ++g) {
-        const int e = 32 * g + 8 * a;
-        float x[8];
-        if (vec) {
-            const float4 lo = *reinterpret_cast<const float4*>(w + e), hi = *reinterpret_cast<const float4*>(w + e + 4);
-            x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w;
-            x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = w[e + j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float p = x[j] * qs[e + j];
-            acc[j] = acc[j] + p;
-        }
-    }
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float u = acc[j] + quad_xor1(acc[j]);  // lanes 0,1: acc0+acc1   lanes 2,3: acc2+acc3
-        v[j] = u + quad_xor2(u);                     // (acc0+acc1)+(acc2+acc3)
-    }
-    for (int c = 4 * groups; c < chunks; ++c)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float p = w[8 * c + j] * qs[8 * c + j];
-            v[j] = v[j] + p;
-        }
-    float s = hreduce8(v, args.hreduce);
-    for (int i = chunks * 8; i < dim; ++i) s = __builtin_fmaf(w[i], qs[i], s);
+    const float s = quad_dot_f32<1>(w, qs, dim, a, vec, args.hreduce);
     if (a != 0 || !in_range) return;
     if (GATHER) {
         if (mine) out_scores[item] = s;

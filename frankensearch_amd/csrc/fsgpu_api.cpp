@@ -349,6 +349,38 @@ fsgpu_status fsgpu_index_create_device(int32_t device, uint32_t dim, uint64_t nr
     });
 }
 
+fsgpu_status fsgpu_index_create_f32(int32_t device, uint32_t dim, uint64_t nrows, const void* slab_f32_le,
+                                    const uint64_t* live_bitmap, uint64_t row_base, fsgpu_index** out) {
+    if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    *out = nullptr;
+    return guarded([&]() -> fsgpu_status {
+        auto* h = new fsgpu_index();
+        fsgpu::SearchError e = h->impl.init_host(device, dim, nrows, slab_f32_le, live_bitmap, row_base, true);
+        if (!e.ok()) {
+            delete h;
+            return finish(e);
+        }
+        *out = h;
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_index_create_f32_device(int32_t device, uint32_t dim, uint64_t nrows, const void* slab_f32_dev,
+                                           const uint64_t* live_bitmap_dev, uint64_t row_base, fsgpu_index** out) {
+    if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    *out = nullptr;
+    return guarded([&]() -> fsgpu_status {
+        auto* h = new fsgpu_index();
+        fsgpu::SearchError e = h->impl.init_device(device, dim, nrows, slab_f32_dev, live_bitmap_dev, row_base, true);
+        if (!e.ok()) {
+            delete h;
+            return finish(e);
+        }
+        *out = h;
+        return FSGPU_OK;
+    });
+}
+
 fsgpu_status fsgpu_index_open_fsvi(const char* path, int32_t device, fsgpu_index** out) {
     if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
     *out = nullptr;

@@ -164,10 +164,10 @@ struct SelectArgs {
                                // sets its flag INSTEAD of `overflow`; big_pool != 0: only flagged queries are processed (second
                                // chance of the finish, launched right behind the first over the same lists)
     // finish step
-    const void* slab;          // [nrows, dim] f16
+    const void* slab;          // [nrows, dim] f16 (f32 when slab_f32 != 0)
     const float* queries;      // [nq, q_stride_f] f32 (the first dim of each are used)
     uint32_t dim, nrows, row_base;
-    uint32_t row_stride;       // bytes between slab rows; 0 = dim * 2
+    uint32_t row_stride;       // bytes between slab rows; 0 = dim * 2 (slab_f32: dense rows only, 0 or dim * 4)
     uint32_t query_stride;     // floats between queries; 0 = dim
     int hreduce;
     uint32_t k_out, out_stride;
@@ -182,6 +182,7 @@ struct SelectArgs {
     u64* cand_exact_out;
     uint32_t cand_out_stride;  // entries between queries in both (>= k)
     uint32_t valid_queries;       // blocks q >= this are padding slots whose query lies past the caller's array (0 = every block's query exists)
+    uint32_t slab_f32;            // != 0: `slab` holds raw f32 rows (Quantization::F32), re-scored in dot_product_f32_bytes_f32's order
     unsigned long long* stamps;   // lab builds (FSGPU_EXPERIMENTS): shader clocks of block 0's phases; null otherwise
 };
 // select_groups_kernel (mfma_scan.hip): the selection behind a group-maxima sample (MfmaScanArgs::stage == 3).  Per query: the
@@ -200,13 +201,14 @@ struct GroupSelectArgs {
     float* tau_out;            // [nq]
     uint32_t* overflow;        // [nq] (may be null)
     uint32_t* spill_reset;     // [nq * kMfmaSpillCountStride] (may be null)
-    const void* slab;          // [nrows, dim] f16
+    const void* slab;          // [nrows, dim] f16 (f32 when slab_f32 != 0)
     const u64* live;           // may be null
     const u64* allow;          // may be null
     const float* queries;      // [nq, query_stride] f32
     uint32_t dim, nrows, row_base, query_stride;
     int hreduce;
     uint32_t valid_queries;    // blocks q >= this are padding slots (0 = every block's query exists)
+    uint32_t slab_f32;         // != 0: `slab` holds raw f32 rows (Quantization::F32), re-scored in dot_product_f32_bytes_f32's order
     uint32_t rank_only;        // != 0 (the int8 two-pass, whose pass-1 scores are the reference's own): no re-score — tau_out = the k-th
                                // best group maximum itself (k <= 64, delta = 0: k distinct rows score at least that); slab may be null
 };
@@ -260,6 +262,8 @@ int scan_mfma_planner_shape(int requested, int elem_bytes);
 hipError_t launch_scan_mfma(const MfmaScanArgs& args, int shape, int grid, hipStream_t stream, int* occupancy);
 hipError_t launch_max_row_norm(const void* slab, uint32_t nrows, uint32_t dim, uint32_t row_stride_bytes, unsigned int* out_bits,
                                hipStream_t stream);
+// ... of dense f32 rows (the rotation decision of an F32 slab's filter copy)
+hipError_t launch_max_row_norm_f32(const float* rows, uint32_t nrows, uint32_t dim, unsigned int* out_bits, hipStream_t stream);
 hipError_t launch_prepare_queries(const float* q, uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t q_stride,
                                   const unsigned int* max_norm_bits, void* qh, float* delta, hipStream_t stream);
 

@@ -374,6 +374,7 @@ __device__ __forceinline__ void merge_wave_winners(const u64* win, int k, u64* t
 constexpr int kSelSortCap = 8192;   // live entries the sorted variant holds (dynamic LDS: 64 KB)
 constexpr int kRescoreBatch = 6;    // slab loads of a candidate row in flight at a time (a row of 384 dimensions: two round trips; 4: -1 % of a step, 12: spills, -2.5 %)
 constexpr int kSelQueryLds = 1024;  // dimensions of the re-score's query kept in LDS (longer queries are read in place)
+constexpr int kRescoreBatchF32 = 3; // ... of an F32 row: a group is two 16-byte loads per lane, so 3 keep the same 24 registers in flight
 #ifdef FSGPU_EXPERIMENTS
 #define SEL_STAMP(slot)                                                                                            \
     do {                                                                                                             \
@@ -385,8 +386,11 @@ constexpr int kSelQueryLds = 1024;  // dimensions of the re-score's query kept i
     do {                \
     } while (0)
 #endif
-template <bool FINISH, bool SORTED>
+// F32 = the slab holds raw f32 rows (Quantization::F32): the finish re-scores in dot_product_f32_bytes_f32's order (quad_dot_f32,
+// scan_common.hpp) instead of dot_product_f16_bytes_f32's; nothing else differs, and the F16 instantiations are the code they were.
+template <bool FINISH, bool SORTED, bool F32 = false>
 __global__ __launch_bounds__(kSelThreads, SORTED ? 4 : kSelMinWaves) void select_kernel(SelectArgs args) {
+    static_assert(FINISH || !F32, "only the re-score reads the slab");
     constexpr int NT = kSelThreads, PER = kSelPer, NW = kSelWaves, POOL = (int)kSelectPool, KL = 1;
     static_assert(POOL == NT, "one pool entry per thread in the final selection");
     __shared__ u64 win[2][NW * 64 * KL];  // per-wave winners [wave][rank], ping-pong across passes
@@ -717,7 +721,7 @@ __global__ __launch_bounds__(kSelThreads, SORTED ? 4 : kSelMinWaves) void select
         const int nc = ncand < pool_cap ? ncand : pool_cap;
         u64* cbuf = big ? sbuf : pool;   // (big: sbuf[0, ncand) are the candidates, best approximate score first)
         const float* qv = dim <= kSelQueryLds ? s_q : args.queries + (size_t)q * (args.query_stride ? args.query_stride : (uint32_t)dim);
-        const size_t row_pitch = args.row_stride ? (size_t)args.row_stride : (size_t)dim * 2;
+        const size_t row_pitch = args.row_stride ? (size_t)args.row_stride : (size_t)dim * (F32 ? 4 : 2);
         const int chunks = dim >> 3, groups = chunks >> 2, leftover = chunks & 3;
         for (int c0 = 0; c0 < nc; c0 += NT / 4) {  // block-uniform trip count
             const int c = c0 + (tid >> 2);
@@ -726,6 +730,13 @@ __global__ __launch_bounds__(kSelThreads, SORTED ? 4 : kSelMinWaves) void select
             uint32_t row = grow - args.row_base;
             const bool mine = mine_e != kEmpty && row < args.nrows;
             if (!mine) row = 0;
+            if constexpr (F32) {
+                // (dense 16-byte aligned rows: launch_select checks dim % 8 and the row stride)
+                const float* w = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(args.slab) + (size_t)row * row_pitch);
+                const float sc = quad_dot_f32<kRescoreBatchF32>(w, qv, dim, a, true, args.hreduce);
+                if (a == 0 && c < nc) cbuf[c] = mine ? pack(sc, grow) : kEmpty;
+                continue;
+            }
             const u32x4* p = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(args.slab) + (size_t)row * row_pitch);
             float acc[8];
 #pragma unroll
@@ -850,6 +861,27 @@ __global__ __launch_bounds__(256) void max_row_norm_kernel(const unsigned short*
         float s = 0.f;
         for (uint32_t i = lane; i < dim; i += 64) {
             const float v = (float)p[i];
+            s += v * v;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        m = fmaxf(m, s);
+    }
+    if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(m) * 1.0001f));
+}
+
+// ... over dense f32 rows (an F32 slab: only the rotation decision of its int8 filter copy reads it).
+__global__ __launch_bounds__(256) void max_row_norm_f32_kernel(const float* __restrict__ rows, uint32_t nrows, uint32_t dim,
+                                                               unsigned int* __restrict__ out_bits) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave_gid = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * 256) >> 6;
+    float m = 0.f;
+    for (uint32_t row = wave_gid; row < nrows; row += nwaves) {
+        const float* p = rows + (size_t)row * dim;
+        float s = 0.f;
+        for (uint32_t i = lane; i < dim; i += 64) {
+            const float v = p[i];
             s += v * v;
         }
 #pragma unroll
@@ -1237,8 +1269,10 @@ hipError_t launch_two_pass_merge(const u64* approx_lists, const u64* exact_lists
 // k x candidate_multiplier = 30 per tier (rrf.rs:113-115) and used to fall back to the two thresholded sample stages for it (0.8 ms of a
 // 3.6 ms step at 10M rows against 0.3); KCAP = 128 serves the int8 two-pass at 3 x 30 = 90 candidates (32 winners per wave: the top
 // 90 of 1,024 entries put ~11 in a wave's 128 on average).
-template <bool RANK, int M, int KCAP>
+// F32: the rows are raw f32 (Quantization::F32) and are re-scored in dot_product_f32_bytes_f32's order, as in select_kernel.
+template <bool RANK, int M, int KCAP, bool F32 = false>
 __global__ __launch_bounds__(512) void select_groups_kernel(GroupSelectArgs args) {
+    static_assert(!(RANK && F32), "the rank form reads no rows");
     constexpr int NT = 512, NW = NT / 64, PERT = 1024 / NT, PERW = RANK ? KCAP / 4 : 8, W0 = NW * PERW / 64, NR = M * 8;
     static_assert(NR <= 256 && NR <= NT && NW * PERW % 64 == 0 && W0 >= 1, "W0 winners per lane of wave 0; the rank loop runs on NR threads");
     static_assert(M <= 64 && KCAP >= 64 && KCAP % 64 == 0 && (RANK || M <= NW * PERW), "wave 0 picks M (or k <= KCAP) of the waves' winners");
@@ -1312,6 +1346,12 @@ __global__ __launch_bounds__(512) void select_groups_kernel(GroupSelectArgs args
         if (mine && args.allow) mine = ((args.allow[row >> 6] >> (row & 63)) & 1ull) != 0;
         // (every lane of a quad computes the same predicate: the quad shuffles below see whole quads)
         if (!mine) row = 0;
+        if constexpr (F32) {
+            const float* w = reinterpret_cast<const float*>(args.slab) + (size_t)row * (size_t)dim;
+            const float sc = quad_dot_f32<kRescoreBatchF32>(w, s_q, dim, a, true, args.hreduce);
+            if (a == 0 && c < NR && mine) pool[c] = pack(sc, grow);
+            continue;
+        }
         const u32x4* p = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(args.slab) + (size_t)row * ((size_t)dim * 2));
         float acc[8];
 #pragma unroll
@@ -1387,7 +1427,10 @@ hipError_t launch_select_groups(const GroupSelectArgs& args, int nq, hipStream_t
         if (args.k <= 64) hipLaunchKernelGGL((select_groups_kernel<true, M0, 64>), dim3(nq), dim3(512), 0, stream, args);
         else hipLaunchKernelGGL((select_groups_kernel<true, M0, (int)kGroupsRankMax>), dim3(nq), dim3(512), 0, stream, args);
     } else {
-        if (args.k <= kGroupsTaken) hipLaunchKernelGGL((select_groups_kernel<false, M0, 64>), dim3(nq), dim3(512), 0, stream, args);
+        if (args.slab_f32) {
+            if (args.k <= kGroupsTaken) hipLaunchKernelGGL((select_groups_kernel<false, M0, 64, true>), dim3(nq), dim3(512), 0, stream, args);
+            else hipLaunchKernelGGL((select_groups_kernel<false, M1, 64, true>), dim3(nq), dim3(512), 0, stream, args);
+        } else if (args.k <= kGroupsTaken) hipLaunchKernelGGL((select_groups_kernel<false, M0, 64>), dim3(nq), dim3(512), 0, stream, args);
         else hipLaunchKernelGGL((select_groups_kernel<false, M1, 64>), dim3(nq), dim3(512), 0, stream, args);
     }
     return hipGetLastError();
@@ -1441,12 +1484,21 @@ hipError_t launch_select(const SelectArgs& args, int nq, hipStream_t stream) {
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel<false, true>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
+        hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel<true, true, true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
         if (e1 != hipSuccess) return e1;
         if (e2 != hipSuccess) return e2;
+        if (e3 != hipSuccess) return e3;
         attr_done = true;
     }
     if (args.slab) {
         if (args.k_out < 1 || args.k_out > 64 || (args.dim & 7)) return hipErrorInvalidValue;
+        if (args.slab_f32) {   // dense f32 rows only (no MRL prefix views of F32 slabs here)
+            if (args.row_stride && args.row_stride != args.dim * 4) return hipErrorInvalidValue;
+            if (sorted) hipLaunchKernelGGL((select_kernel<true, true, true>), dim3(nq), dim3(kSelThreads), sort_lds, stream, args);
+            else hipLaunchKernelGGL((select_kernel<true, false, true>), dim3(nq), dim3(kSelThreads), 0, stream, args);
+            return hipGetLastError();
+        }
         if (sorted) hipLaunchKernelGGL((select_kernel<true, true>), dim3(nq), dim3(kSelThreads), sort_lds, stream, args);
         else hipLaunchKernelGGL((select_kernel<true, false>), dim3(nq), dim3(kSelThreads), 0, stream, args);
     } else {
@@ -1462,6 +1514,13 @@ hipError_t launch_max_row_norm(const void* slab, uint32_t nrows, uint32_t dim, u
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(max_row_norm_kernel, dim3(2048), dim3(256), 0, stream, static_cast<const unsigned short*>(slab),
                        nrows, dim, row_stride_bytes ? row_stride_bytes / 2 : dim, out_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_max_row_norm_f32(const float* rows, uint32_t nrows, uint32_t dim, unsigned int* out_bits, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out_bits, 0, 4, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(max_row_norm_f32_kernel, dim3(2048), dim3(256), 0, stream, rows, nrows, dim, out_bits);
     return hipGetLastError();
 }
 

@@ -149,9 +149,10 @@ SearchError ShardedIndex::check_layout(uint32_t ndev, uint32_t query_groups) {
 }
 
 SearchError ShardedIndex::init_host(const int32_t* devices, uint32_t ndev, uint32_t dim, uint64_t nrows, const void* slab_f16,
-                                    const uint64_t* live, int32_t exchange, uint32_t query_groups) {
+                                    const uint64_t* live, int32_t exchange, uint32_t query_groups, bool f32_rows) {
     if (!devices) return make_err(FSGPU_ERR_INVALID_CONFIG, "at least one device is required");
     SH_TRY(check_layout(ndev, query_groups));
+    f32_ = f32_rows;
     if (dim == 0) return make_err(FSGPU_ERR_INVALID_CONFIG, "dimension must be greater than zero");
     if (nrows >= 0xffffffffull) return make_err(FSGPU_ERR_INVALID_CONFIG, "row ids must fit in u32 (VectorHit.index)");
     if (nrows > 0 && !slab_f16) return make_err(FSGPU_ERR_NULL_ARGUMENT, "slab is null");
@@ -168,8 +169,8 @@ SearchError ShardedIndex::init_host(const int32_t* devices, uint32_t ndev, uint3
         s->rows = std::min<uint64_t>(nrows, s->lo + per) - s->lo;
         std::vector<uint64_t> bits;
         if (live && s->rows) bits = slice_bitmap(live, s->lo, s->rows);
-        const unsigned char* base = static_cast<const unsigned char*>(slab_f16) + (size_t)s->lo * dim * 2;
-        SH_TRY(s->index.init_host(s->device, dim, s->rows, s->rows ? base : nullptr, bits.empty() ? nullptr : bits.data(), s->lo));
+        const unsigned char* base = static_cast<const unsigned char*>(slab_f16) + (size_t)s->lo * dim * (f32_rows ? 4 : 2);
+        SH_TRY(s->index.init_host(s->device, dim, s->rows, s->rows ? base : nullptr, bits.empty() ? nullptr : bits.data(), s->lo, f32_rows));
         shards_.push_back(std::move(s));
     }
     return finish_init(exchange);
@@ -200,16 +201,15 @@ SearchError ShardedIndex::init_device(const int32_t* devices, uint32_t ndev, uin
 }
 
 // VectorIndex::open (lib.rs:1747-1909) for a sharded index: the file is read and validated once; its record table, doc-id
-// strings, tombstone flags (and later its WAL) stay in the catalog, the F16 slab is split over the devices.
+// strings, tombstone flags (and later its WAL) stay in the catalog, the slab (F16 or F32 rows) is split over the devices.
 SearchError ShardedIndex::open_fsvi(const char* path, const int32_t* devices, uint32_t ndev, int32_t exchange, uint32_t query_groups) {
     if (!devices || ndev == 0) return make_err(FSGPU_ERR_INVALID_CONFIG, "at least one device is required");
     catalog_ = std::make_unique<VectorIndex>();
     VectorIndex::FsviImage img;
     SH_TRY(catalog_->open_fsvi_catalog(path, &img));
-    if (img.f32_rows) return make_err(FSGPU_ERR_INVALID_CONFIG, "a sharded index needs an F16 slab (Quantization::F16)");
     const std::vector<uint64_t>& live = catalog_->live_host();
     SH_TRY(init_host(devices, ndev, img.dim, img.nrows, img.bytes.data() + img.slab_offset, live.empty() ? nullptr : live.data(), exchange,
-                     query_groups));
+                     query_groups, img.f32_rows));
     // hits of the catalog's search_top_k (WAL merge, shadowing, dedup) come from the shards
     catalog_->topk_override = [this](const float* q, uint32_t k, uint32_t* rows, float* scores, uint32_t* count) -> SearchError {
         Request rq;
@@ -653,6 +653,9 @@ SearchError ShardedIndex::begin(const Request& rq, uint32_t query_len, uint64_t*
     *ticket = 0;
     if (query_len != dim_)
         return make_err(FSGPU_ERR_DIMENSION_MISMATCH, "expected " + std::to_string(dim_) + ", found " + std::to_string(query_len));
+    // (the int8 / 4-bit two-pass stays F16-only, as on every shard's own index: refused before anything is enqueued)
+    if (f32_ && (rq.mode == kInt8TwoPass || rq.mode == kFourBitTwoPass))
+        return make_err(FSGPU_ERR_INVALID_CONFIG, "two-pass searches need an F16 slab");
     const bool two_pass = rq.mode == kInt8TwoPass || rq.mode == kFourBitTwoPass;
     const uint64_t cc = two_pass ? std::max<uint64_t>((uint64_t)rq.k * (rq.multiplier ? rq.multiplier : 1), rq.k) : rq.k;
     if (rq.nq && rq.k && nrows_) {

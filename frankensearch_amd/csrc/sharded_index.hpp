@@ -50,12 +50,13 @@ class ShardedIndex {
     // exchange: 0 = RCCL when it can be used (distinct devices, librccl loads), else peer copies; 1 = RCCL or fail;
     // 2 = peer copies (hipMemcpyAsync device-to-device into the root's gather buffer)
     // query_groups G (>= 1, divides ndev): ndev / G row shards, each resident on G devices (hybrid layout above)
+    // f32_rows: the slab holds raw little-endian f32 rows (Quantization::F32) instead of f16
     SearchError init_host(const int32_t* devices, uint32_t ndev, uint32_t dim, uint64_t nrows, const void* slab_f16,
-                          const uint64_t* live, int32_t exchange, uint32_t query_groups = 1);
+                          const uint64_t* live, int32_t exchange, uint32_t query_groups = 1, bool f32_rows = false);
     // shard_rows / slabs_dev / live_dev per DEVICE (rank); with query groups, rank r holds row shard r % (ndev / G)
     SearchError init_device(const int32_t* devices, uint32_t ndev, uint32_t dim, const uint64_t* shard_rows,
                             const void* const* slabs_dev, const uint64_t* const* live_dev, int32_t exchange, uint32_t query_groups = 1);
-    // VectorIndex::open for an FSVI v1 file (F16 slab), rows split over the devices; keeps the record table / doc ids / WAL
+    // VectorIndex::open for an FSVI v1 file (F16 or F32 slab), rows split over the devices; keeps the record table / doc ids / WAL
     SearchError open_fsvi(const char* path, const int32_t* devices, uint32_t ndev, int32_t exchange, uint32_t query_groups = 1);
 
     // what a search runs on every shard before the lists are exchanged
@@ -169,6 +170,7 @@ class ShardedIndex {
     uint32_t owner_of(uint64_t row) const;
 
     uint32_t dim_ = 0;
+    bool f32_ = false;   // Quantization::F32 shards: the two-pass modes are refused (they need an F16 slab)
     uint64_t nrows_ = 0;
     uint32_t groups_ = 1, row_shards_ = 1;
     std::vector<std::unique_ptr<Shard>> shards_;

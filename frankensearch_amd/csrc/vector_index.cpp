@@ -110,7 +110,7 @@ SearchError VectorIndex::init_host(int device, uint32_t dim, uint64_t nrows, con
 }
 
 SearchError VectorIndex::init_device(int device, uint32_t dim, uint64_t nrows, const void* slab_dev,
-                                     const uint64_t* live_dev, uint64_t row_base) {
+                                     const uint64_t* live_dev, uint64_t row_base, bool f32_rows) {
     if (dim == 0) return make_error(FSGPU_ERR_INVALID_CONFIG, "dimension must be greater than zero");
     if (nrows + row_base >= 0xffffffffull)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "row ids must fit in u32 (VectorHit.index)");
@@ -119,6 +119,7 @@ SearchError VectorIndex::init_device(int device, uint32_t dim, uint64_t nrows, c
     dim_ = dim;
     nrows_ = nrows;
     row_base_ = row_base;
+    f32_ = f32_rows;
     slab_dev_ = slab_dev;
     live_dev_ = live_dev;
     owns_slab_ = false;

@@ -50,7 +50,7 @@ class VectorIndex {
                           uint64_t row_base, bool f32_rows = false);
     bool f32_rows() const { return f32_; }
     SearchError init_device(int device, uint32_t dim, uint64_t nrows, const void* slab_dev, const uint64_t* live_dev,
-                            uint64_t row_base);
+                            uint64_t row_base, bool f32_rows = false);
     SearchError open_fsvi(const char* path, int device);
     // What open_fsvi leaves behind, from parts that never were a file (index_builder.cpp): the slab is a device allocation that
     // becomes this index's own, the tables are the file's record table in memory (hashes [nrows], offsets [nrows + 1] into blob).
@@ -367,10 +367,14 @@ class VectorIndex {
     // the int8 filter's copy of the slab, its scale word and statistics: the reference's own int8 slab (shared with the two-pass
     // search), or a ROTATED copy of its own (vector_index.cpp, "the int8 filter's copy of the slab")
     static constexpr double kRotateRatio = 9.0;   // max |element| x sqrt(dim) / max row norm above which the copy is rotated
-    bool filter_ready() const { return i8f_rot_ ? i8f_ready_ : (i8_ready_ && i8_stats_ready_); }
-    const void* filter_slab() const { return i8f_rot_ ? i8f_slab_.ptr : i8_slab_.ptr; }
-    const unsigned int* filter_max() const { return static_cast<const unsigned int*>(i8f_rot_ ? i8f_max_.ptr : i8_max_.ptr); }
-    const unsigned int* filter_stats() const { return static_cast<const unsigned int*>(i8f_rot_ ? i8f_stats_.ptr : i8_stats_.ptr); }
+    // (an F32 slab's copy is always one of its own, rotated or not: i8_slab_ is the reference's int8 slab of an F16 index, which the
+    // two-pass searches read and an F32 index does not have)
+    bool filter_own() const { return i8f_rot_ || f32_; }
+    bool filter_ready() const { return filter_own() ? i8f_ready_ : (i8_ready_ && i8_stats_ready_); }
+    const void* filter_slab() const { return filter_own() ? i8f_slab_.ptr : i8_slab_.ptr; }
+    const unsigned int* filter_max() const { return static_cast<const unsigned int*>(filter_own() ? i8f_max_.ptr : i8_max_.ptr); }
+    const unsigned int* filter_stats() const { return static_cast<const unsigned int*>(filter_own() ? i8f_stats_.ptr : i8_stats_.ptr); }
+    bool dense_rows() const { return !row_stride_ || row_stride_ == dim_ * (f32_ ? 4u : 2u); }   // not an MRL prefix view
     SearchError ensure_filter_copy(hipStream_t stream, bool must = false);   // decides the rotation on first use; builds what is missing
     SearchError prepare_filter_queries(const float* q, uint32_t nq, uint32_t nq_pad, uint32_t q_stride, void* qi8, float* delta, float* unit,
                                        hipStream_t stream);
@@ -426,7 +430,7 @@ class VectorIndex {
     const void* slab_dev_ = nullptr;
     const uint64_t* live_dev_ = nullptr;
     bool owns_slab_ = false;
-    bool f32_ = false;  // Quantization::F32 slab: served by the general path (f32_kernels.hip)
+    bool f32_ = false;  // Quantization::F32 slab: the exact kernels of f32_kernels.hip; batches through the int8 filter
     bool catalog_only_ = false;  // the tables of a sharded index: no device state of its own
     DeviceBuffer slab_own_, live_own_;
     hipStream_t stream_ = nullptr;
@@ -459,6 +463,7 @@ class VectorIndex {
     bool hard_batch_ = false;     // the batch in flight is the int8 filter's leftovers (nested f16-filter call)
     bool i8f_disabled_ = false;   // the int8 filter left too many queries uncertified on this slab (or its copy does not fit)
     uint32_t i8f_strikes_ = 0;
+    uint32_t i8f_fb_scratch_ = 0;   // a batch's fallback count when the caller asked for none (an F32 slab's filter accounting reads it)
     uint32_t cert_skip_ = 0, cert_backoff_ = 0;   // the lone query's single-pass certificate: calls still to skip / the current back-off
     uint32_t tp_skip_ = 0, tp_backoff_ = 0;       // ... and the two-pass searches' lone-caller lane
     // search_top_k_batched_device_begin / _end: the ticket being begun (-1: none), per ticket 0 free / 1 plan parked / 2 finished inside begin

@@ -29,27 +29,29 @@ SearchError VectorIndex::search_top_k_batched_device(const float* queries_dev, u
     // Which approximate scores filter the slab: the int8 slab on the integer matrix cores (half the bytes, half the MFMA
     // instructions of the f16 filter; a wider proven margin) unless this index has shown that its margin lets too many rows
     // through (outlier dimensions stretch the corpus-wide int8 scale), the caller forced one, or the shape is not covered.
-    const bool strided = row_stride_ && row_stride_ != dim_ * 2;
-    bool i8f = batched_filter != 1 && (batched_filter == 2 || !i8f_disabled_) && !f32_ && !strided && variant == 0 && knobs().filter != 1 &&
+    // (an F32 slab has the int8 filter and no other: its candidates are re-scored from the f32 rows, and without the filter the batch
+    // is answered by the exact f32 kernels — FSGPU_FILTER_F16 on such an index means exactly that)
+    const bool strided = !dense_rows();
+    bool i8f = batched_filter != 1 && (batched_filter == 2 || !i8f_disabled_) && !strided && variant == 0 && knobs().filter != 1 &&
                scan_mfma_supported((int)dim_) && k >= 1 && k <= 64 && nrows_ >= 4 * 8192ull;
     // a few queries are not worth BUILDING the int8 copy for; once it exists (or the host asked for the int8 latency path) they
     // are answered from it too: one query 0.88 ms against 1.29 ms on the exact kernel at 10M x 384
     if (batched_filter == 0 && knobs().filter == 0 && nq < 16 && !filter_ready() && !int8_latency) i8f = false;
     if (i8f && !filter_ready()) {
-        // the int8 copy of the slab (half its size again; rotated when the slab has outlier channels) is built on first use; no room
-        // for it: the f16 filter needs none
+        // the int8 copy of the slab (half an F16 slab's size again, a quarter of an F32 slab's; rotated when the slab has outlier
+        // channels) is built on first use; no room for it: the f16 filter (an F32 slab: the exact kernels) needs none
         FSGPU_TRY(ensure_filter_copy(stream));
         if (!filter_ready()) i8f = false;
     }
     if (i8f) {
         uint32_t refiltered = 0;
         SearchError e = batched_impl(queries_dev, nq, query_len, k, allow_dev, out_rows_dev, out_scores_dev, out_counts_dev, stream,
-                                     fallbacks, out_packed_dev, 0, 0, true, &refiltered);
+                                     fallbacks ? fallbacks : &i8f_fb_scratch_, out_packed_dev, 0, 0, true, &refiltered);
         if (e.ok() && async_want_ >= 0 && async_state_[async_want_] == 1) {
             async_i8f_[async_want_] = true;   // (the bookkeeping below happens in _end, once the verdicts are in)
             return e;
         }
-        if (e.ok()) i8f_account(nq, refiltered);
+        if (e.ok()) i8f_account(nq, f32_ ? (fallbacks ? *fallbacks : i8f_fb_scratch_) : refiltered);
         return e;
     }
     return batched_impl(queries_dev, nq, query_len, k, allow_dev, out_rows_dev, out_scores_dev, out_counts_dev, stream,
@@ -67,10 +69,11 @@ SearchError VectorIndex::prepare_int8_latency() {
     return ok();
 }
 
-// What a batch's verdicts teach the index about its int8 filter.
+// What a batch's verdicts teach the index about its int8 filter.  refiltered = the queries it could not certify: handed on to the
+// f16 filter, or — an F32 slab, which has none — answered by the exact f32 kernels (fallbacks, not counted as re-filtered).
 void VectorIndex::i8f_account(uint32_t nq, uint32_t refiltered) {
     i8f_queries += nq;
-    i8f_refiltered += refiltered;
+    if (!f32_) i8f_refiltered += refiltered;
     // What overflows on a corpus with a dense score tail (outlier dimensions, big clusters) is the MAIN pass's lists: the rows within
     // the margin of the k-th best number a few hundred whatever the corpus size, but the main pass runs on the threshold of a 1/25
     // sample and lets N / RB times as many through (scripts/r04/i8_bound_study.py).  A handful of leftovers already costs a pass of
@@ -80,7 +83,7 @@ void VectorIndex::i8f_account(uint32_t nq, uint32_t refiltered) {
     //     (scripts/r04/outlier_census.py) 150 of 1,024 queries were handed on at the base sample, 69 at 2 x, 580 at 4 x — the larger
     //     sample's own selection then overflows its candidate pool;
     //   * an eighth of a batch still handed on twice in a row: the index gives the int8 filter up for the f16 filter (unless the
-    //     caller pinned the filter).
+    //     caller pinned the filter) — on an F32 slab, for the exact f32 kernels.
     // Since round 5 a slab with outlier channels gets a ROTATED int8 copy (ensure_filter_copy), which removes the usual cause.
     if (nq >= wide_min_queries() && i8f_sample_boost_ < 2 && (uint64_t)refiltered * 64 > nq) {
         i8f_sample_boost_ *= 2;
@@ -95,8 +98,8 @@ void VectorIndex::i8f_account(uint32_t nq, uint32_t refiltered) {
 SearchError VectorIndex::int8_filter_bound(const float* queries, uint32_t nq, uint32_t query_len, float* out_delta,
                                            float* out_query_scale, float* out_slab_scale, int8_t* out_queries_i8, int8_t* out_slab_i8) {
     FSGPU_TRY(ensure_query_dimension(query_len));
-    if (f32_ || (row_stride_ && row_stride_ != dim_ * 2) || nrows_ == 0 || nrows_ > 0xffffffffull)
-        return make_error(FSGPU_ERR_INVALID_CONFIG, "the int8 filter serves f16 slabs only");
+    if (!dense_rows() || nrows_ == 0 || nrows_ > 0xffffffffull)
+        return make_error(FSGPU_ERR_INVALID_CONFIG, "the int8 filter serves dense, non-empty slabs only");
     FSGPU_HIP(hipSetDevice(device_));
     FSGPU_TRY(ensure_filter_copy(stream_, true));
     if (!filter_ready()) return make_error(FSGPU_ERR_DEVICE, "no room for the int8 copy of the slab");
@@ -189,9 +192,9 @@ void make_rotation(uint32_t dim, std::vector<double>& rt, double* ortho_err) {
 
 SearchError VectorIndex::ensure_filter_copy(hipStream_t stream, bool must) {
     if (filter_ready()) return ok();
-    const bool strided = row_stride_ && row_stride_ != dim_ * 2;
-    if (f32_ || strided || nrows_ == 0) return ok();
+    if (!dense_rows() || nrows_ == 0) return ok();
     FSGPU_HIP(hipSetDevice(device_));
+    const float* slab32 = static_cast<const float*>(slab_dev_);   // (an F32 slab's rows)
     if (!i8f_decided_) {
         // rotate? the slab's largest |element| against the largest row norm spread evenly over the dimensions: a Gaussian-like row
         // has max ~ 6 / sqrt(dim) of its norm (and so has every rotated row), the bench's outlier corpus 17.6 / sqrt(dim)
@@ -202,8 +205,14 @@ SearchError VectorIndex::ensure_filter_copy(hipStream_t stream, bool must) {
         if (filter_rotation == 0 && rot_shape) {
             FSGPU_TRY(i8f_max_.reserve(8));
             unsigned int* w = static_cast<unsigned int*>(i8f_max_.ptr);
-            FSGPU_HIP(launch_slab_maxabs(slab_dev_, (size_t)nrows_ * dim_, w, stream));
-            FSGPU_HIP(launch_max_row_norm(slab_dev_, (uint32_t)nrows_, dim_, 0, w + 1, stream));
+            if (f32_) {
+                FSGPU_HIP(hipMemsetAsync(w, 0, 4, stream));   // (launch_maxabs_f32 accumulates)
+                FSGPU_HIP(launch_maxabs_f32(slab32, (size_t)nrows_ * dim_, w, stream));
+                FSGPU_HIP(launch_max_row_norm_f32(slab32, (uint32_t)nrows_, dim_, w + 1, stream));
+            } else {
+                FSGPU_HIP(launch_slab_maxabs(slab_dev_, (size_t)nrows_ * dim_, w, stream));
+                FSGPU_HIP(launch_max_row_norm(slab_dev_, (uint32_t)nrows_, dim_, 0, w + 1, stream));
+            }
             float host[2] = {0.f, 0.f};
             FSGPU_HIP(hipMemcpyAsync(host, w, 8, hipMemcpyDeviceToHost, stream));
             FSGPU_HIP(hipStreamSynchronize(stream));
@@ -213,7 +222,7 @@ SearchError VectorIndex::ensure_filter_copy(hipStream_t stream, bool must) {
         i8f_rot_ = rot;
         i8f_decided_ = true;
     }
-    if (!i8f_rot_) {
+    if (!i8f_rot_ && !f32_) {
         if (!i8_ready_) {
             if (!i8_slab_.reserve((size_t)nrows_ * dim_).ok()) {   // no room for the copy: the f16 paths need none
                 (void)hipGetLastError();
@@ -236,40 +245,48 @@ SearchError VectorIndex::ensure_filter_copy(hipStream_t stream, bool must) {
     }
     // the rotated copy: R (f64, transposed) -> two passes over the slab in chunks of rows — max-abs of the rotated values, then
     // quantise + statistics — through a chunk-sized f32 staging buffer
+    // An F32 slab's copy is built the same way and lives in the same members whether it is rotated or not (i8_slab_ is the reference's
+    // int8 slab of an F16 index and stays untouched: the two-pass searches refuse F32); unrotated, its chunks ARE f32 rows and go
+    // straight from the slab through the same quantiser and statistics, with no staging buffer.
     if (!i8f_slab_.reserve((size_t)nrows_ * dim_).ok()) {
         (void)hipGetLastError();
         if (must) return make_error(FSGPU_ERR_DEVICE, "no room for the int8 copy of the slab");
         i8f_disabled_ = true;
         return ok();
     }
-    std::vector<double> rt;
-    double ortho_err = 0.0;
-    make_rotation(dim_, rt, &ortho_err);
-    rot_extra_coeff_ = (ortho_err + 2.01 * 5.9604644775390625e-8) * 1.001;   // |R^T R - I| + 2.01 x 2^-24 (two roundings to f32)
-    FSGPU_TRY(rot_mat_.reserve(rt.size() * 8));
-    FSGPU_HIP(hipMemcpyAsync(rot_mat_.ptr, rt.data(), rt.size() * 8, hipMemcpyHostToDevice, stream));
-    FSGPU_HIP(hipStreamSynchronize(stream));   // rt is a local
+    if (i8f_rot_) {
+        std::vector<double> rt;
+        double ortho_err = 0.0;
+        make_rotation(dim_, rt, &ortho_err);
+        rot_extra_coeff_ = (ortho_err + 2.01 * 5.9604644775390625e-8) * 1.001;   // |R^T R - I| + 2.01 x 2^-24 (two roundings to f32)
+        FSGPU_TRY(rot_mat_.reserve(rt.size() * 8));
+        FSGPU_HIP(hipMemcpyAsync(rot_mat_.ptr, rt.data(), rt.size() * 8, hipMemcpyHostToDevice, stream));
+        FSGPU_HIP(hipStreamSynchronize(stream));   // rt is a local
+    }
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(nrows_, 1u << 18);
     DeviceBuffer tmp;
-    FSGPU_TRY(tmp.reserve((size_t)chunk * dim_ * 4));
+    if (i8f_rot_) FSGPU_TRY(tmp.reserve((size_t)chunk * dim_ * 4));
     FSGPU_TRY(i8f_max_.reserve(8));
     FSGPU_TRY(i8f_stats_.reserve(16));
     unsigned int* maxw = static_cast<unsigned int*>(i8f_max_.ptr);
     unsigned int* stats = static_cast<unsigned int*>(i8f_stats_.ptr);
-    const double* rmat = static_cast<const double*>(rot_mat_.ptr);
+    const double* rmat = i8f_rot_ ? static_cast<const double*>(rot_mat_.ptr) : nullptr;
     float* t32 = static_cast<float*>(tmp.ptr);
     const unsigned char* slab8 = static_cast<const unsigned char*>(slab_dev_);
     SearchError err;
     auto pass = [&](bool second) -> SearchError {
         for (uint64_t r0 = 0; r0 < nrows_; r0 += chunk) {
             const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, nrows_ - r0);
-            FSGPU_HIP(launch_rotate_rows_f16(slab8 + (size_t)r0 * dim_ * 2, n, dim_, rmat, t32, stream));
+            const float* src = t32;
+            if (!i8f_rot_) src = slab32 + (size_t)r0 * dim_;
+            else if (f32_) FSGPU_HIP(launch_rotate_rows_f32(slab32 + (size_t)r0 * dim_, n, dim_, dim_, rmat, t32, stream));
+            else FSGPU_HIP(launch_rotate_rows_f16(slab8 + (size_t)r0 * dim_ * 2, n, dim_, rmat, t32, stream));
             if (!second) {
-                FSGPU_HIP(launch_maxabs_f32(t32, (size_t)n * dim_, maxw, stream));
+                FSGPU_HIP(launch_maxabs_f32(src, (size_t)n * dim_, maxw, stream));
             } else {
                 signed char* dst = static_cast<signed char*>(i8f_slab_.ptr) + (size_t)r0 * dim_;
-                FSGPU_HIP(launch_quantize_f32_i8(t32, (size_t)n * dim_, maxw, dst, stream));
-                FSGPU_HIP(launch_i8_stats_f32(t32, dst, n, dim_, maxw, stats, stream));
+                FSGPU_HIP(launch_quantize_f32_i8(src, (size_t)n * dim_, maxw, dst, stream));
+                FSGPU_HIP(launch_i8_stats_f32(src, dst, n, dim_, maxw, stats, stream));
             }
         }
         return ok();
@@ -406,7 +423,8 @@ SearchError VectorIndex::two_pass_candidates_device_end(int32_t ticket, uint32_t
 // int8_mult == 0: f16 slab, f16-rounded queries, approximate scores + proven margin (mfma_scan.hip header).
 // int8_mult >= 1: int8 slab, int8 queries, exact integer scores; the k * int8_mult best rows are the candidates.
 // i8_filter (int8_mult == 0): int8 slab and queries as the FILTER of the exact search — integer scores + the proven margin of
-//                 prepare_queries_i8_filter_kernel; queries it cannot certify are re-filtered on the f16 path (*refiltered).
+//                 prepare_queries_i8_filter_kernel; queries it cannot certify are re-filtered on the f16 path (*refiltered) — on an
+//                 F32 slab, whose candidates are re-scored from f32 rows and which has no f16 path, answered by the exact f32 kernels.
 
 // What one call fixes for all its rounds: the arguments, the sample sizes, the workspaces.
 struct VectorIndex::BatchedPlan {
@@ -609,9 +627,10 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     uint64_t cc64 = std::min<uint64_t>((uint64_t)k * (p.int8_mult ? p.int8_mult : 1), nrows_);
     cc64 = std::max<uint64_t>(cc64, std::min<uint64_t>(k, nrows_));
     p.ksel = p.int8_mult ? (uint32_t)std::min<uint64_t>(cc64, 0xffffffffull) : k;  // rank that anchors the selections
-    p.strided = row_stride_ && row_stride_ != dim_ * 2;   // an MRL prefix view
+    p.strided = !dense_rows();   // an MRL prefix view
     const bool usable = scan_mfma_supported((int)dim_) && k >= 1 && k <= 64 && p.ksel <= kSelectMaxK && nrows_ >= 4 * (uint64_t)RA && variant != 4 &&
-                        !f32_ && (!p.strided || (!p.i8 && p.qs >= dim_)) && (p.query_stride == 0 || !p.i8);
+                        (!f32_ || (p.i8f && !p.strided)) && (!p.strided || (!p.i8 && p.qs >= dim_)) && (p.query_stride == 0 || !p.i8);
+    // (an F32 slab: the int8 filter only — there is no f16-row filter for it, and the int8 two-pass stays F16-only)
     if (!usable) {
         *done = true;
         return batched_unusable(p);
@@ -902,6 +921,7 @@ SearchError VectorIndex::batched_sample(const BatchedPlan& p, BatchedRound& r) {
             g.row_base = (uint32_t)row_base_;
             g.query_stride = p.qs;
             g.hreduce = hreduce;
+            g.slab_f32 = f32_ ? 1u : 0u;
             g.valid_queries = r.ng;
             g.rank_only = r.anchor ? 0u : 1u;
             FSGPU_HIP(launch_select_groups(g, (int)QP, stream));
@@ -949,6 +969,7 @@ SearchError VectorIndex::batched_sample(const BatchedPlan& p, BatchedRound& r) {
         x.nrows = N;
         x.row_base = (uint32_t)row_base_;
         x.hreduce = hreduce;
+        x.slab_f32 = f32_ ? 1u : 0u;
         x.k_out = p.k_eff;
     };
     // (a wide round's second sample only anchors the main pass's threshold — that pass visits every row — so it may take ANY
@@ -1181,6 +1202,7 @@ SearchError VectorIndex::batched_finish(BatchedPlan& p, BatchedRound& r) {
     sb.nrows = p.N;
     sb.row_base = (uint32_t)row_base_;
     sb.hreduce = hreduce;
+    sb.slab_f32 = f32_ ? 1u : 0u;
     sb.k_out = p.k_eff;
     sb.out_stride = k;
     sb.out_rows = p.out_rows_dev ? p.out_rows_dev + (size_t)g0 * k : nullptr;
@@ -1279,7 +1301,8 @@ SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
         FSGPU_HIP(hipMemcpyAsync(idx_dev, fb.data(), nf * 4, hipMemcpyHostToDevice, stream));
         FSGPU_HIP(hipStreamSynchronize(stream));  // fb is a stack-owned pageable buffer
         FSGPU_HIP(launch_gather_queries(p.queries_dev, idx_dev, (uint32_t)nf, dim_, p.qs, q_dev, stream));
-        if (p.i8f && nf > 8) {
+        // (an F32 slab has no f16 filter: its leftovers go straight to the exact f32 kernels below, as fallbacks)
+        if (p.i8f && nf > 8 && !f32_) {
             // rows within the int8 margin of the k-th best did not fit the lists (or the query cannot be certified on the int8
             // slab at all): the f16 filter, whose margin is ~20 x narrower, answers these as a batch of its own
             uint32_t inner_fb = 0;
@@ -1294,7 +1317,7 @@ SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
                                           p.out_scores_dev, p.out_counts_dev, reinterpret_cast<u64*>(p.out_packed_dev), stream));
             return ok();
         }
-        if (p.i8f && p.refiltered) *p.refiltered = (uint32_t)nf;
+        if (p.i8f && p.refiltered && !f32_) *p.refiltered = (uint32_t)nf;
         FSGPU_TRY(fused_search(q_dev, (uint32_t)nf, k, k_eff, p.allow_dev, rows_dev, scores_dev, counts_dev, nullptr, stream));
         FSGPU_HIP(launch_scatter_hits(idx_dev, (uint32_t)nf, k, rows_dev, scores_dev, counts_dev, p.out_rows_dev,
                                       p.out_scores_dev, p.out_counts_dev, reinterpret_cast<u64*>(p.out_packed_dev), stream));
@@ -1347,7 +1370,7 @@ SearchError VectorIndex::search_top_k_batched_device_end(int32_t ticket, uint32_
         p.fallbacks = &async_fb_[t];
         async_state_[t] = 0;   // (before the fallback: it may search again, blocking, on this index)
         FSGPU_TRY(batched_fallback(p, true));
-        if (async_i8f_[t]) i8f_account(async_nq_[t], refiltered);
+        if (async_i8f_[t]) i8f_account(async_nq_[t], f32_ ? async_fb_[t] : refiltered);
         // queries whose hits were written by work enqueued HERE, behind everything begin enqueued: answered by the exact kernels
         // (counted in *fallbacks) or handed by the int8 filter to the f16 filter (re-filtered: certified there, so NOT a fallback) — a
         // caller that chained work to begin's last kernel (a shard's exchange) has to chain it again behind these

@@ -120,6 +120,27 @@ class VectorIndex:
         return cls(h.value, keepalive)
 
     @classmethod
+    def from_slab_f32(cls, slab_f32: np.ndarray, live: Optional[np.ndarray] = None, device: int = 0,
+                      row_base: int = 0) -> "VectorIndex":
+        """slab_f32: [N, dim] float32 (raw little-endian f32 rows: a Quantization::F32 slab, lib.rs:203-208)."""
+        slab = np.ascontiguousarray(slab_f32)
+        if slab.dtype != np.float32 or slab.ndim != 2:
+            raise TypeError("slab must be a 2-D float32 array")
+        bm = pack_bitmap(live) if live is not None else None
+        h = C.c_void_p()
+        check(_lib.lib().fsgpu_index_create_f32(device, slab.shape[1], slab.shape[0], _ptr(slab), _ptr(bm), row_base,
+                                                C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_device_slab_f32(cls, data_ptr: int, nrows: int, dim: int, live_ptr: Optional[int] = None, device: int = 0,
+                             row_base: int = 0, keepalive=None) -> "VectorIndex":
+        """Adopts a device-resident F32 slab (e.g. a float32 torch tensor's data_ptr()); `keepalive` pins its owner."""
+        h = C.c_void_p()
+        check(_lib.lib().fsgpu_index_create_f32_device(device, dim, nrows, data_ptr, live_ptr, row_base, C.byref(h)))
+        return cls(h.value, keepalive)
+
+    @classmethod
     def open(cls, path: str, device: int = 0) -> "VectorIndex":
         """VectorIndex::open for an FSVI v1 / F16 file."""
         h = C.c_void_p()

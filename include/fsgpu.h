@@ -106,6 +106,13 @@ fsgpu_status fsgpu_index_create(int32_t device, uint32_t dim, uint64_t nrows, co
 /* Zero-copy variant: adopts (does not free) a device-resident slab / bitmap. */
 fsgpu_status fsgpu_index_create_device(int32_t device, uint32_t dim, uint64_t nrows, const void *slab_f16_dev,
                                        const uint64_t *live_bitmap_dev, uint64_t row_base, fsgpu_index **out);
+/* The same two doors for a Quantization::F32 slab (lib.rs:203-208; rows are raw little-endian f32, scored in
+ * dot_product_f32_bytes_f32's order, simd.rs:581-702): an f32 matrix the caller holds becomes an index without a detour through an
+ * FSVI file or the index builder.  Everything an FSVI-opened F32 index does, these do. */
+fsgpu_status fsgpu_index_create_f32(int32_t device, uint32_t dim, uint64_t nrows, const void *slab_f32_le,
+                                    const uint64_t *live_bitmap, uint64_t row_base, fsgpu_index **out);
+fsgpu_status fsgpu_index_create_f32_device(int32_t device, uint32_t dim, uint64_t nrows, const void *slab_f32_dev,
+                                           const uint64_t *live_bitmap_dev, uint64_t row_base, fsgpu_index **out);
 /* VectorIndex::open for an FSVI v1 / F16 file (lib.rs:4049-4144 header+CRC, :3510-3537 record table):
  * uploads the slab, builds the live bitmap from record flags, keeps the doc-id table on the host. */
 fsgpu_status fsgpu_index_open_fsvi(const char *path, int32_t device, fsgpu_index **out);
@@ -241,11 +248,15 @@ fsgpu_status fsgpu_search_topk_device(fsgpu_index *idx, const float *queries_dev
  * fsgpu_search_topk.  Queries the batched path cannot certify (k > 64, unsupported dimension, margin overflow) are
  * answered by the exact kernels; *out_fallbacks (optional) counts them.  The _device form synchronises hip_stream. */
 /* The filter those passes score with is chosen per index (FSGPU_FILTER_AUTO): batches of 16 queries and more are
- * filtered on an int8 copy of the slab (built on first use, half the slab's size again; v_mfma_i32_16x16x64_i8: half the
- * bytes and half the matrix instructions per row) under a bound measured from the slab and each query (mfma_scan.hip,
- * prepare_queries_i8_filter_kernel); queries whose margin lets too many rows through are re-filtered on the f16 slab, and an
- * index where that happens to more than 1/8 of a batch twice in a row (or that has no room for the copy) stays with the
- * f16 filter.  Either way the emitted rows and score bits are the exact search's. */
+ * filtered on an int8 copy of the slab (built on first use, half an F16 slab's size again, a quarter of an F32 slab's;
+ * v_mfma_i32_16x16x64_i8: half the bytes and half the matrix instructions per f16 row) under a bound measured from the slab and each
+ * query (mfma_scan.hip, prepare_queries_i8_filter_kernel); queries whose margin lets too many rows through are re-filtered on the f16
+ * slab, and an index where that happens to more than 1/8 of a batch twice in a row (or that has no room for the copy) stays with the
+ * f16 filter.  Either way the emitted rows and score bits are the exact search's.
+ * An F32 slab (Quantization::F32) has the int8 filter and no f16 one: its candidates are re-scored from the f32 rows in
+ * dot_product_f32_bytes_f32's order, queries the int8 filter cannot certify go straight to the exact f32 kernels (counted in
+ * *out_fallbacks, not as re-filtered), and FSGPU_FILTER_F16 — or an index that gave the int8 filter up — means those kernels for the
+ * whole batch.  The int8 two-pass searches stay F16-only, as in the reference (search.rs:579-585). */
 #define FSGPU_FILTER_AUTO 0
 #define FSGPU_FILTER_F16 1
 #define FSGPU_FILTER_INT8 2
@@ -281,8 +292,9 @@ fsgpu_status fsgpu_index_batched_filter_stats(fsgpu_index *idx, uint64_t *int8_q
                                               int32_t *int8_active);
 /* The int8 filter's certificate, for inspection (tests/test_gpu_int8_filter.py checks it against float64 arithmetic): per
  * query the bound out_delta[q] >= |int8 score - exact score * slab scale * query scale| over every row (< 0: the query
- * cannot be certified and goes to the f16 filter), the scales 127 / max|q| and 127 / max|x|, the quantised queries
- * [nq, dim] and the int8 slab [rows, dim] (any output may be null).  Builds the int8 copy if it does not exist yet. */
+ * cannot be certified and goes to the f16 filter — on an F32 slab, to the exact kernels), the scales 127 / max|q| and 127 / max|x|, the quantised queries
+ * [nq, dim] and the int8 slab [rows, dim] (any output may be null).  Builds the int8 copy if it does not exist yet.  Serves F16
+ * and F32 slabs with dense rows (tests/test_gpu_f32_batched.py checks the F32 form the same way). */
 fsgpu_status fsgpu_index_int8_filter_bound(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_len,
                                            float *out_delta, float *out_query_scale, float *out_slab_scale,
                                            int8_t *out_queries_i8, int8_t *out_slab_i8);
@@ -531,8 +543,9 @@ fsgpu_status fsgpu_sharded_set_coalescing(fsgpu_sharded *idx, uint32_t max_batch
 fsgpu_status fsgpu_sharded_coalescing_stats(fsgpu_sharded *idx, uint64_t *batches, uint64_t *requests);
 /* the corpus-wide max-abs the shards' int8 / 4-bit copies are built from (0 before the first two-pass search) */
 float fsgpu_sharded_quant_scale_max(const fsgpu_sharded *idx);
-/* VectorIndex::open (lib.rs:1747-1909) of an FSVI v1 file with an F16 slab, rows split over the devices.  The handle keeps the
- * record table, the doc-id strings and the tombstone flags, so the doc-id level calls below work as on fsgpu_index. */
+/* VectorIndex::open (lib.rs:1747-1909) of an FSVI v1 file (F16 or F32 slab), rows split over the devices.  The handle keeps the
+ * record table, the doc-id strings and the tombstone flags, so the doc-id level calls below work as on fsgpu_index.  On an F32 file
+ * the two-pass modes are refused (FSGPU_ERR_INVALID_CONFIG, "two-pass searches need an F16 slab"); the exact and batched modes serve it. */
 fsgpu_status fsgpu_sharded_open_fsvi(const char *path, const int32_t *devices, uint32_t ndev, int32_t exchange, fsgpu_sharded **out);
 fsgpu_status fsgpu_sharded_open_fsvi_grouped(const char *path, const int32_t *devices, uint32_t ndev, uint32_t query_groups,
                                              int32_t exchange, fsgpu_sharded **out);

@@ -1,7 +1,11 @@
-"""Every kernel of the shipped libfsgpu.so whose metadata note reports spilled registers (vgpr / sgpr) or a private segment."""
+"""Every kernel of the shipped libfsgpu.so whose metadata note reports spilled registers (vgpr / sgpr) or a private segment.
+
+list_spills.py [library or object] [regex]: with a regex, every kernel whose DEMANGLED name matches it is listed too, spills or not
+(the register figures of a family of instantiations, e.g. 'select_(groups_)?kernel')."""
 import os, re, struct, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "frankensearch_amd", "libfsgpu.so")
+also = re.compile(sys.argv[2]) if len(sys.argv) > 2 else None
 LL = "/opt/rocm/lib/llvm/bin/"
 with tempfile.TemporaryDirectory() as td:
     fat = os.path.join(td, "fat.bin")
@@ -28,7 +32,8 @@ with tempfile.TemporaryDirectory() as td:
                 g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", item).group(1))
                 name = re.search(r"\.name:\s+(\S+)", item).group(1)
                 total += 1
-                if g("vgpr_spill_count") or g("sgpr_spill_count") or g("private_segment_fixed_size"):
+                wanted = also is not None and also.search(subprocess.run(["c++filt", name], capture_output=True, text=True).stdout)
+                if wanted or g("vgpr_spill_count") or g("sgpr_spill_count") or g("private_segment_fixed_size"):
                     rows.append((name, g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"), g("private_segment_fixed_size")))
         at = blob.find(magic, at + 1)
     dem = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.split("\n")
