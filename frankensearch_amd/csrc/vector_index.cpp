@@ -14,7 +14,6 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <type_traits>
 
 #include "../../include/fsgpu.h"
 #include "lab_env.hpp"
@@ -54,14 +53,16 @@ void DeviceBuffer::release() {
 // VectorIndex
 // ------------------------------------------------------------------------------------------------
 
+VectorIndex::VectorIndex() : tickets_(new BatchedTicket[2]) {}
+
 VectorIndex::~VectorIndex() {
     if (device_ >= 0) (void)hipSetDevice(device_);
     for (auto& ev : events_) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
     }
-    for (hipEvent_t& e : async_ev_)
-        if (e) (void)hipEventDestroy(e);
+    for (int t = 0; t < 2; ++t)
+        if (tickets_[t].event) (void)hipEventDestroy(tickets_[t].event);
     if (stream_) (void)hipStreamDestroy(stream_);
     for (DeviceBuffer* b : {&slab_own_, &live_own_, &ws_partial_, &ws_queries_, &ws_allow_, &ws_rows_, &ws_scores_,
                             &ws_counts_, &ws_keys_a_, &ws_keys_b_, &ws_sort_tmp_, &ws_gather_rows_, &ws_gather_out_,
@@ -127,7 +128,7 @@ SearchError VectorIndex::init_device(int device, uint32_t dim, uint64_t nrows, c
 }
 
 SearchError VectorIndex::set_live_bitmap(const uint64_t* live) {
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
+    if (any_search_parked())   // (its kernels read the live bitmap this call would rewrite)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     invalidate_hits_state(false);
     if (!live) {
@@ -594,7 +595,7 @@ float VectorIndex::wal_dot(size_t wal_index, const float* query) const {
 SearchError VectorIndex::soft_delete(const char* doc_id, uint32_t len, int32_t* deleted) {
     *deleted = 0;
     if (doc_offsets_.empty()) return make_error(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
+    if (any_search_parked())   // (its kernels read the live bitmap this call would rewrite)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     FSGPU_TRY(fetch_live_host());
     const uint64_t h = fnv1a(doc_id, len);
@@ -1265,9 +1266,11 @@ SearchError VectorIndex::mrl_search_batched(const float* queries, uint32_t nq, u
     FSGPU_HIP(hipMemcpyAsync(q_dev, queries, (size_t)nq * dim_ * 4, hipMemcpyHostToDevice, stream_));
     FSGPU_HIP(hipMemsetAsync(zero, 0, (size_t)nq * 4, stream_));
     view->hreduce = hreduce;
-    uint32_t fb = 0;
-    FSGPU_TRY(view->batched_impl(q_dev, nq, search_dims, rtop, nullptr, nullptr, nullptr, nullptr, stream_, &fb,
-                                 reinterpret_cast<uint64_t*>(packed), 0, dim_, false, nullptr));
+    BatchedRequest scan(q_dev, nq, search_dims, rtop, stream_);
+    scan.out_packed_dev = reinterpret_cast<uint64_t*>(packed);
+    scan.query_stride = dim_;
+    BatchedOutcome scanned;
+    FSGPU_TRY(view->batched_impl(scan, &scanned));
     for (auto& ev : view->events_) events_.push_back(ev);   // the view's timed launches count as this index's
     view->events_.clear();
     profiled_rows_ += view->profiled_rows_;
@@ -1300,7 +1303,7 @@ SearchError VectorIndex::mrl_search_batched(const float* queries, uint32_t nq, u
     FSGPU_HIP(hipMemcpyAsync(out_scores, scores_dev, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream_));
     FSGPU_HIP(hipMemcpyAsync(out_counts, counts_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, stream_));
     FSGPU_HIP(hipStreamSynchronize(stream_));
-    if (fallbacks) *fallbacks = fb;
+    if (fallbacks) *fallbacks = scanned.fallbacks;
     return ok();
 }
 

@@ -39,7 +39,7 @@ SearchError write_fsvi_v1(const char* path, const char* embedder_id, const char*
 
 class VectorIndex {
   public:
-    VectorIndex() = default;
+    VectorIndex();
     ~VectorIndex();
     VectorIndex(const VectorIndex&) = delete;
     VectorIndex& operator=(const VectorIndex&) = delete;
@@ -116,11 +116,8 @@ class VectorIndex {
     // Shard-local HALF of a two-pass search (bits 8: search_top_k_int8_two_pass, 4: search_top_k_4bit_two_pass) for a row-sharded
     // index: this shard's cc = max(k * multiplier, k) pass-1 candidates per query as two aligned packed lists [nq, cc] — position
     // i is one row: its pass-1 entry (integer score as f32 bits | global row) and its exact entry; kEmpty beyond the candidates.
-    // The root repeats the selection over all shards' candidates (launch_two_pass_merge).  Synchronises the stream.
-    SearchError two_pass_candidates_device(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
-                                           uint32_t multiplier, int bits, uint64_t* approx_out_dev, uint64_t* exact_out_dev,
-                                           hipStream_t stream, uint32_t* fallbacks);
-    // ... in two halves (the tickets of search_top_k_batched_device_begin / _end): nothing is waited for in begin
+    // The root repeats the selection over all shards' candidates (launch_two_pass_merge).  In two halves (the tickets of
+    // search_top_k_batched_device_begin / _end): nothing is waited for in begin.
     SearchError two_pass_candidates_device_begin(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
                                                  uint32_t multiplier, int bits, uint64_t* approx_out_dev, uint64_t* exact_out_dev,
                                                  hipStream_t stream, int32_t* ticket);
@@ -331,20 +328,21 @@ class VectorIndex {
     SearchError ensure_query_dimension(uint32_t query_len) const;
     SearchError open_fsvi_impl(const char* path, int device, FsviImage* image);
     void* pinned_io();
-    SearchError batched_impl(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k, const uint64_t* allow_dev,
-                             uint32_t* out_rows_dev, float* out_scores_dev, uint32_t* out_counts_dev, hipStream_t stream,
-                             uint32_t* fallbacks, uint64_t* out_packed_dev, uint32_t int8_mult, uint32_t query_stride,
-                             bool i8_filter, uint32_t* refiltered, int bits = 8);
-    // ... and its stages (vector_index.cpp): what a call fixes for all its rounds, one round's geometry and arguments
+    // The batched search (vector_index_batched.cpp): its request, outcome, plan, round and ticket are defined in vector_index_internal.hpp
+    struct BatchedRequest;
+    struct BatchedOutcome;
     struct BatchedPlan;
     struct BatchedRound;
-    SearchError batched_prepare(BatchedPlan& p, bool* done);
-    SearchError batched_unusable(BatchedPlan& p);
+    struct BatchedTicket;
+    SearchError batched_impl(const BatchedRequest& rq, BatchedOutcome* out);
+    SearchError batched_exact(BatchedRequest& rq, BatchedOutcome* out);   // picks the filter of the exact search, keeps its accounts
+    SearchError batched_prepare(BatchedPlan& p, bool* usable);
+    SearchError batched_unusable(const BatchedPlan& p, BatchedOutcome* out);
     SearchError batched_round_setup(const BatchedPlan& p, BatchedRound& r, uint32_t g0);
     SearchError batched_sample(const BatchedPlan& p, BatchedRound& r);
     SearchError batched_main(const BatchedPlan& p, BatchedRound& r);
-    SearchError batched_finish(BatchedPlan& p, BatchedRound& r);
-    SearchError batched_fallback(BatchedPlan& p, bool already_waited = false);
+    SearchError batched_finish(const BatchedPlan& p, BatchedRound& r);
+    SearchError batched_fallback(const BatchedPlan& p, BatchedOutcome* out, bool already_waited = false);
     void i8f_account(uint32_t nq, uint32_t refiltered);
     SearchError quantized_two_pass(const float* query, uint32_t query_len, uint32_t k, uint32_t multiplier, int bits,
                                    uint32_t* out_rows, float* out_scores, uint32_t* out_count, u64* approx_out_dev = nullptr,
@@ -365,7 +363,7 @@ class VectorIndex {
     SearchError two_pass_lone_check(uint32_t* rows, float* scores, uint32_t* count, u64* approx_out, u64* exact_out, bool* answered);
     SearchError ensure_two_pass_slab(int bits, const void** qslab);
     // the int8 filter's copy of the slab, its scale word and statistics: the reference's own int8 slab (shared with the two-pass
-    // search), or a ROTATED copy of its own (vector_index.cpp, "the int8 filter's copy of the slab")
+    // search), or a ROTATED copy of its own (vector_index_batched.cpp, "the int8 filter's copy of the slab")
     static constexpr double kRotateRatio = 9.0;   // max |element| x sqrt(dim) / max row norm above which the copy is rotated
     // (an F32 slab's copy is always one of its own, rotated or not: i8_slab_ is the reference's int8 slab of an F16 index, which the
     // two-pass searches read and an F32 index does not have)
@@ -457,23 +455,15 @@ class VectorIndex {
                                uint32_t* out_counts, uint32_t* fallbacks, bool queries_on_device, uint32_t multiplier, int bits);
     bool i8_ready_ = false, n4_ready_ = false, i8_stats_ready_ = false, n4u_ready_ = false;
     bool quant_max_ready_ = false;   // i8_max_ holds a corpus-wide max-abs handed in by a sharded index: the quantisers keep it
-    u64* tp_approx_out_ = nullptr;   // two_pass_candidates_device: where the batch in flight leaves its candidate pairs
-    u64* tp_exact_out_ = nullptr;
-    uint32_t tp_stride_ = 0;         // entries between queries in both
-    bool hard_batch_ = false;     // the batch in flight is the int8 filter's leftovers (nested f16-filter call)
     bool i8f_disabled_ = false;   // the int8 filter left too many queries uncertified on this slab (or its copy does not fit)
     uint32_t i8f_strikes_ = 0;
-    uint32_t i8f_fb_scratch_ = 0;   // a batch's fallback count when the caller asked for none (an F32 slab's filter accounting reads it)
     uint32_t cert_skip_ = 0, cert_backoff_ = 0;   // the lone query's single-pass certificate: calls still to skip / the current back-off
     uint32_t tp_skip_ = 0, tp_backoff_ = 0;       // ... and the two-pass searches' lone-caller lane
-    // search_top_k_batched_device_begin / _end: the ticket being begun (-1: none), per ticket 0 free / 1 plan parked / 2 finished inside begin
-    int async_want_ = -1;
-    uint8_t async_state_[2] = {0, 0};
-    bool async_i8f_[2] = {false, false};
-    uint32_t async_nq_[2] = {0, 0}, async_fb_[2] = {0, 0};
-    hipEvent_t async_ev_[2] = {nullptr, nullptr};
-    hipStream_t async_stream_[2] = {nullptr, nullptr};   // the stream each outstanding ticket was enqueued on
-    std::vector<unsigned char> async_plan_[2];   // the parked BatchedPlan (plain data: pointers and sizes), defined in the .cpp
+    // search_top_k_batched_device_begin / _end, two_pass_candidates_device_begin / _end: the two tickets
+    std::unique_ptr<BatchedTicket[]> tickets_;
+    int claim_ticket(uint32_t nq);      // a free ticket, marked finished-in-begin until its search parks; -1: both are out
+    bool any_search_parked() const;     // a begun search's kernels may still be reading the slab, the live bitmap and the workspaces
+    uint32_t tickets_taken() const;     // parked or finished in begin, not yet ended
     uint32_t i8f_sample_boost_ = 1;   // 1 or 2: the second sample of the int8 filter's wide rounds grows before the filter is given up
     bool mf_norm_ready_ = false;
     int mf_shape_i8_ = 4, mf_per_cu_160_ = 1, mf_per_cu_160_i8_ = 1;

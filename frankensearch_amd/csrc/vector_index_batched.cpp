@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <type_traits>
 
 #include "../../include/fsgpu.h"
 #include "lab_env.hpp"
@@ -26,6 +25,21 @@ SearchError VectorIndex::search_top_k_batched_device(const float* queries_dev, u
                                                      uint32_t k, const uint64_t* allow_dev, uint32_t* out_rows_dev,
                                                      float* out_scores_dev, uint32_t* out_counts_dev,
                                                      hipStream_t stream, uint32_t* fallbacks, uint64_t* out_packed_dev) {
+    BatchedRequest rq(queries_dev, nq, query_len, k, stream);
+    rq.allow_dev = allow_dev;
+    rq.out_rows_dev = out_rows_dev;
+    rq.out_scores_dev = out_scores_dev;
+    rq.out_counts_dev = out_counts_dev;
+    rq.out_packed_dev = out_packed_dev;
+    BatchedOutcome o;
+    const SearchError e = batched_exact(rq, &o);
+    if (fallbacks) *fallbacks = o.fallbacks;
+    return e;
+}
+
+// The exact search's request (blocking, or with a ticket to park in): chooses its filter and keeps the int8 filter's accounts.
+SearchError VectorIndex::batched_exact(BatchedRequest& rq, BatchedOutcome* out) {
+    const uint32_t nq = rq.nq, k = rq.k;
     // Which approximate scores filter the slab: the int8 slab on the integer matrix cores (half the bytes, half the MFMA
     // instructions of the f16 filter; a wider proven margin) unless this index has shown that its margin lets too many rows
     // through (outlier dimensions stretch the corpus-wide int8 scale), the caller forced one, or the shape is not covered.
@@ -40,22 +54,14 @@ SearchError VectorIndex::search_top_k_batched_device(const float* queries_dev, u
     if (i8f && !filter_ready()) {
         // the int8 copy of the slab (half an F16 slab's size again, a quarter of an F32 slab's; rotated when the slab has outlier
         // channels) is built on first use; no room for it: the f16 filter (an F32 slab: the exact kernels) needs none
-        FSGPU_TRY(ensure_filter_copy(stream));
+        FSGPU_TRY(ensure_filter_copy(rq.stream));
         if (!filter_ready()) i8f = false;
     }
-    if (i8f) {
-        uint32_t refiltered = 0;
-        SearchError e = batched_impl(queries_dev, nq, query_len, k, allow_dev, out_rows_dev, out_scores_dev, out_counts_dev, stream,
-                                     fallbacks ? fallbacks : &i8f_fb_scratch_, out_packed_dev, 0, 0, true, &refiltered);
-        if (e.ok() && async_want_ >= 0 && async_state_[async_want_] == 1) {
-            async_i8f_[async_want_] = true;   // (the bookkeeping below happens in _end, once the verdicts are in)
-            return e;
-        }
-        if (e.ok()) i8f_account(nq, f32_ ? (fallbacks ? *fallbacks : i8f_fb_scratch_) : refiltered);
-        return e;
-    }
-    return batched_impl(queries_dev, nq, query_len, k, allow_dev, out_rows_dev, out_scores_dev, out_counts_dev, stream,
-                        fallbacks, out_packed_dev, 0, 0, false, nullptr);
+    rq.i8_filter = i8f;
+    FSGPU_TRY(batched_impl(rq, out));
+    if (i8f && out->parked) tickets_[rq.ticket].i8f = true;   // (the bookkeeping happens in _end, once the verdicts are in)
+    else if (i8f) i8f_account(nq, f32_ ? out->fallbacks : out->refiltered);
+    return ok();
 }
 
 // The int8 copy of the slab and its statistics (what the certified lone-query pass and the int8 filter read), built NOW instead of by
@@ -343,24 +349,19 @@ SearchError VectorIndex::search_top_k_int8_batched_device(const float* queries_d
                                                           uint32_t k, uint32_t multiplier, uint32_t* out_rows_dev,
                                                           float* out_scores_dev, uint32_t* out_counts_dev,
                                                           hipStream_t stream, uint32_t* fallbacks, int bits) {
-    return batched_impl(queries_dev, nq, query_len, k, nullptr, out_rows_dev, out_scores_dev, out_counts_dev, stream,
-                        fallbacks, nullptr, multiplier ? multiplier : 1, 0, false, nullptr, bits == 4 ? 4 : 8);
+    BatchedRequest rq(queries_dev, nq, query_len, k, stream);
+    rq.out_rows_dev = out_rows_dev;
+    rq.out_scores_dev = out_scores_dev;
+    rq.out_counts_dev = out_counts_dev;
+    rq.int8_mult = multiplier ? multiplier : 1;
+    rq.bits = bits == 4 ? 4 : 8;
+    BatchedOutcome o;
+    const SearchError e = batched_impl(rq, &o);
+    if (fallbacks) *fallbacks = o.fallbacks;
+    return e;
 }
 
-SearchError VectorIndex::two_pass_candidates_device(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
-                                                    uint32_t multiplier, int bits, uint64_t* approx_out_dev, uint64_t* exact_out_dev,
-                                                    hipStream_t stream, uint32_t* fallbacks) {
-    int32_t ticket = -1;
-    FSGPU_TRY(two_pass_candidates_device_begin(queries_dev, nq, query_len, k, multiplier, bits, approx_out_dev, exact_out_dev, stream, &ticket));
-    FSGPU_TRY(two_pass_candidates_device_end(ticket, fallbacks));
-    if (nq) {
-        FSGPU_HIP(hipSetDevice(device_));
-        FSGPU_HIP(hipStreamSynchronize(stream));
-    }
-    return ok();
-}
-
-// ... in two halves, like search_top_k_batched_device_begin / _end (the same two tickets): begin enqueues pass 1, the candidate
+// A shard's half of a two-pass search in two halves, like search_top_k_batched_device_begin / _end (the same two tickets): begin enqueues pass 1, the candidate
 // selection and the exact re-score; end waits for that search's event and answers what the batch could not (list overflow: a pile of
 // tied integer scores at the threshold) per query.  ticket -1: nothing was enqueued that end would have to wait for.
 SearchError VectorIndex::two_pass_candidates_device_begin(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
@@ -377,38 +378,29 @@ SearchError VectorIndex::two_pass_candidates_device_begin(const float* queries_d
     FSGPU_HIP(hipMemsetAsync(exact_out_dev, 0xff, (size_t)nq * cc * 8, stream));
     if (f32_) return make_error(FSGPU_ERR_INVALID_CONFIG, "two-pass searches need an F16 slab");
     if (nrows_ == 0) return ok();
-    int t = -1;
-    for (int i = 0; i < 2; ++i)
-        if (async_state_[i] == 0) {
-            t = i;
-            break;
-        }
+    const int t = claim_ticket(nq);
     if (t < 0) return make_error(FSGPU_ERR_INVALID_CONFIG, "two begun batched searches are outstanding: end one first");
     // the shard-local top-k the pass also produces (not used by the root): one area per ticket
     DeviceBuffer& io = t == 0 ? mf_io_ : mf_io2_;
-    FSGPU_TRY(io.reserve((size_t)nq * (k * 8 + 4)));
-    uint32_t* rows = static_cast<uint32_t*>(io.ptr);
-    float* scores = reinterpret_cast<float*>(rows + (size_t)nq * k);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(scores + (size_t)nq * k);
-    async_state_[t] = 2;
-    async_i8f_[t] = false;
-    async_nq_[t] = nq;
-    async_fb_[t] = 0;
-    async_want_ = t;
-    tp_approx_out_ = reinterpret_cast<u64*>(approx_out_dev);
-    tp_exact_out_ = reinterpret_cast<u64*>(exact_out_dev);
-    tp_stride_ = (uint32_t)cc;
-    const SearchError e = batched_impl(queries_dev, nq, query_len, k, nullptr, rows, scores, counts, stream, &async_fb_[t], nullptr,
-                                       (uint32_t)mult, 0, false, nullptr, bits == 4 ? 4 : 8);
-    tp_approx_out_ = tp_exact_out_ = nullptr;
-    tp_stride_ = 0;
-    async_want_ = -1;
-    if (!e.ok()) {
-        async_state_[t] = 0;
-        return e;
+    SearchError e = io.reserve((size_t)nq * (k * 8 + 4));
+    BatchedOutcome o;
+    if (e.ok()) {
+        BatchedRequest rq(queries_dev, nq, query_len, k, stream);
+        rq.out_rows_dev = static_cast<uint32_t*>(io.ptr);
+        rq.out_scores_dev = reinterpret_cast<float*>(rq.out_rows_dev + (size_t)nq * k);
+        rq.out_counts_dev = reinterpret_cast<uint32_t*>(rq.out_scores_dev + (size_t)nq * k);
+        rq.int8_mult = (uint32_t)mult;
+        rq.bits = bits == 4 ? 4 : 8;
+        rq.tp_approx = reinterpret_cast<u64*>(approx_out_dev);
+        rq.tp_exact = reinterpret_cast<u64*>(exact_out_dev);
+        rq.tp_stride = (uint32_t)cc;
+        rq.ticket = t;
+        e = batched_impl(rq, &o);
     }
-    *ticket = t;
-    return ok();
+    tickets_[t].fallbacks = o.fallbacks;
+    if (e.ok()) *ticket = t;
+    else tickets_[t].state = BatchedTicket::kFree;
+    return e;
 }
 
 SearchError VectorIndex::two_pass_candidates_device_end(int32_t ticket, uint32_t* fallbacks, uint32_t* late_answers) {
@@ -419,120 +411,43 @@ SearchError VectorIndex::two_pass_candidates_device_end(int32_t ticket, uint32_t
 }
 
 // ---- the batched (matrix-core) search: prepare -> per round { sample -> main -> finish } -> fallback -------------------------
-//
-// int8_mult == 0: f16 slab, f16-rounded queries, approximate scores + proven margin (mfma_scan.hip header).
-// int8_mult >= 1: int8 slab, int8 queries, exact integer scores; the k * int8_mult best rows are the candidates.
-// i8_filter (int8_mult == 0): int8 slab and queries as the FILTER of the exact search — integer scores + the proven margin of
-//                 prepare_queries_i8_filter_kernel; queries it cannot certify are re-filtered on the f16 path (*refiltered) — on an
-//                 F32 slab, whose candidates are re-scored from f32 rows and which has no f16 path, answered by the exact f32 kernels.
 
-// What one call fixes for all its rounds: the arguments, the sample sizes, the workspaces.
-struct VectorIndex::BatchedPlan {
-    static constexpr uint32_t GMAX = 160;    // queries per pass: 128 (160 opt-in), or 64 for small batches / tails
-    static constexpr uint32_t CAPQ = 8192;   // entries one selection pass covers: block lists + pool fit it at the wide shape
-    static constexpr uint32_t SPILL = 4096;  // per-query overflow area for candidates that did not fit their block's list
-    static constexpr uint32_t KC = kSelectPool;  // approximate candidates re-scored exactly (at most)
-    static constexpr uint32_t RA_MAX = 8192;
-    // arguments
-    const float* queries_dev = nullptr;
-    uint32_t nq = 0, query_len = 0, k = 0;
-    const uint64_t* allow_dev = nullptr;
-    uint32_t* out_rows_dev = nullptr;
-    float* out_scores_dev = nullptr;
-    uint32_t* out_counts_dev = nullptr;
-    hipStream_t stream = nullptr;
-    uint32_t* fallbacks = nullptr;
-    uint64_t* out_packed_dev = nullptr;
-    uint32_t int8_mult = 0, query_stride = 0;
-    uint32_t* refiltered = nullptr;
-    int bits = 8;
-    // derived
-    bool i8f = false, i8 = false, strided = false, skip_b = false, wide_ok = false;
-    uint32_t qs = 0;                  // floats between queries
-    uint32_t RA = 4096;               // stage A sample rows (dense; <= 8192)
-    uint32_t RB = 131072;             // stage B sample rows (upper bound; shrinks with the slab)
-    uint32_t ksel_est = 0, ksel = 0;  // the rank the selections anchor on (estimate incl. the int8 filter's growth; exact)
-    uint32_t N = 0, QCAP = 0, wide_max = 0, k_eff = 0;
-    int wide_pref = 3;
-    // per-query verdicts, written by the kernels straight into pinned host memory and read after ONE stream synchronisation
-    uint32_t *overflow_all = nullptr, *counts_all = nullptr;
-    float *delta = nullptr, *tau = nullptr, *unit = nullptr, *tau_floor = nullptr;
-    uint32_t* pool_flag = nullptr;
-    u64 *spill = nullptr, *pool = nullptr;
-    uint32_t* spill_count = nullptr;
-    bool big_pool_last = false;       // the last round's finish had the second-chance launch (debug print only)
-    // two_pass_candidates_device: where this batch leaves its candidate pairs (a parked plan's fallback needs them in _end too)
-    u64 *tp_approx = nullptr, *tp_exact = nullptr;
-    uint32_t tp_stride = 0;
-};
+int VectorIndex::claim_ticket(uint32_t nq) {
+    for (int t = 0; t < 2; ++t)
+        if (tickets_[t].state == BatchedTicket::kFree) {
+            // (complete unless batched_impl parks its plan: shapes answered by the per-query kernels finish inside begin)
+            tickets_[t].state = BatchedTicket::kFinishedInBegin;
+            tickets_[t].i8f = false;
+            tickets_[t].nq = nq;
+            tickets_[t].fallbacks = 0;
+            return t;
+        }
+    return -1;
+}
 
-// One round: up to QCAP queries — the sample stages and every selection are single launches over all its query groups, only the
-// main pass is one launch per group.
-struct VectorIndex::BatchedRound {
-    uint32_t g0 = 0;                  // first query of the round
-    int wide_qt = 0, shape = 0, wpb = 0, full_grid = 0, wide_grid = 0;
-    uint32_t G = 0, wide_mult = 1, ngroups = 0, QP = 0, ng = 0, tile_rows = 0;
-    const float* qg = nullptr;
-    uint32_t *overflow = nullptr, *cand_counts = nullptr, *cand_count = nullptr;
-    u64* cand = nullptr;
-    MfmaScanArgs a{};
-    SelectArgs sb{};
-    bool anchor = false, short_stages = false;
-    int grid_for(uint32_t rows, uint32_t tile) const {
-        int g = (int)(((rows + tile - 1) / tile + wpb - 1) / wpb);
-        if (g > full_grid) g = full_grid;
-        return g < 1 ? 1 : g;
-    }
-    // one candidate list of `slots` entries per (query, block); 16..32 slots, sized so that lists + pool fit one selection pass
-    // when the grid allows (the wide shape's 256 blocks do)
-    uint32_t slots_for(int grid) const {
-        return std::min<uint32_t>((uint32_t)scan_mfma_max_slots(shape),
-                                  std::max<uint32_t>(16, (BatchedPlan::CAPQ - BatchedPlan::KC) / (uint32_t)grid));
-    }
-};
+bool VectorIndex::any_search_parked() const { return tickets_[0].state == BatchedTicket::kParked || tickets_[1].state == BatchedTicket::kParked; }
+uint32_t VectorIndex::tickets_taken() const { return (tickets_[0].state != BatchedTicket::kFree) + (tickets_[1].state != BatchedTicket::kFree); }
 
-SearchError VectorIndex::batched_impl(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
-                                      const uint64_t* allow_dev, uint32_t* out_rows_dev, float* out_scores_dev,
-                                      uint32_t* out_counts_dev, hipStream_t stream, uint32_t* fallbacks,
-                                      uint64_t* out_packed_dev, uint32_t int8_mult, uint32_t query_stride, bool i8_filter,
-                                      uint32_t* refiltered, int bits) {
+SearchError VectorIndex::batched_impl(const BatchedRequest& rq, BatchedOutcome* out) {
     BatchedPlan p;
-    p.queries_dev = queries_dev;
-    p.nq = nq;
-    p.query_len = query_len;
-    p.k = k;
-    p.allow_dev = allow_dev;
-    p.out_rows_dev = out_rows_dev;
-    p.out_scores_dev = out_scores_dev;
-    p.out_counts_dev = out_counts_dev;
-    p.stream = stream;
-    p.fallbacks = fallbacks;
-    p.out_packed_dev = out_packed_dev;
-    p.int8_mult = int8_mult;
-    p.query_stride = query_stride;   // floats between queries (0 = dim): an MRL prefix view searches the first dim_ dimensions of full-length queries
-    p.refiltered = refiltered;
-    p.bits = bits;
-    p.i8f = i8_filter && int8_mult == 0;
-    p.i8 = int8_mult != 0 || p.i8f;
-    p.tp_approx = tp_approx_out_;
-    p.tp_exact = tp_exact_out_;
-    p.tp_stride = tp_stride_;
-    if (refiltered) *refiltered = 0;
-    if (fallbacks) *fallbacks = 0;
-    FSGPU_TRY(ensure_query_dimension(query_len));
-    if (nq == 0) return ok();
+    p.rq = rq;
+    p.i8f = rq.i8_filter && rq.int8_mult == 0;
+    p.i8 = rq.int8_mult != 0 || p.i8f;
+    *out = BatchedOutcome{};
+    FSGPU_TRY(ensure_query_dimension(rq.query_len));
+    if (rq.nq == 0) return ok();
     // Every batched search of this index — begun or blocking — works in ONE set of device workspaces (thresholds, candidate lists,
     // spill areas, prepared queries): a search on another stream than an outstanding ticket's is ordered behind that ticket's last
     // kernel (searches on the same stream queue behind it by themselves).
     for (int t = 0; t < 2; ++t)
-        if (async_state_[t] == 1 && async_stream_[t] != stream && async_ev_[t]) {
+        if (tickets_[t].state == BatchedTicket::kParked && tickets_[t].stream != rq.stream && tickets_[t].event) {
             FSGPU_HIP(hipSetDevice(device_));
-            FSGPU_HIP(hipStreamWaitEvent(stream, async_ev_[t], 0));
+            FSGPU_HIP(hipStreamWaitEvent(rq.stream, tickets_[t].event, 0));
         }
-    bool done = false;
-    FSGPU_TRY(batched_prepare(p, &done));
-    if (done) return ok();
-    for (uint32_t g0 = 0; g0 < nq;) {
+    bool usable = false;
+    FSGPU_TRY(batched_prepare(p, &usable));
+    if (!usable) return batched_unusable(p, out);
+    for (uint32_t g0 = 0; g0 < rq.nq;) {
         BatchedRound r;
         FSGPU_TRY(batched_round_setup(p, r, g0));
         FSGPU_TRY(batched_sample(p, r));
@@ -541,37 +456,37 @@ SearchError VectorIndex::batched_impl(const float* queries_dev, uint32_t nq, uin
         g0 += r.ng;
     }
     // everything of this search is enqueued: the caller's window for host work that should run under it (one shot, outer call only)
-    if (after_enqueue_fn && !hard_batch_) {
+    if (after_enqueue_fn && !rq.nested) {
         void (*fn)(void*) = after_enqueue_fn;
         after_enqueue_fn = nullptr;
         fn(after_enqueue_ctx);
     }
-    if (async_want_ >= 0 && !hard_batch_) {
+    if (rq.ticket >= 0 && !rq.nested) {
         // fsgpu_search_topk_batched_device_begin: everything is enqueued — the verdicts are read (and the rare uncertified query
         // answered) by _end, behind an event instead of a stream synchronisation, so that the caller can enqueue its next search first
-        const int t = async_want_;
-        static_assert(std::is_trivially_copyable<BatchedPlan>::value, "the parked plan is copied as bytes");
-        async_plan_[t].resize(sizeof(BatchedPlan));
-        std::memcpy(async_plan_[t].data(), &p, sizeof(BatchedPlan));
+        BatchedTicket& tk = tickets_[rq.ticket];
+        tk.plan = p;
         // (a DEVICE-scope release: the default event makes the GPU write back and invalidate its caches where it is recorded — ~30 us
         // between this search's last kernel and the next search's first, the very gap the two halves exist to close.  What the host
         // reads behind the event are the verdicts, which the kernels write to coherent pinned memory; the outputs in device memory
         // are read by work that is ordered behind them on the GPU, or through copies that bring their own release.)
-        if (!async_ev_[t]) FSGPU_HIP(hipEventCreateWithFlags(&async_ev_[t], hipEventDisableTiming | hipEventReleaseToDevice));
-        FSGPU_HIP(hipEventRecord(async_ev_[t], p.stream));
-        async_stream_[t] = p.stream;
-        async_state_[t] = 1;
+        if (!tk.event) FSGPU_HIP(hipEventCreateWithFlags(&tk.event, hipEventDisableTiming | hipEventReleaseToDevice));
+        FSGPU_HIP(hipEventRecord(tk.event, rq.stream));
+        tk.stream = rq.stream;
+        tk.state = BatchedTicket::kParked;
+        out->parked = true;
         return ok();
     }
-    return batched_fallback(p);
+    return batched_fallback(p, out);
 }
 
-// Stage "prepare": the sample sizes, the shapes the matrix-core path does not cover (answered here, *done = true), the lazily
+// Stage "prepare": the sample sizes, the shapes the matrix-core path does not cover (*usable = false: batched_unusable answers), the lazily
 // built quantised copies and statistics, the workspaces.
-SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
-    *done = false;
-    const uint32_t nq = p.nq, k = p.k;
-    p.qs = p.query_stride ? p.query_stride : dim_;
+SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* usable) {
+    *usable = false;
+    const BatchedRequest& rq = p.rq;
+    const uint32_t nq = rq.nq, k = rq.k;
+    p.qs = rq.query_stride ? rq.query_stride : dim_;
     uint32_t RA = 4096, RB = 131072;
     if (knobs().ra > 0) RA = (uint32_t)knobs().ra;  // tuning experiments only
     if (knobs().rb > 0) RB = (uint32_t)knobs().rb;
@@ -586,7 +501,7 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     // B lets 4 x as many through — 1.25M-row shard, 1,024 queries: main pass 0.366 -> 0.329 ms, 2.5M: 0.741 -> 0.642 ms.)
     const bool wide_main = knobs().wide != 0 && nq >= wide_min_queries(p.i8 && !p.i8f) && scan_wide_supported((int)dim_, p.i8 ? 1 : 2) && variant != 5 && variant != 6;
     if (knobs().ra <= 0 && !knobs().no_skip_b && !wide_main && nrows_ <= 4'000'000 && nrows_ >= 4 * (uint64_t)RA_MAX) {
-        const uint64_t expect = (uint64_t)std::max<uint32_t>(k, 1) * (p.i8 ? std::max<uint32_t>(p.int8_mult, 1) : 1) * (nrows_ / RA_MAX);
+        const uint64_t expect = (uint64_t)std::max<uint32_t>(k, 1) * (p.i8 ? std::max<uint32_t>(p.rq.int8_mult, 1) : 1) * (nrows_ / RA_MAX);
         if (expect <= 4096) {
             RA = RA_MAX;
             skip_b = true;
@@ -596,7 +511,7 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     // lists, spill area, the selection's capacity), so the samples grow with the rank the selections anchor on.
     // (the int8 filter's margin lets a few times as many rows through each stage as its rank alone would: sized like a larger rank)
     const uint32_t i8f_growth = knobs().i8f_growth > 0 ? (uint32_t)knobs().i8f_growth : 4;
-    const uint32_t ksel_est = std::max<uint32_t>(k, 1) * (p.int8_mult ? p.int8_mult : 1) * (p.i8f ? i8f_growth : 1);
+    const uint32_t ksel_est = std::max<uint32_t>(k, 1) * (p.rq.int8_mult ? p.rq.int8_mult : 1) * (p.i8f ? i8f_growth : 1);
     const uint32_t grow = knobs().rb > 0 ? 1 : std::min<uint32_t>(4, (ksel_est + 15) / 16);
     if (knobs().ra <= 0 && ksel_est > 32) RA = RA_MAX;
     // B = about 1/64 of the slab (times the growth), between 8 RA and the cap, a multiple of RA, at most a quarter of it
@@ -624,21 +539,18 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     p.skip_b = skip_b;
     p.ksel_est = ksel_est;
     // int8 mode: candidate_count of the reference (search.rs:603-607)
-    uint64_t cc64 = std::min<uint64_t>((uint64_t)k * (p.int8_mult ? p.int8_mult : 1), nrows_);
+    uint64_t cc64 = std::min<uint64_t>((uint64_t)k * (p.rq.int8_mult ? p.rq.int8_mult : 1), nrows_);
     cc64 = std::max<uint64_t>(cc64, std::min<uint64_t>(k, nrows_));
-    p.ksel = p.int8_mult ? (uint32_t)std::min<uint64_t>(cc64, 0xffffffffull) : k;  // rank that anchors the selections
+    p.ksel = p.rq.int8_mult ? (uint32_t)std::min<uint64_t>(cc64, 0xffffffffull) : k;  // rank that anchors the selections
     p.strided = !dense_rows();   // an MRL prefix view
-    const bool usable = scan_mfma_supported((int)dim_) && k >= 1 && k <= 64 && p.ksel <= kSelectMaxK && nrows_ >= 4 * (uint64_t)RA && variant != 4 &&
-                        (!f32_ || (p.i8f && !p.strided)) && (!p.strided || (!p.i8 && p.qs >= dim_)) && (p.query_stride == 0 || !p.i8);
+    const bool covered = scan_mfma_supported((int)dim_) && k >= 1 && k <= 64 && p.ksel <= kSelectMaxK && nrows_ >= 4 * (uint64_t)RA && variant != 4 &&
+                        (!f32_ || (p.i8f && !p.strided)) && (!p.strided || (!p.i8 && p.qs >= dim_)) && (p.rq.query_stride == 0 || !p.i8);
     // (an F32 slab: the int8 filter only — there is no f16-row filter for it, and the int8 two-pass stays F16-only)
-    if (!usable) {
-        *done = true;
-        return batched_unusable(p);
-    }
+    if (!covered) return ok();
     FSGPU_HIP(hipSetDevice(device_));
     p.N = (uint32_t)nrows_;
-    hipStream_t stream = p.stream;
-    if (p.i8 && p.bits == 4 && !n4u_ready_) {  // the 4-bit levels of VectorIndex::nibbles_slab(), one per byte: built lazily, once
+    hipStream_t stream = p.rq.stream;
+    if (p.i8 && p.rq.bits == 4 && !n4u_ready_) {  // the 4-bit levels of VectorIndex::nibbles_slab(), one per byte: built lazily, once
         FSGPU_TRY(n4u_slab_.reserve((size_t)nrows_ * dim_));
         FSGPU_TRY(i8_max_.reserve(4));
         FSGPU_HIP(launch_quantize_slab_4bit_levels(slab_dev_, (size_t)nrows_ * dim_, static_cast<unsigned int*>(i8_max_.ptr),
@@ -647,7 +559,7 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     }
     if (p.i8f) {   // the filter's copy (rotated for slabs with outlier channels) + its statistics: built lazily, once
         FSGPU_TRY(ensure_filter_copy(stream, true));
-    } else if (p.i8 && p.bits != 4 && !i8_ready_) {  // VectorIndex::int8_slab(): built lazily, once
+    } else if (p.i8 && p.rq.bits != 4 && !i8_ready_) {  // VectorIndex::int8_slab(): built lazily, once
         FSGPU_TRY(i8_slab_.reserve((size_t)nrows_ * dim_));
         FSGPU_TRY(i8_max_.reserve(4));
         FSGPU_HIP(launch_quantize_slab_i8(slab_dev_, (size_t)nrows_ * dim_, static_cast<unsigned int*>(i8_max_.ptr),
@@ -709,7 +621,7 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     const uint32_t flag_cap = (nq + GMAX - 1) / GMAX * GMAX + 256;   // (a round's query slots may run up to 255 past its real queries)
     if (flag_cap > mf_flags_cap_) {
         // (three areas: blocking calls, and one per begun search — a begun search's verdicts must survive the next call's reset)
-        if (async_state_[0] == 1 || async_state_[1] == 1)
+        if (any_search_parked())
             return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding: end it before searching with a larger batch");
         if (mf_flags_host_) (void)hipHostFree(mf_flags_host_);
         mf_flags_host_ = nullptr;
@@ -717,7 +629,7 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
         FSGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&mf_flags_host_), (size_t)flag_cap * 8 * 3, hipHostMallocMapped));
         mf_flags_cap_ = flag_cap;
     }
-    uint32_t* flags_area = mf_flags_host_ + (size_t)((async_want_ >= 0 && !hard_batch_) ? 1 + async_want_ : 0) * mf_flags_cap_ * 2;
+    uint32_t* flags_area = mf_flags_host_ + (size_t)((rq.ticket >= 0 && !rq.nested) ? 1 + rq.ticket : 0) * mf_flags_cap_ * 2;
     p.overflow_all = flags_area;
     p.counts_all = flags_area + mf_flags_cap_;
     std::memset(flags_area, 0, (size_t)mf_flags_cap_ * 8);
@@ -730,49 +642,55 @@ SearchError VectorIndex::batched_prepare(BatchedPlan& p, bool* done) {
     p.spill_count = reinterpret_cast<uint32_t*>(p.spill + (size_t)QCAP * SPILL);
     p.pool = static_cast<u64*>(mf_sel_.ptr);
     p.k_eff = std::min<uint32_t>(k, p.N);
+    // the int8 filter's margin (and whatever it hands on to the f16 filter) can put thousands of rows within reach of the k-th
+    // score: the finish re-scores up to 8,192 of them per query instead of 1,024
+    p.big_pool = (p.i8f || rq.nested) && !knobs().no_big_pool;
+    *usable = true;
     return ok();
 }
 
 // Shapes the matrix-core path does not cover: answered by the per-query kernels (or handed to the f16 branch).
-SearchError VectorIndex::batched_unusable(BatchedPlan& p) {
-    const uint32_t nq = p.nq, k = p.k;
-    hipStream_t stream = p.stream;
-    if (p.i8f)   // the f16 branch sorts them out
-        return batched_impl(p.queries_dev, nq, p.query_len, k, p.allow_dev, p.out_rows_dev, p.out_scores_dev, p.out_counts_dev, stream,
-                            p.fallbacks, p.out_packed_dev, 0, p.query_stride, false, nullptr);
+SearchError VectorIndex::batched_unusable(const BatchedPlan& p, BatchedOutcome* out) {
+    const uint32_t nq = p.rq.nq, k = p.rq.k;
+    hipStream_t stream = p.rq.stream;
+    if (p.i8f) {   // the f16 branch sorts them out (the same request, ticket included: it may park)
+        BatchedRequest f16 = p.rq;
+        f16.i8_filter = false;
+        return batched_impl(f16, out);
+    }
     if (p.i8) {
         // per-query int8 two-pass through host staging (rare shapes: huge candidate counts, tiny or odd-dimension slabs)
         std::vector<float> q((size_t)nq * dim_), sc((size_t)nq * k);
         std::vector<uint32_t> rw((size_t)nq * k, 0xffffffffu), cnt(nq);
-        FSGPU_HIP(hipMemcpyAsync(q.data(), p.queries_dev, q.size() * 4, hipMemcpyDeviceToHost, stream));
+        FSGPU_HIP(hipMemcpyAsync(q.data(), p.rq.queries_dev, q.size() * 4, hipMemcpyDeviceToHost, stream));
         FSGPU_HIP(hipStreamSynchronize(stream));
         for (uint32_t i = 0; i < nq; ++i)
-            FSGPU_TRY(quantized_two_pass(q.data() + (size_t)i * dim_, dim_, k, p.int8_mult, p.bits, rw.data() + (size_t)i * k,
-                                         sc.data() + (size_t)i * k, &cnt[i], p.tp_approx ? p.tp_approx + (size_t)i * p.tp_stride : nullptr,
-                                         p.tp_exact ? p.tp_exact + (size_t)i * p.tp_stride : nullptr));
-        if (p.out_rows_dev) FSGPU_HIP(hipMemcpyAsync(p.out_rows_dev, rw.data(), rw.size() * 4, hipMemcpyHostToDevice, stream));
-        if (p.out_scores_dev) FSGPU_HIP(hipMemcpyAsync(p.out_scores_dev, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, stream));
-        if (p.out_counts_dev) FSGPU_HIP(hipMemcpyAsync(p.out_counts_dev, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, stream));
+            FSGPU_TRY(quantized_two_pass(q.data() + (size_t)i * dim_, dim_, k, p.rq.int8_mult, p.rq.bits, rw.data() + (size_t)i * k,
+                                         sc.data() + (size_t)i * k, &cnt[i], p.rq.tp_approx ? p.rq.tp_approx + (size_t)i * p.rq.tp_stride : nullptr,
+                                         p.rq.tp_exact ? p.rq.tp_exact + (size_t)i * p.rq.tp_stride : nullptr));
+        if (p.rq.out_rows_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_rows_dev, rw.data(), rw.size() * 4, hipMemcpyHostToDevice, stream));
+        if (p.rq.out_scores_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_scores_dev, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, stream));
+        if (p.rq.out_counts_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_counts_dev, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, stream));
         FSGPU_HIP(hipStreamSynchronize(stream));
-        if (p.fallbacks) *p.fallbacks = nq;
+        out->fallbacks = nq;
         return ok();
     }
-    if (p.query_stride)
+    if (p.rq.query_stride)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "strided queries need the matrix-core path (caller falls back per query)");
-    if (p.fallbacks) *p.fallbacks = nq;
-    if (p.out_packed_dev) {
-        FSGPU_TRY(search_top_k_packed_device(p.queries_dev, nq, p.query_len, k, p.allow_dev, p.out_packed_dev, stream));
-        if (!p.out_rows_dev) return ok();
+    out->fallbacks = nq;
+    if (p.rq.out_packed_dev) {
+        FSGPU_TRY(search_top_k_packed_device(p.rq.queries_dev, nq, p.rq.query_len, k, p.rq.allow_dev, p.rq.out_packed_dev, stream));
+        if (!p.rq.out_rows_dev) return ok();
     }
-    return search_top_k_device(p.queries_dev, nq, p.query_len, k, p.allow_dev, p.out_rows_dev, p.out_scores_dev, p.out_counts_dev, stream);
+    return search_top_k_device(p.rq.queries_dev, nq, p.rq.query_len, k, p.rq.allow_dev, p.rq.out_rows_dev, p.rq.out_scores_dev, p.rq.out_counts_dev, stream);
 }
 
 // The geometry of the round that starts at query g0, the prepared (rounded / quantised) queries, the scan arguments every stage shares.
 SearchError VectorIndex::batched_round_setup(const BatchedPlan& p, BatchedRound& r, uint32_t g0) {
     const bool i8 = p.i8;
-    hipStream_t stream = p.stream;
+    hipStream_t stream = p.rq.stream;
     r.g0 = g0;
-    const uint32_t left = p.nq - g0;
+    const uint32_t left = p.rq.nq - g0;
     // Main pass at 384 / 256 queries per launch (mfma_wide.hip: queries in registers, row tiles through an LDS-DMA
     // ring) when that many are left; the sample stages then run as sub-groups of 128 on the LDS-query kernel.
     r.wide_qt = 0;
@@ -811,12 +729,12 @@ SearchError VectorIndex::batched_round_setup(const BatchedPlan& p, BatchedRound&
                                           : (r.shape ? mf_per_cu_wide_ : mf_per_cu_narrow_));
     r.full_grid = num_cus_ * per_cu;
     r.tile_rows = (uint32_t)scan_mfma_rows_per_tile(r.shape);
-    r.qg = p.queries_dev + (size_t)g0 * p.qs;
+    r.qg = p.rq.queries_dev + (size_t)g0 * p.qs;
     r.overflow = p.overflow_all + g0;
     r.cand_counts = p.counts_all + g0;
     if (p.i8f)
         FSGPU_TRY(prepare_filter_queries(r.qg, r.ng, r.QP, p.qs, mf_qh_.ptr, p.delta, p.unit, stream));
-    else if (i8) FSGPU_HIP(launch_prepare_queries_i8(r.qg, r.ng, r.QP, dim_, mf_qh_.ptr, p.delta, stream, p.bits));
+    else if (i8) FSGPU_HIP(launch_prepare_queries_i8(r.qg, r.ng, r.QP, dim_, mf_qh_.ptr, p.delta, stream, p.rq.bits));
     else
         FSGPU_HIP(launch_prepare_queries(r.qg, r.ng, r.QP, dim_, p.qs, static_cast<const unsigned int*>(mf_max_norm_.ptr),
                                          mf_qh_.ptr, p.delta, stream));
@@ -827,10 +745,10 @@ SearchError VectorIndex::batched_round_setup(const BatchedPlan& p, BatchedRound&
     r.cand_count = static_cast<uint32_t*>(mf_cand_count_.ptr);
     MfmaScanArgs& a = r.a;
     a = MfmaScanArgs{};
-    a.slab = p.i8f ? filter_slab() : i8 ? (p.bits == 4 ? n4u_slab_.ptr : i8_slab_.ptr) : slab_dev_;
+    a.slab = p.i8f ? filter_slab() : i8 ? (p.rq.bits == 4 ? n4u_slab_.ptr : i8_slab_.ptr) : slab_dev_;
     a.elem_bytes = i8 ? 1 : 2;
     a.live = reinterpret_cast<const u64*>(live_dev_);
-    a.allow = reinterpret_cast<const u64*>(p.allow_dev);
+    a.allow = reinterpret_cast<const u64*>(p.rq.allow_dev);
     a.queries = mf_qh_.ptr;
     a.tau = p.tau;
     a.cand = r.cand;
@@ -857,7 +775,7 @@ SearchError VectorIndex::batched_round_setup(const BatchedPlan& p, BatchedRound&
 // the slab: B = every stride_b-th group, A = a subset of B.
 SearchError VectorIndex::batched_sample(const BatchedPlan& p, BatchedRound& r) {
     constexpr uint32_t SPILL = BatchedPlan::SPILL;
-    hipStream_t stream = p.stream;
+    hipStream_t stream = p.rq.stream;
     const bool i8 = p.i8, i8f = p.i8f, skip_b = p.skip_b;
     const uint32_t N = p.N, RA = p.RA, RB = p.RB, QP = r.QP, ksel = p.ksel;
     MfmaScanArgs& a = r.a;
@@ -1063,7 +981,7 @@ SearchError VectorIndex::batched_sample(const BatchedPlan& p, BatchedRound& r) {
 // group-maxima selection, stage A's selection, stage B's selection).  FSGPU_DEBUG_BATCHED checks it.
 SearchError VectorIndex::batched_main(const BatchedPlan& p, BatchedRound& r) {
     constexpr uint32_t SPILL = BatchedPlan::SPILL, CAPQ = BatchedPlan::CAPQ, KC = BatchedPlan::KC;
-    hipStream_t stream = p.stream;
+    hipStream_t stream = p.rq.stream;
     MfmaScanArgs& a = r.a;
     SelectArgs& sb = r.sb;
     // (an event pair idles the stream ~6 us on either side of a launch: with a period, the main launches of every n-th call are timed)
@@ -1184,16 +1102,12 @@ SearchError VectorIndex::batched_main(const BatchedPlan& p, BatchedRound& r) {
 
 // Stage "finish": every row whose approximate score is within 2 delta of the k-th best (more than KC of them: the query goes to
 // the exact path) is re-scored in the reference's order; the best k exact entries are the answer.
-SearchError VectorIndex::batched_finish(BatchedPlan& p, BatchedRound& r) {
-    hipStream_t stream = p.stream;
+SearchError VectorIndex::batched_finish(const BatchedPlan& p, BatchedRound& r) {
+    hipStream_t stream = p.rq.stream;
     SelectArgs& sb = r.sb;
-    const uint32_t k = p.k, g0 = r.g0;
+    const uint32_t k = p.rq.k, g0 = r.g0;
     sb.cand_counts = r.cand_counts;
-    // the int8 filter's margin (and whatever it hands on to the f16 filter) can put thousands of rows within reach of the k-th
-    // score: the finish re-scores up to 8,192 of them per query instead of 1,024
-    const bool second_chance = (p.i8f || hard_batch_) && !knobs().no_big_pool;
-    p.big_pool_last = second_chance;
-    sb.pool_flag = second_chance ? p.pool_flag : nullptr;
+    sb.pool_flag = p.big_pool ? p.pool_flag : nullptr;
     sb.slab = slab_dev_;
     sb.queries = r.qg;
     sb.dim = dim_;
@@ -1205,14 +1119,14 @@ SearchError VectorIndex::batched_finish(BatchedPlan& p, BatchedRound& r) {
     sb.slab_f32 = f32_ ? 1u : 0u;
     sb.k_out = p.k_eff;
     sb.out_stride = k;
-    sb.out_rows = p.out_rows_dev ? p.out_rows_dev + (size_t)g0 * k : nullptr;
-    sb.out_scores = p.out_scores_dev ? p.out_scores_dev + (size_t)g0 * k : nullptr;
-    sb.out_counts = p.out_counts_dev ? p.out_counts_dev + g0 : nullptr;
-    sb.out_packed = p.out_packed_dev ? reinterpret_cast<u64*>(p.out_packed_dev) + (size_t)g0 * k : nullptr;
-    if (p.int8_mult && p.tp_approx) {   // a sharded index's shard: the candidate pairs themselves (two_pass_candidates_device)
-        sb.cand_approx_out = p.tp_approx + (size_t)g0 * p.tp_stride;
-        sb.cand_exact_out = p.tp_exact + (size_t)g0 * p.tp_stride;
-        sb.cand_out_stride = p.tp_stride;
+    sb.out_rows = p.rq.out_rows_dev ? p.rq.out_rows_dev + (size_t)g0 * k : nullptr;
+    sb.out_scores = p.rq.out_scores_dev ? p.rq.out_scores_dev + (size_t)g0 * k : nullptr;
+    sb.out_counts = p.rq.out_counts_dev ? p.rq.out_counts_dev + g0 : nullptr;
+    sb.out_packed = p.rq.out_packed_dev ? reinterpret_cast<u64*>(p.rq.out_packed_dev) + (size_t)g0 * k : nullptr;
+    if (p.rq.int8_mult && p.rq.tp_approx) {   // a sharded index's shard: the candidate pairs themselves (two_pass_candidates_device_begin)
+        sb.cand_approx_out = p.rq.tp_approx + (size_t)g0 * p.rq.tp_stride;
+        sb.cand_exact_out = p.rq.tp_exact + (size_t)g0 * p.rq.tp_stride;
+        sb.cand_out_stride = p.rq.tp_stride;
     }
 #ifdef FSGPU_EXPERIMENTS
     static unsigned long long* sel_stamps = nullptr;   // FSGPU_SELECT_STAMPS=1: shader clocks of the phases of blocks 0, 256, 512, 768 of the finish
@@ -1231,7 +1145,7 @@ SearchError VectorIndex::batched_finish(BatchedPlan& p, BatchedRound& r) {
 #endif
     FSGPU_HIP(launch_select(sb, (int)r.ng, stream));
     sb.stamps = nullptr;
-    if (second_chance) {   // queries whose candidates did not fit the pool: the sorted finish over the same lists (others return at once)
+    if (p.big_pool) {   // queries whose candidates did not fit the pool: the sorted finish over the same lists (others return at once)
         sb.big_pool = 1;
         FSGPU_HIP(launch_select(sb, (int)r.ng, stream));
     }
@@ -1241,10 +1155,10 @@ SearchError VectorIndex::batched_finish(BatchedPlan& p, BatchedRound& r) {
 // Stage "fallback": ONE stream synchronisation for the whole batch, then the host reads the per-query verdicts — margin / capacity
 // overflow, or fewer than k candidates — and the uncertified queries are answered by the exact kernels (the int8 filter hands a
 // larger set to the f16 filter first; the int8 two-pass to its per-query form).
-SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
+SearchError VectorIndex::batched_fallback(const BatchedPlan& p, BatchedOutcome* out, bool already_waited) {
     constexpr uint32_t KC = BatchedPlan::KC;
-    hipStream_t stream = p.stream;
-    const uint32_t nq = p.nq, k = p.k, k_eff = p.k_eff;
+    hipStream_t stream = p.rq.stream;
+    const uint32_t nq = p.rq.nq, k = p.rq.k, k_eff = p.k_eff;
     // (polling the stream with hipStreamQuery before blocking was measured: no change at 10M rows or on a 1.25M-row shard,
     // profiles/r04/step_overheads.txt — the runtime's wait is already an active one for waits this short)
     if (!already_waited) FSGPU_HIP(hipStreamSynchronize(stream));
@@ -1254,7 +1168,7 @@ SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
     if (knobs().debug_batched) {
         uint32_t big = 0, slot = 0, few = 0, mx = 0;
         for (uint32_t i = 0; i < nq; ++i) {
-            if (p.counts_all[i] > (p.big_pool_last ? 8192u : KC)) ++big;
+            if (p.counts_all[i] > (p.big_pool ? 8192u : KC)) ++big;
             else if (p.overflow_all[i]) ++slot;
             if (p.counts_all[i] < k_eff) ++few;
             mx = std::max(mx, p.counts_all[i]);
@@ -1264,22 +1178,22 @@ SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
         for (size_t j = 0; j < fb.size() && j < 4; ++j)
             std::fprintf(stderr, "    query %u: overflow=%u candidates=%u\n", fb[j], p.overflow_all[fb[j]], p.counts_all[fb[j]]);
     }
-    const uint32_t total_fallbacks = (uint32_t)fb.size();
+    uint32_t total_fallbacks = (uint32_t)fb.size();
     if (total_fallbacks && p.i8 && !p.i8f) {
         // list/spill overflow (a pile of tied scores at the threshold): the per-query int8 two-pass answers those
         std::vector<float> qh(dim_), sc(k);
         std::vector<uint32_t> rw(k);
         for (uint32_t i : fb) {
             uint32_t cnt = 0;
-            FSGPU_HIP(hipMemcpyAsync(qh.data(), p.queries_dev + (size_t)i * dim_, (size_t)dim_ * 4, hipMemcpyDeviceToHost, stream));
+            FSGPU_HIP(hipMemcpyAsync(qh.data(), p.rq.queries_dev + (size_t)i * dim_, (size_t)dim_ * 4, hipMemcpyDeviceToHost, stream));
             FSGPU_HIP(hipStreamSynchronize(stream));
             std::fill(rw.begin(), rw.end(), 0xffffffffu);
-            FSGPU_TRY(quantized_two_pass(qh.data(), dim_, k, p.int8_mult, p.bits, rw.data(), sc.data(), &cnt,
-                                         p.tp_approx ? p.tp_approx + (size_t)i * p.tp_stride : nullptr,
-                                         p.tp_exact ? p.tp_exact + (size_t)i * p.tp_stride : nullptr));
-            if (p.out_rows_dev) FSGPU_HIP(hipMemcpyAsync(p.out_rows_dev + (size_t)i * k, rw.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
-            if (p.out_scores_dev) FSGPU_HIP(hipMemcpyAsync(p.out_scores_dev + (size_t)i * k, sc.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
-            if (p.out_counts_dev) FSGPU_HIP(hipMemcpyAsync(p.out_counts_dev + i, &cnt, 4, hipMemcpyHostToDevice, stream));
+            FSGPU_TRY(quantized_two_pass(qh.data(), dim_, k, p.rq.int8_mult, p.rq.bits, rw.data(), sc.data(), &cnt,
+                                         p.rq.tp_approx ? p.rq.tp_approx + (size_t)i * p.rq.tp_stride : nullptr,
+                                         p.rq.tp_exact ? p.rq.tp_exact + (size_t)i * p.rq.tp_stride : nullptr));
+            if (p.rq.out_rows_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_rows_dev + (size_t)i * k, rw.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
+            if (p.rq.out_scores_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_scores_dev + (size_t)i * k, sc.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
+            if (p.rq.out_counts_dev) FSGPU_HIP(hipMemcpyAsync(p.rq.out_counts_dev + i, &cnt, 4, hipMemcpyHostToDevice, stream));
             FSGPU_HIP(hipStreamSynchronize(stream));
         }
     } else if (total_fallbacks) {
@@ -1300,29 +1214,32 @@ SearchError VectorIndex::batched_fallback(BatchedPlan& p, bool already_waited) {
         uint32_t* counts_dev = reinterpret_cast<uint32_t*>(base + o_counts);
         FSGPU_HIP(hipMemcpyAsync(idx_dev, fb.data(), nf * 4, hipMemcpyHostToDevice, stream));
         FSGPU_HIP(hipStreamSynchronize(stream));  // fb is a stack-owned pageable buffer
-        FSGPU_HIP(launch_gather_queries(p.queries_dev, idx_dev, (uint32_t)nf, dim_, p.qs, q_dev, stream));
-        // (an F32 slab has no f16 filter: its leftovers go straight to the exact f32 kernels below, as fallbacks)
+        FSGPU_HIP(launch_gather_queries(p.rq.queries_dev, idx_dev, (uint32_t)nf, dim_, p.qs, q_dev, stream));
+        // (an F32 slab has no f16 filter: its leftovers go straight to the exact f32 kernels, as fallbacks)
+        if (p.i8f && !f32_) out->refiltered = (uint32_t)nf;
         if (p.i8f && nf > 8 && !f32_) {
             // rows within the int8 margin of the k-th best did not fit the lists (or the query cannot be certified on the int8
             // slab at all): the f16 filter, whose margin is ~20 x narrower, answers these as a batch of its own
-            uint32_t inner_fb = 0;
-            hard_batch_ = true;
-            const SearchError inner = batched_impl(q_dev, (uint32_t)nf, p.query_len, k, p.allow_dev, rows_dev, scores_dev, counts_dev, stream,
-                                                   &inner_fb, nullptr, 0, 0, false, nullptr);
-            hard_batch_ = false;
-            FSGPU_TRY(inner);
-            if (p.refiltered) *p.refiltered = (uint32_t)nf;
-            if (p.fallbacks) *p.fallbacks = inner_fb;
-            FSGPU_HIP(launch_scatter_hits(idx_dev, (uint32_t)nf, k, rows_dev, scores_dev, counts_dev, p.out_rows_dev,
-                                          p.out_scores_dev, p.out_counts_dev, reinterpret_cast<u64*>(p.out_packed_dev), stream));
-            return ok();
+            BatchedRequest leftovers = p.rq;   // (nested: blocking, the blocking calls' verdict area, no after-enqueue hook)
+            leftovers.queries_dev = q_dev;
+            leftovers.nq = (uint32_t)nf;
+            leftovers.out_rows_dev = rows_dev;
+            leftovers.out_scores_dev = scores_dev;
+            leftovers.out_counts_dev = counts_dev;
+            leftovers.out_packed_dev = nullptr;
+            leftovers.query_stride = 0;
+            leftovers.i8_filter = false;
+            leftovers.nested = true;
+            BatchedOutcome inner;
+            FSGPU_TRY(batched_impl(leftovers, &inner));
+            total_fallbacks = inner.fallbacks;
+        } else {
+            FSGPU_TRY(fused_search(q_dev, (uint32_t)nf, k, k_eff, p.rq.allow_dev, rows_dev, scores_dev, counts_dev, nullptr, stream));
         }
-        if (p.i8f && p.refiltered && !f32_) *p.refiltered = (uint32_t)nf;
-        FSGPU_TRY(fused_search(q_dev, (uint32_t)nf, k, k_eff, p.allow_dev, rows_dev, scores_dev, counts_dev, nullptr, stream));
-        FSGPU_HIP(launch_scatter_hits(idx_dev, (uint32_t)nf, k, rows_dev, scores_dev, counts_dev, p.out_rows_dev,
-                                      p.out_scores_dev, p.out_counts_dev, reinterpret_cast<u64*>(p.out_packed_dev), stream));
+        FSGPU_HIP(launch_scatter_hits(idx_dev, (uint32_t)nf, k, rows_dev, scores_dev, counts_dev, p.rq.out_rows_dev,
+                                      p.rq.out_scores_dev, p.rq.out_counts_dev, reinterpret_cast<u64*>(p.rq.out_packed_dev), stream));
     }
-    if (p.fallbacks) *p.fallbacks = total_fallbacks;
+    out->fallbacks = total_fallbacks;
     return ok();
 }
 
@@ -1333,51 +1250,43 @@ SearchError VectorIndex::search_top_k_batched_device_begin(const float* queries_
                                                            const uint64_t* allow_dev, uint32_t* out_rows_dev, float* out_scores_dev,
                                                            uint32_t* out_counts_dev, hipStream_t stream, uint64_t* out_packed_dev,
                                                            int32_t* ticket) {
-    int t = -1;
-    for (int i = 0; i < 2; ++i)
-        if (async_state_[i] == 0) {
-            t = i;
-            break;
-        }
+    const int t = claim_ticket(nq);
     if (t < 0) return make_error(FSGPU_ERR_INVALID_CONFIG, "two begun batched searches are outstanding: end one first");
-    async_state_[t] = 2;   // (complete unless batched_impl parks its plan: shapes answered by the per-query kernels finish inside)
-    async_i8f_[t] = false;
-    async_nq_[t] = nq;
-    async_fb_[t] = 0;
-    async_want_ = t;
-    const SearchError e = search_top_k_batched_device(queries_dev, nq, query_len, k, allow_dev, out_rows_dev, out_scores_dev, out_counts_dev,
-                                                      stream, &async_fb_[t], out_packed_dev);
-    async_want_ = -1;
-    if (!e.ok()) {
-        async_state_[t] = 0;
-        return e;
-    }
-    *ticket = t;
-    return ok();
+    BatchedRequest rq(queries_dev, nq, query_len, k, stream);
+    rq.allow_dev = allow_dev;
+    rq.out_rows_dev = out_rows_dev;
+    rq.out_scores_dev = out_scores_dev;
+    rq.out_counts_dev = out_counts_dev;
+    rq.out_packed_dev = out_packed_dev;
+    rq.ticket = t;
+    BatchedOutcome o;
+    const SearchError e = batched_exact(rq, &o);
+    tickets_[t].fallbacks = o.fallbacks;
+    if (e.ok()) *ticket = t;
+    else tickets_[t].state = BatchedTicket::kFree;   // (a begin whose search fails gives its ticket back)
+    return e;
 }
 
 SearchError VectorIndex::search_top_k_batched_device_end(int32_t ticket, uint32_t* fallbacks, uint32_t* late_answers) {
     if (late_answers) *late_answers = 0;
-    if (ticket < 0 || ticket > 1 || async_state_[ticket] == 0) return make_error(FSGPU_ERR_INVALID_CONFIG, "no such begun batched search");
-    const int t = ticket;
-    if (async_state_[t] == 1) {
+    if (ticket < 0 || ticket > 1 || tickets_[ticket].state == BatchedTicket::kFree) return make_error(FSGPU_ERR_INVALID_CONFIG, "no such begun batched search");
+    BatchedTicket& tk = tickets_[ticket];
+    if (tk.state == BatchedTicket::kParked) {
         FSGPU_HIP(hipSetDevice(device_));
-        FSGPU_HIP(hipEventSynchronize(async_ev_[t]));
-        BatchedPlan p;
-        std::memcpy(&p, async_plan_[t].data(), sizeof(BatchedPlan));
-        uint32_t refiltered = 0;
-        p.refiltered = async_i8f_[t] ? &refiltered : nullptr;   // (begin's were the addresses of its own locals)
-        p.fallbacks = &async_fb_[t];
-        async_state_[t] = 0;   // (before the fallback: it may search again, blocking, on this index)
-        FSGPU_TRY(batched_fallback(p, true));
-        if (async_i8f_[t]) i8f_account(async_nq_[t], f32_ ? async_fb_[t] : refiltered);
+        FSGPU_HIP(hipEventSynchronize(tk.event));
+        const BatchedPlan plan = tk.plan;   // (a copy, and the ticket freed before the fallback: it may search again on this index)
+        tk.state = BatchedTicket::kFree;
+        BatchedOutcome o;
+        FSGPU_TRY(batched_fallback(plan, &o, true));
+        tk.fallbacks = o.fallbacks;
+        if (tk.i8f) i8f_account(tk.nq, f32_ ? o.fallbacks : o.refiltered);
         // queries whose hits were written by work enqueued HERE, behind everything begin enqueued: answered by the exact kernels
         // (counted in *fallbacks) or handed by the int8 filter to the f16 filter (re-filtered: certified there, so NOT a fallback) — a
         // caller that chained work to begin's last kernel (a shard's exchange) has to chain it again behind these
-        if (late_answers) *late_answers = async_fb_[t] + refiltered;
+        if (late_answers) *late_answers = o.fallbacks + o.refiltered;
     }
-    async_state_[t] = 0;
-    if (fallbacks) *fallbacks = async_fb_[t];
+    tk.state = BatchedTicket::kFree;
+    if (fallbacks) *fallbacks = tk.fallbacks;
     return ok();
 }
 

@@ -82,7 +82,7 @@ bool VectorIndex::needs_compaction(uint64_t threshold, double ratio) const {
 SearchError VectorIndex::wal_append_batch(uint32_t n, const char* const* doc_ids, const uint32_t* doc_id_lens, const float* vectors,
                                           uint32_t vector_len) {
     if (doc_offsets_.empty()) return make_error(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the live bitmap this call would rewrite)
+    if (any_search_parked())   // (its kernels read the live bitmap this call would rewrite)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     if (n == 0) return ok();
     if (!doc_ids || !vectors) return make_error(FSGPU_ERR_NULL_ARGUMENT, "null argument");
@@ -147,7 +147,7 @@ SearchError VectorIndex::rewrite_refusal() const {
     if (catalog_only_)
         return make_error(FSGPU_ERR_INVALID_CONFIG,
                           "compact / vacuum of a row-sharded index is not supported: the rows would have to be re-sharded");
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (its kernels read the slab this call would replace)
+    if (any_search_parked())   // (its kernels read the slab this call would replace)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     if (lone_.kind != kLoneNone) return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun lone search is outstanding on this index: end it first");
     if (row_stride_ && row_stride_ != dim_ * (f32_ ? 4u : 2u))

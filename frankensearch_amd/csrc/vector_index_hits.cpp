@@ -144,7 +144,7 @@ SearchError VectorIndex::search_hits_batched(const float* queries, uint32_t nq, 
     if (doc_offsets_.empty()) return make_error(FSGPU_ERR_INVALID_CONFIG, "index has no doc-id table");
     FSGPU_TRY(ensure_query_dimension(query_len));
     if (nq == 0) return ok();
-    if (async_state_[0] == 1 || async_state_[1] == 1)   // (this call reads the workspaces and the live bitmap of that search)
+    if (any_search_parked())   // (this call reads the workspaces and the live bitmap of that search)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     const uint64_t W = wal_.size();
     const uint32_t kw = (uint32_t)std::min<uint64_t>(k, W);
@@ -204,7 +204,7 @@ SearchError VectorIndex::search_hits_two_pass_batched(const float* queries, uint
         return search_hits_batched(queries, nq, query_len, k, out_rows, out_scores, out_counts, fallbacks);
     FSGPU_TRY(ensure_query_dimension(query_len));
     if (nq == 0) return ok();
-    if (async_state_[0] == 1 || async_state_[1] == 1)
+    if (any_search_parked())
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun batched search is outstanding on this index: end it first");
     if (k > kHitsMaxK || nrows_ > 0xffffffffull || topk_override || catalog_only_ || row_base_ != 0)   // (as in search_hits_batched)
         return hits_per_query(queries, nq, query_len, k, out_rows, out_scores, out_counts, fallbacks, false, multiplier, bits);

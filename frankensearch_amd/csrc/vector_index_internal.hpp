@@ -1,5 +1,6 @@
 // vector_index_internal.hpp — what the translation units of VectorIndex share: status helpers, the HIP / status early-return
-// macros and the switches read from the environment.  Not installed, not part of the C ABI (include/fsgpu.h is).
+// macros, the switches read from the environment and the batched search's request, outcome, plan, round and ticket.  Not installed,
+// not part of the C ABI (include/fsgpu.h is).
 //   vector_index.cpp          lifecycle, FSVI image, WAL, tombstones, the exact scan paths, MRL views, packed lists
 //   vector_index_batched.cpp  the batched (matrix-core) search: plan, sample, main pass, selections, fallback, tickets, and the
 //                             int8 filter's copy of the slab
@@ -132,6 +133,102 @@ inline uint32_t wide_min_queries(bool two_pass = false) {
 }
 
 }  // namespace detail
+
+// ---- the batched (matrix-core) search: what a call asks for, reports and fixes for its rounds; a begun search -------------------
+// int8_mult == 0: f16 slab, f16-rounded queries, approximate scores + proven margin (mfma_scan.hip header).
+// int8_mult >= 1: int8 slab, int8 queries, exact integer scores; the k * int8_mult best rows are the candidates.
+// i8_filter (int8_mult == 0): int8 slab and queries as the FILTER of the exact search — integer scores + the proven margin of
+//                 prepare_queries_i8_filter_kernel; queries it cannot certify are re-filtered on the f16 path (refiltered) — on an
+//                 F32 slab, whose candidates are re-scored from f32 rows and which has no f16 path, answered by the exact f32 kernels.
+struct VectorIndex::BatchedRequest {
+    BatchedRequest() = default;   // (a plan's before batched_impl fills it in)
+    // what every search names, in the order the entry points of VectorIndex take it; everything else is set by name
+    BatchedRequest(const float* queries, uint32_t nq_, uint32_t query_len_, uint32_t k_, hipStream_t stream_)
+        : queries_dev(queries), nq(nq_), query_len(query_len_), k(k_), stream(stream_) {}
+    const float* queries_dev = nullptr;
+    uint32_t nq = 0, query_len = 0, k = 0;
+    hipStream_t stream = nullptr;
+    const uint64_t* allow_dev = nullptr;
+    uint32_t *out_rows_dev = nullptr, *out_counts_dev = nullptr;
+    float* out_scores_dev = nullptr;
+    uint64_t* out_packed_dev = nullptr;
+    uint32_t int8_mult = 0;
+    uint32_t query_stride = 0;   // floats between queries (0 = dim): an MRL prefix view searches the first dim_ dimensions of full-length queries
+    bool i8_filter = false;
+    int bits = 8;
+    // two_pass_candidates_device_begin: where this batch leaves its candidate pairs (a parked plan's fallback needs them in _end too)
+    u64 *tp_approx = nullptr, *tp_exact = nullptr;
+    uint32_t tp_stride = 0;      // entries between queries in both
+    int ticket = -1;             // the ticket this search parks in once everything is enqueued (-1: blocking)
+    bool nested = false;         // the int8 filter's leftovers on their way through the f16 filter, inside an outer call: never parks
+};
+
+struct VectorIndex::BatchedOutcome {
+    uint32_t fallbacks = 0;    // queries answered by the exact kernels (int8 two-pass: by its per-query form)
+    uint32_t refiltered = 0;   // queries the int8 filter handed to the f16 filter
+    bool parked = false;       // enqueued only: the verdicts are read, and both counts known, in _end
+};
+
+// What one call fixes for all its rounds: the request, the sample sizes, the workspaces.
+struct VectorIndex::BatchedPlan {
+    static constexpr uint32_t GMAX = 160;    // queries per pass: 128 (160 opt-in), or 64 for small batches / tails
+    static constexpr uint32_t CAPQ = 8192;   // entries one selection pass covers: block lists + pool fit it at the wide shape
+    static constexpr uint32_t SPILL = 4096;  // per-query overflow area for candidates that did not fit their block's list
+    static constexpr uint32_t KC = kSelectPool;  // approximate candidates re-scored exactly (at most)
+    static constexpr uint32_t RA_MAX = 8192;
+    BatchedRequest rq;
+    // derived
+    bool i8f = false, i8 = false, strided = false, skip_b = false, wide_ok = false;
+    uint32_t qs = 0;                  // floats between queries
+    uint32_t RA = 4096;               // stage A sample rows (dense; <= 8192)
+    uint32_t RB = 131072;             // stage B sample rows (upper bound; shrinks with the slab)
+    uint32_t ksel_est = 0, ksel = 0;  // the rank the selections anchor on (estimate incl. the int8 filter's growth; exact)
+    uint32_t N = 0, QCAP = 0, wide_max = 0, k_eff = 0;
+    int wide_pref = 3;
+    // per-query verdicts, written by the kernels straight into pinned host memory and read after ONE stream synchronisation
+    uint32_t *overflow_all = nullptr, *counts_all = nullptr;
+    float *delta = nullptr, *tau = nullptr, *unit = nullptr, *tau_floor = nullptr;
+    uint32_t* pool_flag = nullptr;
+    u64 *spill = nullptr, *pool = nullptr;
+    uint32_t* spill_count = nullptr;
+    bool big_pool = false;            // the finish has the second-chance launch: the int8 filter's batches and its leftovers'
+};
+
+// One round: up to QCAP queries — the sample stages and every selection are single launches over all its query groups, only the
+// main pass is one launch per group.
+struct VectorIndex::BatchedRound {
+    uint32_t g0 = 0;                  // first query of the round
+    int wide_qt = 0, shape = 0, wpb = 0, full_grid = 0, wide_grid = 0;
+    uint32_t G = 0, wide_mult = 1, ngroups = 0, QP = 0, ng = 0, tile_rows = 0;
+    const float* qg = nullptr;
+    uint32_t *overflow = nullptr, *cand_counts = nullptr, *cand_count = nullptr;
+    u64* cand = nullptr;
+    MfmaScanArgs a{};
+    SelectArgs sb{};
+    bool anchor = false, short_stages = false;
+    int grid_for(uint32_t rows, uint32_t tile) const {
+        int g = (int)(((rows + tile - 1) / tile + wpb - 1) / wpb);
+        if (g > full_grid) g = full_grid;
+        return g < 1 ? 1 : g;
+    }
+    // one candidate list of `slots` entries per (query, block); 16..32 slots, sized so that lists + pool fit one selection pass
+    // when the grid allows (the wide shape's 256 blocks do)
+    uint32_t slots_for(int grid) const {
+        return std::min<uint32_t>((uint32_t)scan_mfma_max_slots(shape),
+                                  std::max<uint32_t>(16, (BatchedPlan::CAPQ - BatchedPlan::KC) / (uint32_t)grid));
+    }
+};
+
+// A begun search (search_top_k_batched_device_begin / two_pass_candidates_device_begin .. _end).
+struct VectorIndex::BatchedTicket {
+    enum State : uint8_t { kFree, kParked, kFinishedInBegin } state = kFree;   // parked: all is enqueued, _end reads the verdicts behind `event`
+    bool i8f = false;          // the exact search's int8 filter took it: _end keeps the filter's accounts
+    uint32_t nq = 0, fallbacks = 0;
+    hipEvent_t event = nullptr;   // behind the search's last kernel (created on first use, kept)
+    hipStream_t stream = nullptr; // the stream it was enqueued on
+    BatchedPlan plan;             // what _end's fallback stage works from
+};
+
 }  // namespace fsgpu
 
 #define FSGPU_HIP(expr)                                                   \

@@ -74,7 +74,7 @@ SearchError VectorIndex::build_knn_graph(uint64_t first_row, uint64_t n_rows, ui
                                                         " lie past record_count " + std::to_string(nrows_));
     if (n_rows == 0) return ok();
     if (catalog_only_ || !slab_dev_) return make_error(FSGPU_ERR_INVALID_CONFIG, "this index holds no slab of its own");
-    if (async_state_[0] != 0 || async_state_[1] != 0 || lone_.kind != kLoneNone)
+    if (tickets_taken() != 0 || lone_.kind != kLoneNone)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun search is outstanding on this index: end it first (the build takes both tickets)");
     FSGPU_TRY(fetch_live_host());
     FSGPU_HIP(hipSetDevice(device_));

@@ -201,7 +201,7 @@ SearchError VectorIndex::lone_exact_begin(const float* query, uint32_t k) {
             }
         }
     }
-    if (via_filter && async_state_[0] != 0 && async_state_[1] != 0) {   // both tickets of the staged path are out: end() answers, blocking
+    if (via_filter && tickets_taken() == 2) {   // both tickets of the staged path are out: end() answers, blocking
         lone_.kind = kLoneStagedBlocking;
         return ok();
     }
@@ -492,7 +492,7 @@ SearchError VectorIndex::ensure_two_pass_slab(int bits, const void** qslab) {
 
 // One query of a row-sharded two-pass search, this shard's half, in two halves: begin enqueues (the lone caller's lane when the
 // shape allows, else the batched sequence with one query), end yields the shard's cc_out = max(k * multiplier, k) candidate pairs
-// (pass-1 entry, exact entry; kEmpty beyond the candidates) — what two_pass_candidates_device yields for one query.
+// (pass-1 entry, exact entry; kEmpty beyond the candidates) — what two_pass_candidates_device_begin / _end yield for one query.
 SearchError VectorIndex::lone_two_pass_begin(const float* query, uint32_t k, uint32_t multiplier, int bits) {
     lone_ = LoneState{};
     lone_.query = query;
@@ -529,7 +529,7 @@ SearchError VectorIndex::lone_two_pass_begin(const float* query, uint32_t k, uin
         }
     }
     FSGPU_TRY(ws_pairs_.reserve((size_t)lone_.cc_out * 16));
-    if (async_state_[0] != 0 && async_state_[1] != 0) {
+    if (tickets_taken() == 2) {
         lone_.kind = kLoneTwoPassBlocking;
         return ok();
     }

@@ -1268,3 +1268,90 @@ def test_batched_search_in_two_halves_equals_the_blocking_call(fa):
     for x, y in zip(b[0], want[1]):
         assert torch.equal(x.view(torch.int32), y.view(torch.int32))
     idx.close()
+
+
+def test_ticket_bookkeeping_at_the_edge_of_the_verdict_block(fa):
+    """The pinned verdict block does not grow while a search is parked: with a 64-query search begun on a fresh index, a 600-query
+    search — blocking or begun — is refused (INVALID_CONFIG, "... larger batch"), and the refused begin gives its ticket back: one more
+    begin succeeds, the one after it is refused.  Both tickets end with the exact call's rows, score bits and counts, and once they
+    have ended the 600-query search goes through."""
+    import torch
+    from frankensearch_amd.sharded import GpuShardBackend
+    from frankensearch_amd.errors import InvalidConfig
+    rng = np.random.default_rng(31)
+    n, dim, k = 40_000, 128, 10          # just over the 32,768 rows the filters need
+    slab = rand_slab(rng, n, dim)
+    q = rng.standard_normal((600, dim)).astype(np.float32)
+    twin = fa.VectorIndex.from_slab(slab)
+    want = twin.search_batch(q, k, exact=True)   # fsgpu_search_topk_exact
+    twin.close()
+    idx = fa.VectorIndex.from_slab(slab)
+    dev = torch.device("cuda", 0)
+    be = GpuShardBackend(idx, dev, batched=True)
+    qd = torch.from_numpy(q).to(dev)
+
+    def assert_exact(got, lo, hi):
+        torch.cuda.synchronize()
+        r, s, c = (x.cpu().numpy() for x in got)
+        assert np.array_equal(r.view(np.uint32), want[0][lo:hi]), (lo, hi)
+        assert np.array_equal(bits(s), bits(want[1][lo:hi])), (lo, hi)
+        assert np.array_equal(c.view(np.uint32), want[2][lo:hi]), (lo, hi)
+
+    a = be.scan_begin(qd[:64], k, packed=False)          # parks: the verdict block is sized for 64 queries
+    with pytest.raises(InvalidConfig, match="larger batch"):
+        be.search_batched(qd, k)
+    with pytest.raises(InvalidConfig, match="larger batch"):
+        be.scan_begin(qd, k, packed=False)
+    b = be.scan_begin(qd[64:96], k, packed=False)        # the refused begin released its ticket
+    with pytest.raises(InvalidConfig, match="two begun batched searches are outstanding"):
+        be.scan_begin(qd[96:128], k, packed=False)
+    be.scan_end(a[1])
+    be.scan_end(b[1])
+    assert_exact(a[0], 0, 64)
+    assert_exact(b[0], 64, 96)
+    assert_exact(be.search_batched(qd, k), 0, 600)
+    idx.close()
+
+
+def test_end_half_refilters_through_the_nested_f16_batch_on_one_index(fa):
+    """The corpus of test_queries_refiltered_in_the_end_half_travel_again (tests/test_gpu_sharded.py), its smallest parametrisation
+    (90,000 x 256, noise 0.02, 4 clusters, 300 queries, k = 10), on ONE index with two tickets in flight: the int8 filter's lists
+    overflow, and each ticket's END half hands more than 8 queries to the f16 filter as a nested batch (8 or fewer would take the
+    fused exact pass instead).  late_answers is fallbacks + re-filtered, the hits are the exact call's bits, and both tickets'
+    queries are accounted to the int8 filter."""
+    import torch
+    from frankensearch_amd.sharded import GpuShardBackend
+    n, dim, noise, clusters, nq, k = 90_000, 256, 0.02, 4, 300, 10
+    rng = np.random.default_rng(n + k)
+    cent = rng.standard_normal((clusters, dim)).astype(np.float32)
+    x = cent[rng.integers(0, clusters, n)] + (rng.standard_normal((n, dim)) * noise).astype(np.float32)
+    x /= np.linalg.norm(x, axis=1, keepdims=True) + 1e-9
+    slab = x.astype(np.float16).view(np.uint16)
+    q = x[rng.integers(0, n, nq)] + (rng.standard_normal((nq, dim)) * 0.15).astype(np.float32)
+    twin = fa.VectorIndex.from_slab(slab)
+    want = [np.concatenate(z) for z in zip(*[twin.search_batch(q[s0:s0 + 64], k, exact=True) for s0 in range(0, nq, 64)])]
+    twin.close()
+    idx = fa.VectorIndex.from_slab(slab)
+    dev = torch.device("cuda", 0)
+    be = GpuShardBackend(idx, dev, batched=True)
+    qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(dev)
+    st0 = idx.batched_filter_stats()
+    halves = [be.scan_begin(qd[:nq // 2], k, packed=False), be.scan_begin(qd[nq // 2:], k, packed=False)]
+    fallbacks, late = [], []
+    for _, ticket in halves:
+        fallbacks.append(be.scan_end(ticket))
+        late.append(be.last_late_answers)
+    torch.cuda.synchronize()
+    st1 = idx.batched_filter_stats()
+    refiltered = st1["refiltered_f16"] - st0["refiltered_f16"]
+    print(f"fallbacks {fallbacks}  late answers {late}  refiltered_f16 +{refiltered}  int8_queries +{st1['int8_queries'] - st0['int8_queries']}")
+    assert refiltered > 0, "the case no longer re-filters: pick another corpus"
+    for fb, la in zip(fallbacks, late):
+        assert la - fb > 8, (fb, la)      # this ticket's re-filtered queries: the nested batch, not the fused exact pass
+    assert sum(late) == sum(fallbacks) + refiltered
+    got = [np.concatenate([h[0][j].cpu().numpy() for h in halves]) for j in range(3)]
+    assert np.array_equal(got[0].view(np.uint32), want[0])
+    assert np.array_equal(bits(got[1]), bits(want[1]))
+    assert np.array_equal(got[2].view(np.uint32), want[2])
+    assert st1["int8_queries"] - st0["int8_queries"] == nq
+    idx.close()
