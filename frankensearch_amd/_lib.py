@@ -78,6 +78,7 @@ SIGNATURES = {
     "fsgpu_lab_index_set_compact_nt_stores": (_i32, [_vp, _i32]),
     "fsgpu_lab_index_last_rewrite": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(_u64)]),
     "fsgpu_lab_index_attach_synthetic_doc_ids": (_i32, [_vp]),
+    "fsgpu_lab_hash_embed_stage_ms": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "fsgpu_lab_device_copy_ms": (_i32, [_i32, _u64, _u32, C.POINTER(C.c_double)]),
     "fsgpu_index_set_live_bitmap": (_i32, [_vp, _vp]),
     "fsgpu_search_topk": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
@@ -183,6 +184,13 @@ SIGNATURES = {
     "fsgpu_index_builder_add_device": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, C.POINTER(_u64)]),
     "fsgpu_index_builder_add_bert": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "fsgpu_index_builder_add_m2v": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "fsgpu_index_builder_add_hash": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "fsgpu_hash_create": (_i32, [_i32, _u32, _i32, _u64, _vp, C.POINTER(_vp)]),
+    "fsgpu_hash_destroy": (None, [_vp]),
+    "fsgpu_hash_dimension": (_u32, [_vp]),
+    "fsgpu_hash_device": (_i32, [_vp]),
+    "fsgpu_hash_embed": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_hash_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "fsgpu_index_builder_finish": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), _vp]),   # (stats: index_builder._Stats)
     "fsgpu_rerank_apply": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, C.c_float, _vp]),
     "fsgpu_mmr_config_default": (_i32, [_vp]),

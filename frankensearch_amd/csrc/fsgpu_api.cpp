@@ -19,6 +19,7 @@
 #include "bert_embedder.hpp"
 #include "bert_reranker.hpp"
 #include "coalescer.hpp"
+#include "hash_embedder.hpp"
 #include "index_builder.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
@@ -98,6 +99,9 @@ struct fsgpu_reranker {
 };
 struct fsgpu_index_builder {
     fsgpu::IndexBuilder impl;
+};
+struct fsgpu_hash {
+    fsgpu::HashEmbedder impl;
 };
 namespace {
 
@@ -2853,6 +2857,68 @@ fsgpu_status fsgpu_index_builder_finish(fsgpu_index_builder* b, const char* path
         }
         *out_index = h.release();
         return FSGPU_OK;
+    });
+}
+
+// ---- the hash embedder (hash_embedder.cpp): HashEmbedder, crates/frankensearch-embed/src/hash_embedder.rs:201-328 ----
+
+fsgpu_status fsgpu_hash_create(int32_t device, uint32_t dimension, int32_t algorithm, uint64_t seed, const uint8_t* alnum_bitmap_or_null,
+                               fsgpu_hash** out) {
+    if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    *out = nullptr;
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_hash>();
+        fsgpu::SearchError e = h->impl.init(device, dimension, algorithm, seed, alnum_bitmap_or_null);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_hash_destroy(fsgpu_hash* h) { delete h; }
+uint32_t fsgpu_hash_dimension(const fsgpu_hash* h) { return h ? h->impl.dimension() : 0; }
+int32_t fsgpu_hash_device(const fsgpu_hash* h) { return h ? h->impl.device() : -1; }
+
+fsgpu_status fsgpu_hash_embed(fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out,
+                              uint32_t* out_token_counts_or_null, uint32_t* out_bad_text) {
+    if (!h) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
+    if (n && !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    return guarded([&]() -> fsgpu_status {
+        return finish(h->impl.embed_batch(text_bytes, offsets, n, out, nullptr, out_token_counts_or_null, out_bad_text));
+    });
+}
+
+fsgpu_status fsgpu_hash_embed_device(fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out_dev,
+                                     uint32_t* out_token_counts_or_null, uint32_t* out_bad_text) {
+    if (!h) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
+    if (n && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_dev is null");
+    return guarded([&]() -> fsgpu_status {
+        return finish(h->impl.embed_batch(text_bytes, offsets, n, nullptr, out_dev, out_token_counts_or_null, out_bad_text));
+    });
+}
+
+fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out,
+                                           float* out_stage_ms) {
+    if (!h || !out_stage_ms) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (n && !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    return guarded([&]() -> fsgpu_status {
+        return finish(h->impl.embed_batch(text_bytes, offsets, n, out, nullptr, nullptr, nullptr, out_stage_ms));
+    });
+}
+
+fsgpu_status fsgpu_index_builder_add_hash(fsgpu_index_builder* b, fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                          const char* const* doc_ids, const uint32_t* doc_id_lens, uint64_t* out_bad_row) {
+    if (!b) return fail(FSGPU_ERR_NULL_ARGUMENT, "builder is null");
+    if (!h) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
+    return guarded([&]() -> fsgpu_status {
+        // (the call fsgpu_hash_embed_device makes, into the builder's own buffer; a refused text is the call's bad row)
+        auto embed = [&](float* out_dev) {
+            uint32_t bad_text = fsgpu::HashEmbedder::kNoBadText;
+            fsgpu::SearchError e = h->impl.embed_batch(text_bytes, offsets, n, nullptr, out_dev, nullptr, &bad_text);
+            if (!e.ok() && out_bad_row && bad_text != fsgpu::HashEmbedder::kNoBadText) *out_bad_row = bad_text;
+            return e;
+        };
+        return finish(b->impl.add_embedded(embed, h->impl.device(), h->impl.dimension(), n, doc_ids, doc_id_lens, out_bad_row));
     });
 }
 

@@ -225,3 +225,111 @@ class NativeEmbedder:
             self.close()
         except Exception:
             pass
+
+
+# fsgpu_hash_create's algorithm (include/fsgpu.h): the keyword of HashEmbedder -> FSGPU_HASH_*
+HASH_ALGORITHMS = {"fnv_modular": 0, "jl": 1}
+ALNUM_BITMAP_BYTES = 0x110000 // 8
+
+
+def python_alnum_bitmap() -> np.ndarray:
+    """The alphanumeric table of fsgpu_hash_create (0x110000 bits, bit c = byte[c >> 3] >> (c & 7) & 1) built from `str.isalnum`.
+
+    These are PYTHON's tables, not Rust's: `char::is_alphanumeric` is Alphabetic | Nd | Nl | No of the Rust toolchain's Unicode
+    version, `str.isalnum` is the L* | Nd | Nl | No categories of this interpreter's, and the two differ on the `Other_Alphabetic`
+    combining marks (and wherever the Unicode versions differ).  A host that wants the reference's bits passes the table its own
+    toolchain gives."""
+    bits = np.zeros(0x110000, dtype=np.uint8)
+    for c in range(0x110000):
+        if chr(c).isalnum():
+            bits[c] = 1
+    return np.packbits(bits, bitorder="little")
+
+
+def _text_arrays(texts: Sequence[str]):
+    """Texts -> the C ABI's shape: UTF-8 bytes back to back (uint8) and uint32 offsets [n + 1]."""
+    raw = [t if isinstance(t, (bytes, bytearray)) else str(t).encode("utf-8", "surrogatepass") for t in texts]
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint32)
+    total = 0
+    for i, b in enumerate(raw):
+        total += len(b)
+        if total > 0xFFFFFFFF:
+            raise ValueError("a batch of texts must stay below 4 GiB")
+        offsets[i + 1] = total
+    flat = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+    return flat, offsets
+
+
+class HashEmbedder:
+    """The hash embedder (crates/frankensearch-embed/src/hash_embedder.rs:201-328): raw text in, no weights.  `algorithm` is
+    "fnv_modular" (HashAlgorithm::FnvModular) or "jl" (JLProjection { seed }).  `alnum_bitmap` (139,264 bytes, see
+    python_alnum_bitmap) says which code points above U+007F are alphanumeric; without one the embedder is ASCII only and refuses
+    any other text.  A refused text raises with `.bad_text` set to its index in the call; nothing is written."""
+
+    def __init__(self, dimension: int = 384, algorithm: str = "fnv_modular", seed: int = 0, device: int = 0, alnum_bitmap=None):
+        if isinstance(algorithm, str):
+            if algorithm not in HASH_ALGORITHMS:
+                raise ValueError(f"algorithm must be one of {sorted(HASH_ALGORITHMS)}, not {algorithm!r}")
+            algorithm = HASH_ALGORITHMS[algorithm]
+        bm = None
+        if alnum_bitmap is not None:
+            bm = np.ascontiguousarray(alnum_bitmap, dtype=np.uint8).reshape(-1)
+            if bm.size != ALNUM_BITMAP_BYTES:
+                raise ValueError(f"alnum_bitmap must hold {ALNUM_BITMAP_BYTES} bytes")
+        h = C.c_void_p()
+        check(_lib.lib().fsgpu_hash_create(device, dimension, algorithm, seed & 0xFFFFFFFFFFFFFFFF, None if bm is None else bm.ctypes.data,
+                                           C.byref(h)))
+        self._h = h
+        self._dim = dimension
+        self.device = device
+        self.last_token_counts = None
+
+    @classmethod
+    def default_384(cls, **kw) -> "HashEmbedder":
+        return cls(384, "fnv_modular", **kw)
+
+    @classmethod
+    def default_256(cls, **kw) -> "HashEmbedder":
+        return cls(256, "fnv_modular", **kw)
+
+    @classmethod
+    def jl_384(cls, seed: int, **kw) -> "HashEmbedder":
+        return cls(384, "jl", seed, **kw)
+
+    def dimension(self) -> int:
+        return self._dim
+
+    def _call(self, fn, texts, out_ptr):
+        from .errors import SearchError
+        flat, offsets = _text_arrays(texts)
+        n = offsets.shape[0] - 1
+        counts = np.zeros(n, dtype=np.uint32)
+        bad = C.c_uint32(0xFFFFFFFF)
+        try:
+            check(fn(self._h, flat.ctypes.data, offsets.ctypes.data, n, out_ptr, counts.ctypes.data, C.byref(bad)))
+        except SearchError as e:
+            e.bad_text = None if bad.value == 0xFFFFFFFF else int(bad.value)
+            raise
+        self.last_token_counts = counts
+
+    def embed(self, texts: Sequence[str], out: np.ndarray = None) -> np.ndarray:
+        """embed_batch_sync (hash_embedder.rs:254-260) -> [n, dimension] f32; `last_token_counts` holds the tokens hashed per text."""
+        if out is None:
+            out = np.empty((len(texts), self._dim), dtype=np.float32)
+        self._call(_lib.lib().fsgpu_hash_embed, texts, out.ctypes.data)
+        return out
+
+    def embed_device(self, texts: Sequence[str], out_ptr: int) -> None:
+        """... into [n, dimension] f32 of the embedder's device (a torch tensor's data_ptr(), fsgpu_device_malloc)."""
+        self._call(_lib.lib().fsgpu_hash_embed_device, texts, out_ptr)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().fsgpu_hash_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -111,12 +111,19 @@ class IndexBuilder:
 
     def add_texts(self, embedder, doc_ids: Sequence, batch: Sequence[Sequence[int]]) -> None:
         """Pre-tokenised texts embedded on the device by a NativeEmbedder or a Model2VecEmbedder and ingested where the embedder left
-        them (fsgpu_index_builder_add_bert / _add_m2v)."""
-        from .embed import Model2VecEmbedder
+        them (fsgpu_index_builder_add_bert / _add_m2v).  With a HashEmbedder the batch is a sequence of str (_add_hash)."""
+        from .embed import HashEmbedder, Model2VecEmbedder, _text_arrays
         m2v = isinstance(embedder, Model2VecEmbedder)
         n = len(batch)
         if n != len(doc_ids):
             raise ValueError("one doc id per text")
+        if isinstance(embedder, HashEmbedder):   # raw texts: a sequence of str (fsgpu_index_builder_add_hash)
+            flat, offsets = _text_arrays(batch)
+            ids, arr, lens = _doc_id_arrays(doc_ids)
+            bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+            self._checked(_lib.lib().fsgpu_index_builder_add_hash(self._h, embedder._h, flat.ctypes.data, offsets.ctypes.data, n,
+                                                                  C.cast(arr, C.c_void_p), lens.ctypes.data, C.byref(bad)), bad)
+            return
         offsets = np.zeros(n + 1, dtype=np.uint32)
         for i, t in enumerate(batch):
             offsets[i + 1] = offsets[i] + len(t)

@@ -69,6 +69,7 @@ typedef int32_t fsgpu_status;
 
 typedef struct fsgpu_index fsgpu_index;     /* device-resident VectorIndex (lib.rs:819) */
 typedef struct fsgpu_m2v fsgpu_m2v;         /* Model2VecEmbedder (embed/src/model2vec_embedder.rs:55) */
+typedef struct fsgpu_hash fsgpu_hash;       /* HashEmbedder (embed/src/hash_embedder.rs:201) */
 typedef struct fsgpu_bert fsgpu_bert;       /* NativeEmbedder (rerank/src/native_embedder.rs:40-50) */
 typedef struct fsgpu_reranker fsgpu_reranker; /* NativeReranker, the cross-encoder (rerank/src/native.rs:1240) */
 
@@ -599,6 +600,36 @@ uint32_t fsgpu_m2v_dimension(const fsgpu_m2v *m); /* Embedder::dimension (crates
  * ids[offsets[i]..offsets[i+1]); out is [n,dim].  Empty / all-OOV texts give zeros. */
 fsgpu_status fsgpu_m2v_embed(fsgpu_m2v *m, const uint32_t *ids, const uint32_t *offsets, uint32_t n, float *out);
 
+/* ---- HashEmbedder: FNV-1a modular / JL projection from raw text, no weights ---- */
+/* HashEmbedder::new (embed/src/hash_embedder.rs:215-223): the reference's test double and fast-tier fall-back (default_384 =
+ * {384, FNV_MODULAR}, default_256 = {256, FNV_MODULAR}, jl_384(seed) = {384, JL_PROJECTION, seed}).  The vectors equal
+ * embed_sync's in every bit: tokenize :601-685 (split on !char::is_alphanumeric, tokens of >= 2 UTF-8 bytes, case kept),
+ * fnv1a_hash :588-595, embed_fnv_modular :263-280, embed_jl :299-346, l2_normalize_in_place (core/src/traits.rs:606-618).
+ * alnum_bitmap_or_null: 0x110000 bits (139,264 bytes), bit c = byte[c >> 3] >> (c & 7) & 1 = char::is_alphanumeric of code point
+ * c, made by the caller from its own toolchain's table and copied to the device once.  With NULL the embedder is ASCII only.
+ * dimension 0 (the reference panics), dimension > 1,024 and an unknown algorithm are FSGPU_ERR_INVALID_CONFIG, decided before a
+ * device is looked for; then no device is FSGPU_ERR_NO_DEVICE.  seed is read by FSGPU_HASH_JL_PROJECTION only. */
+#define FSGPU_HASH_FNV_MODULAR 0   /* HashAlgorithm::FnvModular */
+#define FSGPU_HASH_JL_PROJECTION 1 /* HashAlgorithm::JLProjection { seed } */
+fsgpu_status fsgpu_hash_create(int32_t device, uint32_t dimension, int32_t algorithm, uint64_t seed,
+                               const uint8_t *alnum_bitmap_or_null, fsgpu_hash **out);
+void fsgpu_hash_destroy(fsgpu_hash *h);
+uint32_t fsgpu_hash_dimension(const fsgpu_hash *h);
+int32_t fsgpu_hash_device(const fsgpu_hash *h);
+/* embed_batch_sync (:254-260): text i owns text_bytes[offsets[i]..offsets[i+1]); offsets must be non-decreasing and
+ * text_bytes hold offsets[n] bytes; out is [n, dimension] f32; out_token_counts_or_null[n] = tokens hashed per text.  An empty or
+ * token-less text gives zeros.  Refused with FSGPU_ERR_INVALID_CONFIG, *out_bad_text (nullable) = the first such text, nothing
+ * written and nothing launched: a text with a byte >= 0x80 when the embedder has no table; with a table, a text that is not
+ * strict UTF-8 (overlong forms, surrogates, values past U+10FFFF, truncated sequences: what a &str cannot hold); a text longer
+ * than 32 MiB (it could hold 2^24 tokens, where the exact-integer argument of :294-298 ends).  Otherwise *out_bad_text is
+ * 0xFFFFFFFF. */
+fsgpu_status fsgpu_hash_embed(fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n, float *out,
+                              uint32_t *out_token_counts_or_null, uint32_t *out_bad_text);
+/* ... with the [n, dimension] output left in memory of the embedder's device, where
+ * fsgpu_search_topk_batched_device_queries and fsgpu_index_builder_add_device take it. */
+fsgpu_status fsgpu_hash_embed_device(fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n, float *out_dev,
+                                     uint32_t *out_token_counts_or_null, uint32_t *out_bad_text);
+
 /* ---- MiniLM-class BERT embedder ---- */
 /* NativeEmbedder::load (native_embedder.rs:60-116): copies the weights to the GPU (linears as f16). */
 fsgpu_status fsgpu_bert_create(int32_t device, const fsgpu_bert_config *config, const fsgpu_bert_weights *weights,
@@ -767,6 +798,11 @@ fsgpu_status fsgpu_index_builder_add_bert(fsgpu_index_builder *b, fsgpu_bert *m,
                                           const char *const *doc_ids, const uint32_t *doc_id_lens_or_null, uint64_t *out_bad_row);
 fsgpu_status fsgpu_index_builder_add_m2v(fsgpu_index_builder *b, fsgpu_m2v *m, const uint32_t *ids, const uint32_t *offsets, uint32_t n,
                                          const char *const *doc_ids, const uint32_t *doc_id_lens_or_null, uint64_t *out_bad_row);
+/* ... raw texts through a hash embedder, by the call fsgpu_hash_embed_device makes.  A text the embedder refuses is the call's
+ * *out_bad_row; an empty or token-less text embeds to zeros and is refused by the norm rule naming its row, as above. */
+fsgpu_status fsgpu_index_builder_add_hash(fsgpu_index_builder *b, fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets,
+                                          uint32_t n, const char *const *doc_ids, const uint32_t *doc_id_lens_or_null,
+                                          uint64_t *out_bad_row);
 /* VectorIndexWriter::finish (lib.rs:3752-3943).  The file, when path is given, is written to `path`.tmp and renamed over `path`, as
  * fsgpu_index_compact writes its image.  A finished builder is spent, as finish(self) consumes the reference's: only destroy and
  * record_count remain valid (anything else is FSGPU_ERR_INVALID_CONFIG).  A finish that fails (I/O, allocation) leaves the builder

@@ -187,6 +187,10 @@ fsgpu_status fsgpu_lab_index_attach_synthetic_doc_ids(fsgpu_index *idx);
 fsgpu_status fsgpu_lab_index_wal_scores(fsgpu_index *idx, const float *queries, uint32_t nq, float *out);
 /* The yardstick of the copy kernel: `reps` hipMemcpyDtoD of `bytes` between two fresh buffers, each timed by events (ms). */
 fsgpu_status fsgpu_lab_device_copy_ms(int32_t device, uint64_t bytes, uint32_t reps, double *out_ms);
+/* fsgpu_hash_embed with the device's own time of its three stages, between events on the embedder's stream (ms):
+ * out_stage_ms[3] = {texts and offsets to the device, the kernel, vectors back to `out`}. */
+fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n, float *out,
+                                           float *out_stage_ms);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
