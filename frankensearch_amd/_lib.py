@@ -159,6 +159,8 @@ SIGNATURES = {
     "fsgpu_lab_scan_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_scan_stage_args: ScanStageArgs below)
     "fsgpu_lab_scan_stage_check": (_i32, [_vp]),
     "fsgpu_lab_scan_planner_shape": (_i32, [_i32, _i32]),
+    "fsgpu_lab_select": (_i32, [_i32, _vp]),   # (fsgpu_lab_select_args: SelectLabArgs below)
+    "fsgpu_lab_select_check": (_i32, [_vp]),
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
@@ -266,6 +268,17 @@ class ScanStageArgs(C.Structure):
                                           "nq_pad", "want_counts", "nq", "max_norm_bits", "bits", "reserved")] + [
         (name, _vp) for name in ("slab", "live", "allow", "queries", "tau", "queries_f32", "cand", "cand_count", "spill", "spill_count",
                                  "overflow", "dense", "prepared", "delta")]
+
+
+class SelectLabArgs(C.Structure):
+    """fsgpu_lab_select_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("kernel", "nq", "valid_queries", "k")] + [("q_stride", _u64), ("shard_pitch", _u64)] + [
+        (name, _u32) for name in ("l_stride", "nlists", "list_len", "extra_len", "spill_cap", "reset_spill", "take_topk", "heur_rank", "big_pool",
+                                  "dim", "nrows", "row_base", "row_stride", "query_stride")] + [("hreduce", _i32)] + [
+        (name, _u32) for name in ("k_out", "out_stride", "cand_out_stride", "slab_f32", "nentries", "rank_only", "nshards", "cc")] + [
+        (name, _vp) for name in ("lists", "list_counts", "extra", "spill", "exact_lists", "delta", "anchor_unit", "tau_floor_in", "slab", "live",
+                                 "allow", "queries", "spill_count", "pool_flag", "tau_out", "tau_floor_out", "pool_out", "cand_counts",
+                                 "overflow", "out_rows", "out_scores", "out_packed", "out_counts", "cand_approx_out", "cand_exact_out")]
 
 
 _lib = None

@@ -2589,6 +2589,246 @@ fsgpu_status fsgpu_lab_scan_stage(int32_t device, const fsgpu_lab_scan_stage_arg
     });
 }
 
+namespace {
+// What fsgpu_lab_select derives from its arguments once they have passed: array sizes in elements.
+struct SelectGeom {
+    size_t lists_n = 0, exact_n = 0, counts_n = 0, query_rows = 0, query_pitch = 0, slab_pitch = 0, bitmap_words = 0;
+    bool finish = false;
+};
+
+fsgpu_status select_check(const fsgpu_lab_select_args& a, SelectGeom* geom) {
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    auto null = [](const char* what) { return fail(FSGPU_ERR_NULL_ARGUMENT, what); };
+    SelectGeom g;
+    if (a.kernel > FSGPU_LAB_TWO_PASS_MERGE) return bad("select: unknown kernel");
+    if (a.kernel != FSGPU_LAB_LIST_CUT && (a.nq == 0 || a.nq > 4096)) return bad("select: nq must be in 1..=4096");
+    if (a.valid_queries > a.nq) return bad("select: valid_queries beyond nq");
+    if (a.dim > 4096 || a.nrows > (1u << 22) || a.spill_cap > (1u << 20) || a.extra_len > (1u << 20) || a.out_stride > 4096 || a.cand_out_stride > 4096)
+        return bad("select: dim, nrows, spill_cap, extra_len or an output stride out of range");
+    if (a.reset_spill > 1 || a.big_pool > 2 || a.hreduce < 0 || a.hreduce > 2) return bad("select: a flag out of range");
+    // the slab and the queries of a re-score (SELECT's finish, the anchored SELECT_GROUPS)
+    auto rescore_geom = [&](bool strided) -> fsgpu_status {
+        const size_t elem = a.slab_f32 ? 4 : 2;
+        g.slab_pitch = strided && a.row_stride ? a.row_stride : (size_t)a.dim * elem;
+        if (a.dim == 0 || a.nrows == 0) return bad("select: a re-score needs dim and nrows");
+        if (g.slab_pitch < (size_t)a.dim * elem || (g.slab_pitch & 15) || g.slab_pitch > (1u << 16)) return bad("select: row_stride must be a multiple of 16 bytes that holds a row");
+        if ((uint64_t)a.nrows * g.slab_pitch > (1ull << 30)) return bad("select: the slab exceeds 1 GB");
+        g.query_pitch = a.query_stride ? a.query_stride : a.dim;
+        if (g.query_pitch < a.dim) return bad("select: query_stride below dim");
+        g.query_rows = a.valid_queries ? a.valid_queries : a.nq;
+        g.bitmap_words = ((size_t)a.nrows + 63) / 64;
+        if (!a.queries) return null("select: queries is null");
+        return FSGPU_OK;
+    };
+    if (a.kernel == FSGPU_LAB_SELECT) {
+        fsgpu::SelectArgs s{};
+        s.nlists = a.nlists, s.list_len = a.list_len, s.k = a.k, s.k_out = a.k_out, s.dim = a.dim, s.row_stride = a.row_stride, s.slab_f32 = a.slab_f32;
+        s.delta = a.delta, s.slab = a.slab;
+        if (!a.delta) return null("select: delta is null");
+        if (!fsgpu::select_args_ok(s)) return bad("select: launch_select refuses the arguments");
+        const uint64_t need = a.nlists && a.list_len ? (uint64_t)(a.nlists - 1) * a.l_stride + a.list_len : 0;
+        if (a.l_stride < a.list_len || a.q_stride < need || (uint64_t)a.nq * a.q_stride > (1ull << 25)) return bad("select: q_stride / l_stride do not hold the lists, or they exceed 2^25 entries");
+        if ((uint64_t)a.nlists * a.list_len + a.extra_len + a.spill_cap > (1u << 22)) return bad("select: more than 2^22 entries per query");
+        g.lists_n = (size_t)a.nq * a.q_stride;
+        g.counts_n = (size_t)a.nq * a.nlists;
+        if (need && !a.lists) return null("select: lists is null");
+        if (a.extra_len && !a.extra) return null("select: extra is null");
+        if (a.spill && !a.spill_count) return null("select: spill without spill_count");
+        if (a.reset_spill && !a.spill_count) return null("select: reset_spill without spill_count");
+        if (a.big_pool && !a.pool_flag) return null("select: the big-pool forms need pool_flag");
+        g.finish = a.slab != nullptr;
+        if (g.finish) {
+            if (const fsgpu_status st = rescore_geom(true); st != FSGPU_OK) return st;
+            if (a.out_stride < a.k_out) return bad("select: out_stride below k_out");
+            if ((a.cand_approx_out || a.cand_exact_out) && a.cand_out_stride < a.k) return bad("select: cand_out_stride below k");
+        } else if (a.big_pool || a.anchor_unit || a.out_rows || a.out_scores || a.out_packed || a.out_counts || a.cand_approx_out || a.cand_exact_out) {
+            return bad("select: a finish field without a slab");
+        }
+    } else if (a.kernel == FSGPU_LAB_SELECT_GROUPS) {
+        fsgpu::GroupSelectArgs s{};
+        s.nentries = a.nentries, s.k = a.k, s.dim = a.dim, s.rank_only = a.rank_only;
+        s.delta = a.delta, s.tau_out = a.tau_out, s.anchor_unit = a.anchor_unit, s.slab = a.slab;
+        if (!a.delta || !a.tau_out) return null("select: delta or tau_out is null");
+        if (!a.rank_only && (!a.anchor_unit || !a.slab)) return null("select: the anchored form needs anchor_unit and slab");
+        if (!fsgpu::select_groups_args_ok(s)) return bad("select: launch_select_groups refuses the arguments");
+        if (!a.lists) return null("select: lists is null");
+        if (a.reset_spill && !a.spill_count) return null("select: reset_spill without spill_count");
+        g.lists_n = (size_t)a.nq * a.nentries;
+        g.finish = !a.rank_only;
+        if (g.finish)
+            if (const fsgpu_status st = rescore_geom(false); st != FSGPU_OK) return st;
+    } else if (a.kernel == FSGPU_LAB_LIST_CUT) {
+        if (!fsgpu::list_cut_args_ok(a.nlists, a.list_len)) return bad("select: launch_list_cut refuses the arguments");
+        if ((uint64_t)a.nlists * a.list_len > (1ull << 25)) return bad("select: the lists exceed 2^25 entries");
+        g.lists_n = (size_t)a.nlists * a.list_len;
+        if ((g.lists_n && !a.lists) || !a.tau_out) return null("select: lists or tau_out is null");
+    } else {
+        if (!fsgpu::two_pass_merge_args_ok(a.nshards, a.cc, a.k)) return bad("select: launch_two_pass_merge refuses the arguments");
+        if (a.nshards == 0 || a.shard_pitch < (uint64_t)a.nq * a.cc || (uint64_t)a.nshards * a.shard_pitch > (1ull << 25)) return bad("select: shard_pitch does not hold nq x cc entries, or the lists exceed 2^25");
+        g.lists_n = g.exact_n = (size_t)a.nshards * a.shard_pitch;
+        if (!a.lists || !a.exact_lists) return null("select: lists or exact_lists is null");
+    }
+    if (geom) *geom = g;
+    return FSGPU_OK;
+}
+}  // namespace
+
+fsgpu_status fsgpu_lab_select_check(const fsgpu_lab_select_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return select_check(*args, nullptr);
+}
+
+fsgpu_status fsgpu_lab_select(int32_t device, const fsgpu_lab_select_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_select_args& a = *args;
+    SelectGeom g;
+    if (const fsgpu_status st = select_check(a, &g); st != FSGPU_OK) return st;
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        // outputs: [band | body | band], the bands of kGuardByte; the body prefilled with `fill`, or with the caller's contents (init)
+        constexpr size_t kBand = 4096;
+        struct Out {
+            unsigned char* base;
+            size_t bytes;
+            void* host;
+        };
+        std::vector<Out> outs;
+        auto out = [&](size_t bytes, int fill, void* host, bool init = false) -> void* {
+            if (bytes == 0 || !host) return nullptr;
+            unsigned char* base = static_cast<unsigned char*>(s.alloc(bytes + 2 * kBand));
+            if (s.ok()) s.hip(hipMemset(base, LabStage::kGuardByte, bytes + 2 * kBand));
+            if (s.ok()) s.hip(init ? hipMemcpy(base + kBand, host, bytes, hipMemcpyHostToDevice) : hipMemset(base + kBand, fill, bytes));
+            outs.push_back({base, bytes, host});
+            return s.ok() ? base + kBand : nullptr;
+        };
+        auto in_u64 = [&](const uint64_t* src, size_t n) -> const fsgpu::u64* {
+            return src && n ? static_cast<const fsgpu::u64*>(s.raw(src, n * 8)) : static_cast<const fsgpu::u64*>(s.alloc(16));
+        };
+        auto in_f32 = [&](const float* src, size_t n) -> const float* { return src && n ? s.f32(src, n) : nullptr; };
+        // the slab with NaN guard rows behind its last row, the queries with NaN rows behind the last valid one
+        constexpr size_t kGuardRows = 64;
+        auto nan_tail = [&](const void* src, size_t body, size_t tail, bool half) -> void* {
+            std::vector<unsigned char> h(body + tail);
+            std::memcpy(h.data(), src, body);
+            if (half)   // f16 0x7e00
+                for (size_t i = body; i + 1 < body + tail; i += 2) h[i] = 0x00, h[i + 1] = 0x7e;
+            else        // f32 0x7fc00000
+                for (size_t i = body; i + 3 < body + tail; i += 4) h[i] = 0, h[i + 1] = 0, h[i + 2] = 0xc0, h[i + 3] = 0x7f;
+            return s.raw(h.data(), h.size());
+        };
+        const void* slab = nullptr;
+        const float* queries = nullptr;
+        const fsgpu::u64 *live = nullptr, *allow = nullptr;
+        if (g.finish) {
+            slab = nan_tail(a.slab, (size_t)a.nrows * g.slab_pitch, kGuardRows * g.slab_pitch, !a.slab_f32);
+            queries = static_cast<const float*>(nan_tail(a.queries, g.query_rows * g.query_pitch * 4, kGuardRows * g.query_pitch * 4, false));
+            auto bitmap = [&](const uint64_t* src) -> const fsgpu::u64* {
+                if (!src) return nullptr;
+                std::vector<uint64_t> w(g.bitmap_words + 2, 0);   // (two zero words behind the last)
+                std::memcpy(w.data(), src, g.bitmap_words * 8);
+                return static_cast<const fsgpu::u64*>(s.raw(w.data(), w.size() * 8));
+            };
+            live = bitmap(a.live);
+            allow = bitmap(a.allow);
+        }
+        const fsgpu::u64* lists = in_u64(a.lists, g.lists_n);
+        uint32_t* spill_count = static_cast<uint32_t*>(out((size_t)a.nq * fsgpu::kMfmaSpillCountStride * 4, 0, a.spill_count, true));
+        float* tau_out = static_cast<float*>(out((a.kernel == FSGPU_LAB_LIST_CUT ? 1 : (size_t)a.nq) * 4, 0xCD, a.tau_out));
+        uint32_t* overflow = static_cast<uint32_t*>(out((size_t)a.nq * 4, 0, a.overflow));
+        if (a.kernel == FSGPU_LAB_SELECT) {
+            fsgpu::SelectArgs m{};
+            m.lists = lists;
+            m.q_stride = a.q_stride;
+            m.l_stride = a.l_stride, m.nlists = a.nlists, m.list_len = a.list_len;
+            m.list_counts = a.list_counts && g.counts_n ? static_cast<const uint32_t*>(s.raw(a.list_counts, g.counts_n * 4)) : nullptr;
+            m.extra = a.extra_len ? in_u64(a.extra, (size_t)a.nq * a.extra_len) : nullptr;
+            m.extra_len = a.extra_len;
+            m.spill = a.spill ? in_u64(a.spill, (size_t)a.nq * a.spill_cap) : nullptr;
+            m.spill_count = spill_count;
+            m.spill_cap = a.spill_cap;
+            m.k = a.k;
+            m.spill_reset = a.reset_spill ? spill_count : nullptr;
+            m.delta = in_f32(a.delta, a.nq);
+            m.tau_out = tau_out;
+            m.pool_out = static_cast<fsgpu::u64*>(out((size_t)a.nq * fsgpu::kSelectPool * 8, 0xCD, a.pool_out));
+            m.cand_counts = static_cast<uint32_t*>(out((size_t)a.nq * 4, 0xCD, a.cand_counts));
+            m.overflow = overflow;
+            m.take_topk = a.take_topk;
+            m.anchor_unit = in_f32(a.anchor_unit, a.nq);
+            m.heur_rank = a.heur_rank;
+            m.tau_floor_out = static_cast<float*>(out((size_t)a.nq * 4, 0xCD, a.tau_floor_out));
+            m.tau_floor_in = in_f32(a.tau_floor_in, a.nq);
+            m.pool_flag = static_cast<uint32_t*>(out((size_t)a.nq * 4, 0, a.pool_flag, true));
+            m.slab = slab;
+            m.queries = queries;
+            m.dim = a.dim, m.nrows = a.nrows, m.row_base = a.row_base, m.row_stride = a.row_stride, m.query_stride = a.query_stride;
+            m.hreduce = a.hreduce;
+            m.k_out = a.k_out, m.out_stride = a.out_stride;
+            m.out_rows = static_cast<uint32_t*>(out((size_t)a.nq * a.out_stride * 4, 0xCD, a.out_rows));
+            m.out_scores = static_cast<float*>(out((size_t)a.nq * a.out_stride * 4, 0xCD, a.out_scores));
+            m.out_packed = static_cast<fsgpu::u64*>(out((size_t)a.nq * a.out_stride * 8, 0xCD, a.out_packed));
+            m.out_counts = static_cast<uint32_t*>(out((size_t)a.nq * 4, 0xCD, a.out_counts));
+            m.cand_approx_out = static_cast<fsgpu::u64*>(out((size_t)a.nq * a.cand_out_stride * 8, 0xCD, a.cand_approx_out));
+            m.cand_exact_out = static_cast<fsgpu::u64*>(out((size_t)a.nq * a.cand_out_stride * 8, 0xCD, a.cand_exact_out));
+            m.cand_out_stride = a.cand_out_stride;
+            m.valid_queries = a.valid_queries;
+            m.slab_f32 = a.slab_f32;
+            if (s.ok() && a.big_pool != 2) s.hip(fsgpu::launch_select(m, (int)a.nq, nullptr));
+            if (s.ok() && a.big_pool != 0) {
+                m.big_pool = 1;
+                s.hip(fsgpu::launch_select(m, (int)a.nq, nullptr));
+            }
+        } else if (a.kernel == FSGPU_LAB_SELECT_GROUPS) {
+            fsgpu::GroupSelectArgs m{};
+            m.groups = lists;
+            m.nentries = a.nentries;
+            m.k = a.k;
+            m.delta = in_f32(a.delta, a.nq);
+            m.anchor_unit = in_f32(a.anchor_unit, a.nq);
+            m.tau_out = tau_out;
+            m.overflow = overflow;
+            m.spill_reset = a.reset_spill ? spill_count : nullptr;
+            m.slab = slab;
+            m.live = live, m.allow = allow;
+            m.queries = queries;
+            m.dim = a.dim, m.nrows = a.nrows, m.row_base = a.row_base, m.query_stride = a.query_stride;
+            m.hreduce = a.hreduce;
+            m.valid_queries = a.valid_queries;
+            m.slab_f32 = a.slab_f32;
+            m.rank_only = a.rank_only;
+            if (s.ok()) s.hip(fsgpu::launch_select_groups(m, (int)a.nq, nullptr));
+        } else if (a.kernel == FSGPU_LAB_LIST_CUT) {
+            if (s.ok()) s.hip(fsgpu::launch_list_cut(lists, a.nlists, a.list_len, tau_out, nullptr));
+        } else {
+            const fsgpu::u64* exact = in_u64(a.exact_lists, g.exact_n);
+            uint32_t* rows = static_cast<uint32_t*>(out((size_t)a.nq * a.out_stride * 4, 0xCD, a.out_rows));
+            float* scores = static_cast<float*>(out((size_t)a.nq * a.out_stride * 4, 0xCD, a.out_scores));
+            uint32_t* counts = static_cast<uint32_t*>(out((size_t)a.nq * 4, 0xCD, a.out_counts));
+            if (s.ok()) s.hip(fsgpu::launch_two_pass_merge(lists, exact, a.nshards, a.shard_pitch, a.nq, a.cc, a.k, a.out_stride, rows, scores, counts, nullptr));
+        }
+        s.hip(hipStreamSynchronize(nullptr));
+        bool guard_hit = false;
+        for (const Out& o : outs) {
+            if (!s.ok()) break;
+            std::vector<unsigned char> h(o.bytes + 2 * kBand);
+            s.hip(hipMemcpy(h.data(), o.base, h.size(), hipMemcpyDeviceToHost));
+            if (!s.ok()) break;
+            for (size_t i = 0; i < kBand; ++i)
+                if (h[i] != LabStage::kGuardByte || h[kBand + o.bytes + i] != LabStage::kGuardByte) guard_hit = true;
+            std::memcpy(o.host, h.data() + kBand, o.bytes);
+        }
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he == hipErrorInvalidValue) return fail(FSGPU_ERR_INVALID_CONFIG, "select: the launcher refused the arguments");
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (guard_hit) return fail(FSGPU_ERR_DEVICE, "select: a kernel wrote into a guard band of its output");
+        return FSGPU_OK;
+    });
+}
+
 fsgpu_status fsgpu_bert_embed_device(fsgpu_bert* m, const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out_dev) {
     if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
     if (n && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_dev is null");

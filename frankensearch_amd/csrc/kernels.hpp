@@ -215,6 +215,11 @@ struct GroupSelectArgs {
 constexpr uint32_t kGroupsTaken = 24;      // groups whose rows are re-scored for ranks up to 24 (192 rows) ...
 constexpr uint32_t kGroupsTakenMax = 32;   // ... and up to 32 (256 rows: the two-tier flow's fetch of 3 x 10)
 constexpr uint32_t kGroupsRankMax = 128;   // rank-only form (int8 / 4-bit two-pass: k x multiplier candidates, 3 x 30 = 90)
+// (the launchers' predicates: what they refuse with hipErrorInvalidValue before anything is launched; host code, no device needed)
+bool select_args_ok(const SelectArgs& args);
+bool select_groups_args_ok(const GroupSelectArgs& args);
+bool list_cut_args_ok(uint32_t nlists, uint32_t list_len);
+bool two_pass_merge_args_ok(uint32_t nshards, uint32_t cc, uint32_t k);
 hipError_t launch_select_groups(const GroupSelectArgs& args, int nq, hipStream_t stream);
 constexpr uint32_t kSelectPool = 1024;
 constexpr uint32_t kSelectMaxK = 128;   // largest rank a selection can anchor on (k, or k * multiplier in int8 mode)

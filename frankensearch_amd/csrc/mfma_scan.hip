@@ -559,6 +559,25 @@ __global__ __launch_bounds__(kSelThreads, SORTED ? 4 : kSelMinWaves) void select
                 if (__uint_as_float((uint32_t)(sbuf[j] >> 32)) >= tau) atomicMax(&s_count, j + 1);
             __syncthreads();
             ncand = s_count;
+            if (tau == -INFINITY && ncand > 0) {   // block-uniform; only a query without a threshold comes here
+                // The entries that rank as -inf are ordered by row alone, so a NaN score can sit in front of a -inf one, inside the
+                // prefix: it is no candidate (score >= tau is false for it, as in the extraction form) — close the gaps.  What lies
+                // behind the candidates is not read again.
+                __syncthreads();   // (every thread has read s_count)
+                if (tid == 0) {
+                    int f = ncand;
+                    while (f > 0 && score_ord((uint32_t)(sbuf[f - 1] >> 32)) == score_ord(0xff800000u)) --f;
+                    int w = f;
+                    for (int j = f; j < ncand; ++j) {
+                        const u64 v = sbuf[j];
+                        const float s = __uint_as_float((uint32_t)(v >> 32));
+                        if (s == s) sbuf[w++] = v;
+                    }
+                    s_count = w;
+                }
+                __syncthreads();
+                ncand = s_count;
+            }
         }
         pool[tid] = tid < ncand && tid < kSelSortCap ? sbuf[tid] : kEmpty;
         __syncthreads();
@@ -1249,11 +1268,13 @@ __global__ __launch_bounds__(256) void two_pass_merge_kernel(const u64* __restri
     }
 }
 
+bool two_pass_merge_args_ok(uint32_t nshards, uint32_t cc, uint32_t k) { return !(cc == 0 || (uint64_t)nshards * cc > 1024 || k > cc); }
+
 hipError_t launch_two_pass_merge(const u64* approx_lists, const u64* exact_lists, uint32_t nshards, uint64_t shard_pitch, uint32_t nq,
                                  uint32_t cc, uint32_t k, uint32_t out_stride, uint32_t* out_rows, float* out_scores, uint32_t* out_counts,
                                  hipStream_t stream) {
     if (nq == 0) return hipSuccess;
-    if (cc == 0 || (uint64_t)nshards * cc > 1024 || k > cc) return hipErrorInvalidValue;
+    if (!two_pass_merge_args_ok(nshards, cc, k)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(two_pass_merge_kernel, dim3(nq), dim3(256), 0, stream, approx_lists, exact_lists, nshards, shard_pitch, nq, cc, k,
                        out_stride, out_rows, out_scores, out_counts);
     return hipGetLastError();
@@ -1418,10 +1439,15 @@ __global__ __launch_bounds__(512) void select_groups_kernel(GroupSelectArgs args
     }
 }
 
-hipError_t launch_select_groups(const GroupSelectArgs& args, int nq, hipStream_t stream) {
-    if (args.k < 1 || args.nentries == 0 || args.nentries > 1024 || !args.delta || !args.tau_out) return hipErrorInvalidValue;
+bool select_groups_args_ok(const GroupSelectArgs& args) {
+    if (args.k < 1 || args.nentries == 0 || args.nentries > 1024 || !args.delta || !args.tau_out) return false;
     if (args.rank_only ? args.k > kGroupsRankMax : (args.k > kGroupsTakenMax || (args.dim & 7) || args.dim > kSelQueryLds || !args.anchor_unit || !args.slab))
-        return hipErrorInvalidValue;
+        return false;
+    return true;
+}
+
+hipError_t launch_select_groups(const GroupSelectArgs& args, int nq, hipStream_t stream) {
+    if (!select_groups_args_ok(args)) return hipErrorInvalidValue;
     constexpr int M0 = (int)kGroupsTaken, M1 = (int)kGroupsTakenMax;
     if (args.rank_only) {
         if (args.k <= 64) hipLaunchKernelGGL((select_groups_kernel<true, M0, 64>), dim3(nq), dim3(512), 0, stream, args);
@@ -1459,15 +1485,28 @@ __global__ __launch_bounds__(256) void list_cut_kernel(const u64* __restrict__ l
     }
 }
 
+bool list_cut_args_ok(uint32_t nlists, uint32_t list_len) {
+    (void)nlists;
+    return list_len != 0;
+}
+
 hipError_t launch_list_cut(const u64* lists, uint32_t nlists, uint32_t list_len, float* out, hipStream_t stream) {
-    if (list_len == 0) return hipErrorInvalidValue;
+    if (!list_cut_args_ok(nlists, list_len)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(list_cut_kernel, dim3(1), dim3(256), 0, stream, lists, nlists, list_len, out);
     return hipGetLastError();
 }
 
+bool select_args_ok(const SelectArgs& args) {
+    if (args.k < 1 || args.k > kSelectMaxK || !args.delta || (uint64_t)args.nlists * args.list_len > 0x7fffffffull) return false;
+    if (args.slab) {
+        if (args.k_out < 1 || args.k_out > 64 || (args.dim & 7)) return false;
+        if (args.slab_f32 && args.row_stride && args.row_stride != args.dim * 4) return false;   // dense f32 rows only (no MRL prefix views of F32 slabs here)
+    }
+    return true;
+}
+
 hipError_t launch_select(const SelectArgs& args, int nq, hipStream_t stream) {
-    if (args.k < 1 || args.k > kSelectMaxK || !args.delta || (uint64_t)args.nlists * args.list_len > 0x7fffffffull)
-        return hipErrorInvalidValue;
+    if (!select_args_ok(args)) return hipErrorInvalidValue;
 #ifdef FSGPU_EXPERIMENTS
     static const int sort_above = [] {
         const char* e = std::getenv("FSGPU_SELECT_SORT_ABOVE");  // tuning experiments only
@@ -1492,9 +1531,7 @@ hipError_t launch_select(const SelectArgs& args, int nq, hipStream_t stream) {
         attr_done = true;
     }
     if (args.slab) {
-        if (args.k_out < 1 || args.k_out > 64 || (args.dim & 7)) return hipErrorInvalidValue;
-        if (args.slab_f32) {   // dense f32 rows only (no MRL prefix views of F32 slabs here)
-            if (args.row_stride && args.row_stride != args.dim * 4) return hipErrorInvalidValue;
+        if (args.slab_f32) {
             if (sorted) hipLaunchKernelGGL((select_kernel<true, true, true>), dim3(nq), dim3(kSelThreads), sort_lds, stream, args);
             else hipLaunchKernelGGL((select_kernel<true, false, true>), dim3(nq), dim3(kSelThreads), 0, stream, args);
             return hipGetLastError();

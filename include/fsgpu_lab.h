@@ -161,6 +161,58 @@ fsgpu_status fsgpu_lab_scan_stage(int32_t device, const fsgpu_lab_scan_stage_arg
 /* The 128-query shape of the LDS-query kernel the batched planner runs when FSGPU_MFMA_SHAPE (elem_bytes 2) or FSGPU_MFMA_SHAPE_I8
  * (elem_bytes 1) asks for `requested` (0: nothing asked): a shape this build does not contain is never chosen. */
 int32_t fsgpu_lab_scan_planner_shape(int32_t requested, int32_t elem_bytes);
+/* ONE selection of the batched search on host arrays, through the launcher the product calls (launch_select, launch_select_groups,
+ * launch_list_cut, launch_two_pass_merge) with a SelectArgs / GroupSelectArgs filled field for field from this struct: for kernel-level
+ * tests against tests/selection_ref.py.  Default stream, fresh device buffers, no kernel of its own.  nq blocks are launched.
+ *   SELECT        lists: nq x q_stride entries (q_stride >= (nlists - 1) l_stride + list_len); list_counts [nq][nlists] or NULL;
+ *                 extra [nq][extra_len]; spill [nq][spill_cap] with spill_count [nq x 16] (the product's counter stride; in: the counts, out:
+ *                 what the launch left).  reset_spill = 1: SelectArgs::spill_reset IS spill_count, as the product always passes it.
+ *                 slab != NULL makes it a finish step (rows of row_stride bytes, 0 = dense; f32 rows with slab_f32); queries holds
+ *                 valid_queries rows (nq when that is 0) of query_stride (0 = dim) floats and is followed on the device by NaN rows, so a
+ *                 padding block that reads its query shows.  pool_flag [nq] (in: initial contents, out: final) or NULL.
+ *                 big_pool 0: one launch (pool_flag as given).  1: the product's two launches over the same lists, the first with
+ *                 big_pool = 0 (it fills pool_flag), the second with big_pool = 1.  2: the second-chance launch alone, on the flags given.
+ *   SELECT_GROUPS lists = groups [nq][nentries]; delta, anchor_unit, tau_out, overflow, spill_count / reset_spill, slab (dense rows),
+ *                 live / allow (ceil(nrows / 64) words or NULL), queries, dim, nrows, row_base, query_stride, hreduce, valid_queries,
+ *                 slab_f32, rank_only as in GroupSelectArgs.
+ *   LIST_CUT      lists [nlists][list_len]; tau_out[0] receives the cut.
+ *   TWO_PASS_MERGE lists = the pass-1 entries, exact_lists = the exact ones: nshards x shard_pitch entries each (shard_pitch >= nq x cc);
+ *                 k, out_stride, out_rows, out_scores, out_counts.
+ * Output areas a launch may write (those given non-NULL) are prefilled with bytes 0xCD, `overflow` with zero, and lie between guard bands
+ * (FSGPU_ERR_DEVICE, "guard band", if one is touched); the slab is followed by guard rows of NaN.  Arguments are checked before a device is
+ * looked for (fsgpu_lab_select_check does only that: FSGPU_OK = it would be launched); what the launchers' own predicates refuse
+ * (select_args_ok, select_groups_args_ok, list_cut_args_ok, two_pass_merge_args_ok of kernels.hpp) is FSGPU_ERR_INVALID_CONFIG with
+ * nothing launched. */
+#define FSGPU_LAB_SELECT 0
+#define FSGPU_LAB_SELECT_GROUPS 1
+#define FSGPU_LAB_LIST_CUT 2
+#define FSGPU_LAB_TWO_PASS_MERGE 3
+typedef struct fsgpu_lab_select_args {
+    uint32_t kernel, nq, valid_queries, k;
+    uint64_t q_stride, shard_pitch;
+    uint32_t l_stride, nlists, list_len, extra_len, spill_cap, reset_spill, take_topk, heur_rank, big_pool;
+    uint32_t dim, nrows, row_base, row_stride, query_stride;
+    int32_t hreduce;
+    uint32_t k_out, out_stride, cand_out_stride, slab_f32, nentries, rank_only, nshards, cc;
+    const uint64_t *lists;
+    const uint32_t *list_counts;
+    const uint64_t *extra, *spill, *exact_lists;
+    const float *delta, *anchor_unit, *tau_floor_in;
+    const void *slab;
+    const uint64_t *live, *allow;
+    const float *queries;
+    uint32_t *spill_count, *pool_flag;
+    float *tau_out, *tau_floor_out;
+    uint64_t *pool_out;
+    uint32_t *cand_counts, *overflow;
+    uint32_t *out_rows;
+    float *out_scores;
+    uint64_t *out_packed;
+    uint32_t *out_counts;
+    uint64_t *cand_approx_out, *cand_exact_out;
+} fsgpu_lab_select_args;
+fsgpu_status fsgpu_lab_select_check(const fsgpu_lab_select_args *args);
+fsgpu_status fsgpu_lab_select(int32_t device, const fsgpu_lab_select_args *args);
 /* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
