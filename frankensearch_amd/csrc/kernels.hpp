@@ -253,6 +253,7 @@ bool scan_wide_supported(int dim, int elem_bytes);
 bool scan_wide_group_maxima_supported(int dim, int query_tiles);   // MfmaScanArgs::stage == 3 (int8 rows): see select_groups
 int scan_wide_max_query_tiles(int dim, int elem_bytes);  // 3 for f16 rows of 384 dimensions, 5 for their int8 form
 hipError_t launch_scan_wide(const MfmaScanArgs& args, int query_tiles, int grid, hipStream_t stream, int* occupancy);
+bool scan_wide_flat_priority();   // FSGPU_WIDE_PRIO=off (knobs(), vector_index_batched.cpp): launch_scan_wide's split loop without priority levels
 void note_main_pass_kernel(const char* name);  // remembers the instantiation the last main pass ran (last_main_pass_kernel)
 const char* last_main_pass_kernel();  // template instantiation of the last batched main pass launched, as rocprofv3 names it
 // shape: see mfma_scan.hip (0 = 64 queries; 1..3 = 128 queries with different row tiling / buffering)

@@ -169,7 +169,19 @@ __device__ __forceinline__ void wait_vmcnt() {
 //              waves therefore drift up to about a tile apart instead of meeting at every tile: a wave held up in the append path
 //              (a scalar bitmap load, an LDS atomic, a store — ~5 events per tile at 10M rows, ~40 on a 1.25M-row shard) no longer
 //              stops the other seven, and the two waves of a SIMD no longer stop together.
-constexpr int kOptNegTau = 2, kOptSaddr = 4, kOptSplit = 8, kOptBig = 16, kOptFlags = 32;
+//   kOptFlat   (with kOptSplit) the split loop WITHOUT its progress-ordered wave priority.  By default a wave of the split loop lowers
+//              its own priority (s_setprio) as it advances through a tile: level 3 at the tile's first sub-tile pair — where the
+//              tile's barrier stands — falling to 0 at its last.  Of a SIMD's two waves the one that is BEHIND then has the higher or
+//              equal priority, whatever their age: under the oldest-first arbiter alone the older wave took the matrix pipe whenever
+//              both were ready, finished the tile early and parked at the barrier while its twin finished alone.  The levels are
+//              compile-time constants of the unrolled loop (no state, no communication); the append excursion runs at level 3 (a wave
+//              in it is the laggard by definition) and restores its place's level.  FSGPU_WIDE_PRIO=off launches these instantiations.
+constexpr int kOptNegTau = 2, kOptSaddr = 4, kOptSplit = 8, kOptBig = 16, kOptFlags = 32, kOptFlat = 64;
+
+// The priority level of half-phase h of H (a tile's sub-tile pairs x the two query-tile halves of each): four levels spread evenly
+// over the tile — one per pair of a 128-row tile, one per half-phase of a 64-row tile.  (Measured against it on the bench shape,
+// profiles/wide_level/level_ab.txt: the levels changing half a pair later, and two levels split at the tile's midpoint — both slower.)
+constexpr int wide_level(int h, int H) { return 3 - (h * 4) / H; }
 
 // k-steps per chunk of the chunk loop (fewer where the resident queries leave fewer registers for the fragment double buffer)
 constexpr int wide_chunk_ksteps(int KS, int QT) {
@@ -190,6 +202,8 @@ constexpr bool wide_split_ok(int ROWB, int EB, int QT, int OPT, int DBG) {
 constexpr bool wide_big_ok(int ROWB, int EB, int QT, int NSLOT, int OPT, int DBG) {
     return (OPT & kOptBig) != 0 && wide_split_ok(ROWB, EB, QT, OPT, DBG) && (DBG == 0 || DBG == 8 || DBG >= 16) && NSLOT == 3;
 }   // (bit 1 was a barrier-phase shift between the SIMD twins: measured null, removed)
+// (the group-maxima sample in this form — a 128-row slot holding two of the block's 64-row groups — was built and measured: 131.1 against
+// 132.9 us per launch with the groups one after the other, 120.0 against 119.6 side by side; profiles/wide_level/level_ab.txt: left out)
 // one 64-bit word through the scalar cache (wave-uniform address): counted by lgkmcnt, not by the vmcnt the DMA ring lives on
 __device__ __forceinline__ u64 sload_u64(const u64* pv) {
     const u64* p = reinterpret_cast<const u64*>((uintptr_t)uniform_u64((uint64_t)(uintptr_t)pv));
@@ -282,6 +296,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     constexpr bool NEGTAU = (OPT & kOptNegTau) != 0 && EB == 1 && ROOM;
     constexpr bool SADDR = (OPT & kOptSaddr) != 0 && ROOM;
     constexpr bool SPLIT = wide_split_ok(ROWB, EB, QT, OPT, DBG);
+    constexpr bool LEVEL = SPLIT && (OPT & kOptFlat) == 0;          // progress-ordered wave priority (kOptFlat)
     // Timing skeletons of the split loop (experiments builds, scripts/r04/skeletons.sh; their answers are not valid).  DBG in [16, 32):
     // a bit set on 16 — 1 no DMA, 2 no per-tile wait + barrier, 4 no fragment reads in the loop, 8 no threshold tests; the append path
     // is one LDS store.  DBG >= 32: everything real but the append path, a bit set on 32 — 1 no global store, 2 no LDS counter (slot 0),
@@ -537,7 +552,20 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     // addresses per lane, which spilled: every entry paid a scratch reload + s_waitcnt vmcnt(0), i.e. a drain of the DMA ring the
     // loop never drains — 1,600 cycles per entry, profiles/r04/wide_stamps.txt), the entry leaves through a store that nobody waits
     // for, and only a list that overflows its slots (rare: the spill area) touches a returning global atomic.
-    auto emit_tiles = [&](uint32_t t, int sp, const acc_t (&acc)[2][QT], int nt_lo, int nt_hi) {
+    // LEVEL: the wave's priority level.  s_setprio takes an immediate: `level` is a constant wherever the unrolled loop calls this, and
+    // the switch folds to the one instruction.
+    auto set_level = [&](int level) __attribute__((always_inline)) {
+        if constexpr (LEVEL) {
+            switch (level) {
+                case 0: __builtin_amdgcn_s_setprio(0); break;
+                case 1: __builtin_amdgcn_s_setprio(1); break;
+                case 2: __builtin_amdgcn_s_setprio(2); break;
+                default: __builtin_amdgcn_s_setprio(3); break;
+            }
+        }
+    };
+    // (LEVEL: `back` is the priority level of the place the excursion returns to)
+    auto emit_tiles = [&](uint32_t t, int sp, const acc_t (&acc)[2][QT], int nt_lo, int nt_hi, int back) {
 #ifdef FSGPU_EXPERIMENTS
         if constexpr (DBG == 2 || DBG == 4 || DBG == 5 || SK) {  // (timing skeletons read stale bytes: keep the scores live, append nothing)
             lcnt[q0 + frow] = 0;
@@ -547,11 +575,16 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
         if (t >= ntiles) return;   // (wave-uniform) a ragged round: the slot holds the last tile again
         [[maybe_unused]] unsigned long long st_in = 0;
         if constexpr (STAMPS) st_in = __builtin_readcyclecounter();
+        if constexpr (LEVEL) {
+            set_level(3);   // the wave in the excursion is the one behind
+        } else {
 #ifdef FSGPU_LAB_APPEND_PRIO
-        // (lab) the partner wave of this SIMD keeps issuing matrix instructions; at equal priority the OLDER wave's vector instructions
-        // go first and an excursion on the younger one crawls (MI355X_MICROARCH.md, "Two waves per SIMD", item 2)
-        __builtin_amdgcn_s_setprio(FSGPU_LAB_APPEND_PRIO);
+            // (lab, loops without the progress-ordered levels) the partner wave of this SIMD keeps issuing matrix instructions; at equal
+            // priority the OLDER wave's vector instructions go first and an excursion on the younger one crawls (MI355X_MICROARCH.md,
+            // "Two waves per SIMD", item 2)
+            __builtin_amdgcn_s_setprio(FSGPU_LAB_APPEND_PRIO);
 #endif
+        }
         // C layout: column (query) = lane & 15, row = (lane >> 4) * 4 + reg
         const uint32_t pair_row0 = __builtin_amdgcn_readfirstlane(tile_row0(t) + sp * 16);   // a multiple of 32: the pair's 32 rows share one bitmap word
         // the pair's 32 rows: bit i set = row pair_row0 + i exists, is live and allowed (scalar arithmetic)
@@ -639,9 +672,13 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                     }
             }
         }
+        if constexpr (LEVEL) {
+            set_level(back);
+        } else {
 #ifdef FSGPU_LAB_APPEND_PRIO
-        __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
 #endif
+        }
         if constexpr (STAMPS) {
             const unsigned long long dt = __builtin_readcyclecounter() - st_in;
             if (lane == 0) {
@@ -656,7 +693,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     // with the hint the loop is ~480 contiguous instructions that fall through and the append code sits behind the function's end)
     auto emit_pair = [&](uint32_t t, int sp, const acc_t (&acc)[2][QT]) {
         // one test for the whole pair; almost always negative: survivors are a few hundred rows of the slab
-        if (__builtin_expect(wave_any(any_passes(acc, 0, QT)), 0)) emit_tiles(t, sp, acc, 0, QT);
+        if (__builtin_expect(wave_any(any_passes(acc, 0, QT)), 0)) emit_tiles(t, sp, acc, 0, QT, 0);
     };
 
     // The append path reads the tombstone / allow words with SCALAR loads (sload_u64).  The scalar data cache is not invalidated
@@ -804,6 +841,10 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 constexpr int TK = KS >= 4 ? 2 : 0;   // the k-step after which a phase carries the other half's test
+                // the wave's priority falls as it advances through the tile (kOptFlat): one s_setprio where the level changes
+                constexpr int H = 2 * NP;
+                const int lv1 = wide_level(2 * p, H), lv2 = wide_level(2 * p + 1, H);
+                if (lv1 != wide_level((2 * p + H - 1) % H, H)) set_level(lv1);
                 // ---- phase 1: query tiles [0, QA); the previous pair's tiles [QA, QT) are tested in its shadow
                 init_acc(0, QA);
                 bool anyB = false;
@@ -846,7 +887,8 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (__builtin_expect(wave_any(anyB), 0)) emit_tiles(tB, ((p + NP - 1) % NP) * 2, acc, QA, QT);
+                if (__builtin_expect(wave_any(anyB), 0)) emit_tiles(tB, ((p + NP - 1) % NP) * 2, acc, QA, QT, lv1);
+                if (lv2 != lv1) set_level(lv2);
                 // ---- phase 2: query tiles [QA, QT); the next pair's fragments roll in behind each k-step; this pair's tiles
                 // [0, QA) are tested in its shadow
                 init_acc(QA, QT);
@@ -869,7 +911,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                 if constexpr (FLAGS) {   // this wave's last read of the tile is out (the last pair's fragments): its slot may be refilled
                     if (p + 2 == NP) flag_post(flags + 16 + slot * 4, lane);
                 }
-                if (__builtin_expect(wave_any(anyA), 0)) emit_tiles(t, p * 2, acc, 0, QA);
+                if (__builtin_expect(wave_any(anyA), 0)) emit_tiles(t, p * 2, acc, 0, QA, lv2);
                 tB = t;
             }
             cursor_next(cc);
@@ -889,7 +931,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
             __syncthreads();   // (no DMA may outlive the block's LDS allocation: every wave has waited for its own above)
             return;
         } else {
-            if (__builtin_expect(wave_any(any_passes(acc, QA, QT)), 0)) emit_tiles(tB, (NP - 1) * 2, acc, QA, QT);
+            if (__builtin_expect(wave_any(any_passes(acc, QA, QT)), 0)) emit_tiles(tB, (NP - 1) * 2, acc, QA, QT, 0);
         }
     } else {
     half8 fa[2][2][CK];   // fragment double buffer: [buffer][sub-tile of the pair][k-step of the chunk]
@@ -1017,7 +1059,7 @@ int wide_env(const char* name) {
 #endif
 
 template <int ROWB, int EB, int QT, int NSLOT, int OPT, int DBG = 0>
-hipError_t launch_wide_t(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
+hipError_t launch_wide_k(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
     constexpr bool BIG = wide_big_ok(ROWB, EB, QT, NSLOT, OPT, DBG);
     constexpr int TR = BIG ? 128 : ROWB >= 512 ? 32 : 64;
     constexpr size_t ring = (size_t)NSLOT * TR * ROWB;
@@ -1041,6 +1083,12 @@ hipError_t launch_wide_t(const MfmaScanArgs& args, int grid, hipStream_t stream,
     if (DBG != 3 && DBG != 7) note_main_pass_kernel(name.c_str());
     hipLaunchKernelGGL(kern, dim3(grid, args.groups ? args.groups : 1), dim3(512), lds, stream, args);
     return hipGetLastError();
+}
+
+// (kOptFlat names a kernel of its own only where the split loop runs: everything else has no priority levels to leave out)
+template <int ROWB, int EB, int QT, int NSLOT, int OPT, int DBG = 0>
+hipError_t launch_wide_t(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
+    return launch_wide_k<ROWB, EB, QT, NSLOT, wide_split_ok(ROWB, EB, QT, OPT, DBG) ? OPT : (OPT & ~kOptFlat), DBG>(args, grid, stream, occupancy);
 }
 
 #ifdef FSGPU_LAB_ASYM
@@ -1069,12 +1117,11 @@ hipError_t launch_wide_pick(const MfmaScanArgs& args, int grid, hipStream_t stre
     else return launch_wide_t<ROWB, EB, QT, NSLOT, O & ~(kOptBig | kOptFlags), MODE>(args, grid, stream, occupancy);
 }
 
-template <int EB, int QT, int MODE = 0>
-hipError_t launch_wide_d(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
+template <int EB, int QT, int MODE, int O>
+hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
     // resident query fragments: QT x (row bytes / 64) x 4 registers per lane; 144 is what fits next to the accumulators and
     // the fragment double buffer (f16 rows of 768 bytes: 3 tiles; int8 rows of 384 bytes: 6)
     if (QT * (int)(args.dim * EB / 64) * 4 > 144) return hipErrorInvalidValue;
-    constexpr int O = kWideOptDefault;
     switch (args.dim * EB / 2) {  // row length in 2-byte units
         case 384: if constexpr (QT <= 3 && MODE != 7) {
 #ifdef FSGPU_EXPERIMENTS
@@ -1167,6 +1214,13 @@ hipError_t launch_wide_d(const MfmaScanArgs& args, int grid, hipStream_t stream,
                   else return launch_wide_pick<256, EB, QT, 8, O, MODE>(args, grid, stream, occupancy);   // 8 x 16 KB (3 x 32 KB)
         default: return hipErrorInvalidValue;
     }
+}
+
+// FSGPU_WIDE_PRIO=off: the split-loop kernels without their progress-ordered wave priority (kOptFlat), for timing both from one build
+template <int EB, int QT, int MODE = 0>
+hipError_t launch_wide_d(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
+    if (scan_wide_flat_priority()) return launch_wide_o<EB, QT, MODE, kWideOptDefault | kOptFlat>(args, grid, stream, occupancy);
+    return launch_wide_o<EB, QT, MODE, kWideOptDefault>(args, grid, stream, occupancy);
 }
 
 }  // namespace

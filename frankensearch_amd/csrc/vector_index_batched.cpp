@@ -20,6 +20,8 @@ namespace fsgpu {
 
 using namespace detail;
 
+bool scan_wide_flat_priority() { return knobs().wide_flat_priority; }
+
 // Batched search on the matrix cores; see mfma_scan.hip for the error bound that makes the result exact.
 SearchError VectorIndex::search_top_k_batched_device(const float* queries_dev, uint32_t nq, uint32_t query_len,
                                                      uint32_t k, const uint64_t* allow_dev, uint32_t* out_rows_dev,
@@ -797,22 +799,34 @@ SearchError VectorIndex::batched_sample(const BatchedPlan& p, BatchedRound& r) {
     const bool group_sample = (r.anchor ? ksel <= kGroupsTakenMax : rank_groups) && r.wide_qt != 0 && !skip_b && !knobs().no_wide_b &&
                               !knobs().no_group_sample && (dim_ & 7) == 0 && dim_ <= 1024 && scan_wide_group_maxima_supported((int)dim_, r.wide_qt);
     if (group_sample) {
-        const int grid_g = std::min(r.wide_grid, (int)std::max<uint32_t>(1, RB / 64 / 4));   // at least 4 sample groups per block
+        int grid_g = std::min(r.wide_grid, (int)std::max<uint32_t>(1, RB / 64 / 4));   // at least 4 sample groups per block
         // (enough groups for the picks: the rank form needs ksel of them — and not all from a wave or two of the selection)
         // (the ranks round 6 added — above 24 with an anchor, above 64 by rank — only with the FULL 1,024-entry sample of a large slab: on a
         // 43k-row slab the 30th best of 160 group maxima is so loose a threshold that 40 % of a batch overflowed its lists and was
         // re-filtered on the f16 slab — results right, time wrong; scripts/fuzz_sharded.py found it through a second bug, see
         // search_top_k_batched_device_end's late_answers)
-        const uint32_t entries = (uint32_t)grid_g * 4;
         const bool extended = r.anchor ? ksel > kGroupsTaken : ksel > 64;
-        if (grid_g * 4 <= 1024 && entries >= (r.anchor ? 96u : 4u * std::min(ksel, 64u)) && (!extended || entries >= 1024)) {
+        const uint32_t entries_min = r.anchor ? 96u : 4u * std::min(ksel, 64u);
+        // Several 512-query groups in the launch run SIDE BY SIDE like the main pass's (batched_main): every group on
+        // grid / groups walkers, all blocks resident, walker w of every group on the same sample groups at the same time — one read of
+        // the sample and one ramp per launch, and walkers x 4 entries per query for the selection instead of grid x 4.  Under the same
+        // conditions (walkers a multiple of 8, at least four sample groups per walker, FSGPU_WIDE_LAYOUT), and only where the fewer
+        // entries still are what the ranks need: never for the extended ranks, which take the full 1,024.
+        const uint32_t sample_groups = r.ngroups / r.wide_mult;
+        const uint32_t walkers = sample_groups > 1 && (uint32_t)grid_g % sample_groups == 0 ? (uint32_t)grid_g / sample_groups : 0;
+        const bool side_by_side = walkers != 0 && walkers % 8 == 0 && groups_b >= walkers * 4 && !knobs().wide_sequential && !extended &&
+                                  grid_g * 4 <= 1024 && walkers * 4 >= entries_min;
+        if (side_by_side) grid_g = (int)walkers;
+        const uint32_t entries = (uint32_t)grid_g * 4;
+        if (grid_g * 4 <= 1024 && entries >= entries_min && (!extended || entries >= 1024)) {
             MfmaScanArgs c = a;
             c.dense = nullptr;
             c.stage = 3;
             c.group_stride = stride_b;
             c.group_count = groups_b;
             c.slots = 4;
-            c.groups = r.ngroups / r.wide_mult;
+            c.groups = sample_groups;
+            c.side_by_side = side_by_side;
             c.queries = mf_qh_.ptr;
             c.tau = p.tau;
             c.cand = r.cand;
