@@ -88,6 +88,12 @@ SIGNATURES = {
     "fsgpu_allow_bitmap_allowed_rows": (_u64, [_vp]),
     "fsgpu_search_topk_filtered": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "fsgpu_search_topk_batched_filtered": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_search_topk_batched_multi_filtered": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_search_topk_batched_multi_filtered_device_queries": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp,
+                                                                        C.POINTER(_u32)]),
+    "fsgpu_allow_bitmap_rows": (_i32, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "fsgpu_index_multi_filter_stats": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "fsgpu_lab_multi_filter_plan": (_i32, [_u64, _vp, _u32, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "fsgpu_search_topk_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "fsgpu_search_topk_batched": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "fsgpu_search_topk_batched_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),

@@ -70,6 +70,11 @@ struct fsgpu_allow_bitmap {   // a precomputed SearchFilter resident on an index
     uint64_t generation = 0;       // the index's slab generation it was made for: row ids do not survive compact / vacuum
     std::vector<uint64_t> words;   // host copy: the selectivity rule (1/50) and the coalescer's batch key
     fsgpu::DeviceBuffer dev;
+    // the ascending row ids of the set bits, built on the device at first use (fsgpu_search_topk_batched_multi_filtered's
+    // selective groups, fsgpu_allow_bitmap_rows) and kept: the handle pins device, record count and generation
+    mutable std::mutex rows_mu;
+    mutable fsgpu::DeviceBuffer rows;
+    mutable bool rows_ready = false;
 };
 struct fsgpu_sharded {
     fsgpu::ShardedIndex impl;
@@ -589,6 +594,7 @@ void fsgpu_allow_bitmap_destroy(fsgpu_allow_bitmap* f) {
     if (!f) return;
     if (f->device >= 0) (void)hipSetDevice(f->device);
     f->dev.release();
+    f->rows.release();
     delete f;
 }
 
@@ -621,6 +627,120 @@ fsgpu_status fsgpu_search_topk_batched_filtered(fsgpu_index* idx, const float* q
         std::lock_guard<std::mutex> lock(idx->impl.mutex());
         return finish(idx->impl.search_top_k_batched(queries, nq, query_len, k, filter->words.data(), out_rows, out_scores, out_counts,
                                                      out_fallbacks, static_cast<const uint64_t*>(filter->dev.ptr)));
+    });
+}
+
+// ---- a filter per query (vector_index_filtered.cpp) ----
+// the handle's row list, built on first use
+static fsgpu_status ensure_filter_rows(const fsgpu_allow_bitmap* f) {
+    std::lock_guard<std::mutex> lock(f->rows_mu);
+    if (f->rows_ready) return FSGPU_OK;
+    const fsgpu::SearchError e = fsgpu::build_filter_row_list(f->device, static_cast<const uint64_t*>(f->dev.ptr), f->nrows, f->allowed, &f->rows);
+    if (!e.ok()) return finish(e);
+    f->rows_ready = true;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_allow_bitmap_rows(const fsgpu_allow_bitmap* filter, uint32_t* out_rows, uint64_t cap, uint64_t* out_n) {
+    if (!filter || !out_n || (cap && !out_rows)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        *out_n = filter->allowed;
+        const fsgpu_status c = ensure_filter_rows(filter);
+        if (c != FSGPU_OK) return c;
+        const uint64_t n = std::min<uint64_t>(cap, filter->allowed);
+        if (n == 0) return FSGPU_OK;
+        if (hipSetDevice(filter->device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        if (hipMemcpy(out_rows, filter->rows.ptr, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(FSGPU_ERR_DEVICE, "download of the row list failed");
+        return FSGPU_OK;
+    });
+}
+
+// Everything that can be refused is refused here, before anything is launched; the views of the filters for the index.
+static fsgpu_status multi_filter_views(const fsgpu_index* idx, uint32_t nq, uint32_t query_len, const fsgpu_allow_bitmap* const* filters,
+                                       uint32_t nfilters, const int32_t* filter_of_query, std::vector<fsgpu::ResidentFilterView>* views) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    if ((nfilters && !filters) || (nq && !filter_of_query)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (query_len != idx->impl.dimension())
+        return fail(FSGPU_ERR_DIMENSION_MISMATCH, ("expected " + std::to_string(idx->impl.dimension()) + ", found " + std::to_string(query_len)).c_str());
+    for (uint32_t f = 0; f < nfilters; ++f) {
+        const fsgpu_status c = check_filter(idx, filters[f]);
+        if (c != FSGPU_OK) return c;
+    }
+    const fsgpu::SearchError e = fsgpu::multi_filter_plan(idx->impl.record_count(), nullptr, nfilters, filter_of_query, nq, nullptr, nullptr,
+                                                          nullptr, nullptr);
+    if (!e.ok()) return finish(e);
+    std::vector<uint8_t> named(nfilters, 0);
+    for (uint32_t q = 0; q < nq; ++q)
+        if (filter_of_query[q] >= 0) named[filter_of_query[q]] = 1;
+    views->resize(nfilters);
+    const uint64_t nrows = idx->impl.record_count();
+    for (uint32_t f = 0; f < nfilters; ++f) {
+        fsgpu::ResidentFilterView& v = (*views)[f];
+        v.words_host = filters[f]->words.data();
+        v.words_dev = static_cast<const uint64_t*>(filters[f]->dev.ptr);
+        v.allowed = filters[f]->allowed;
+        // a selective filter some query names: its row list (first use builds it, on the device)
+        if (named[f] && v.allowed && (unsigned __int128)v.allowed * 50u < (unsigned __int128)nrows) {
+            const fsgpu_status c = ensure_filter_rows(filters[f]);
+            if (c != FSGPU_OK) return c;
+            v.rows_dev = static_cast<const uint32_t*>(filters[f]->rows.ptr);
+        }
+    }
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_search_topk_batched_multi_filtered(fsgpu_index* idx, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                                      const fsgpu_allow_bitmap* const* filters, uint32_t nfilters,
+                                                      const int32_t* filter_of_query, uint32_t* out_rows, float* out_scores,
+                                                      uint32_t* out_counts, uint32_t* out_fallbacks) {
+    if (out_fallbacks) *out_fallbacks = 0;
+    if (idx && nq && (!queries || !out_counts || (k && (!out_rows || !out_scores)))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::vector<fsgpu::ResidentFilterView> views;
+        const fsgpu_status c = multi_filter_views(idx, nq, query_len, filters, nfilters, filter_of_query, &views);
+        if (c != FSGPU_OK) return c;
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.search_top_k_multi_filtered_host(queries, nq, query_len, k, views.data(), nfilters, filter_of_query, out_rows,
+                                                                 out_scores, out_counts, out_fallbacks));
+    });
+}
+
+fsgpu_status fsgpu_search_topk_batched_multi_filtered_device_queries(fsgpu_index* idx, const float* queries_dev, uint32_t nq, uint32_t query_len,
+                                                                     uint32_t k, const fsgpu_allow_bitmap* const* filters, uint32_t nfilters,
+                                                                     const int32_t* filter_of_query, uint32_t* out_rows_dev,
+                                                                     float* out_scores_dev, uint32_t* out_counts_dev, void* hip_stream,
+                                                                     uint32_t* out_fallbacks) {
+    if (out_fallbacks) *out_fallbacks = 0;
+    if (idx && nq && (!queries_dev || !out_counts_dev || (k && (!out_rows_dev || !out_scores_dev))))
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::vector<fsgpu::ResidentFilterView> views;
+        const fsgpu_status c = multi_filter_views(idx, nq, query_len, filters, nfilters, filter_of_query, &views);
+        if (c != FSGPU_OK) return c;
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.search_top_k_multi_filtered(queries_dev, nq, query_len, k, views.data(), nfilters, filter_of_query, out_rows_dev,
+                                                            out_scores_dev, out_counts_dev, static_cast<hipStream_t>(hip_stream), out_fallbacks));
+    });
+}
+
+fsgpu_status fsgpu_index_multi_filter_stats(fsgpu_index* idx, uint64_t* gathered, uint64_t* scanned, uint64_t* unfiltered, uint64_t* fallbacks) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    std::lock_guard<std::mutex> lock(idx->impl.mutex());
+    if (gathered) *gathered = idx->impl.multi_gathered;
+    if (scanned) *scanned = idx->impl.multi_scanned;
+    if (unfiltered) *unfiltered = idx->impl.multi_unfiltered;
+    if (fallbacks) *fallbacks = idx->impl.multi_fallbacks;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_lab_multi_filter_plan(uint64_t nrows, const uint64_t* allowed_per_filter, uint32_t nfilters, const int32_t* filter_of_query,
+                                         uint32_t nq, int32_t* out_group_of_query, int32_t* out_path_of_group, uint32_t* out_ngroups) {
+    if ((nfilters && !allowed_per_filter) || (nq && (!filter_of_query || !out_group_of_query || !out_path_of_group)) || !out_ngroups)
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        return finish(fsgpu::multi_filter_plan(nrows, allowed_per_filter, nfilters, filter_of_query, nq, out_group_of_query, out_path_of_group,
+                                               nullptr, out_ngroups));
     });
 }
 

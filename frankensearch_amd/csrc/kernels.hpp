@@ -613,4 +613,38 @@ struct PermuteArgs {
 };
 hipError_t launch_build_permute(const PermuteArgs& args, hipStream_t stream);
 
+// filter_gather_kernels.hip: a filter per query in one batched call (vector_index_filtered.cpp)
+// The ascending local row ids of the set bits of an allow bitmap (bits past nrows ignored), built on the device: popcount per word,
+// exclusive scan, expand.  scratch: filter_row_list_scratch_bytes(nrows); out_rows holds cap entries (the bitmap's popcount);
+// *out_total (device) = the rows written.
+constexpr uint32_t kRowListWordsPerBlock = 1024;
+size_t filter_row_list_scratch_bytes(uint32_t nrows);
+hipError_t launch_filter_row_list(const u64* words_dev, uint32_t nrows, uint32_t cap, uint32_t* scratch, uint32_t* out_rows,
+                                  uint32_t* out_total, hipStream_t stream);
+// The segmented gather scan: group g = the queries [q0, q0 + nq) of args.queries that share one selective filter, whose row list is
+// rows[0 .. n).  One launch, grid (grid_x, groups): nblocks <= grid_x blocks of a group walk its 64-row tiles; every (query, block
+// < grid_x) owns one best-first list of k packed entries in partial — [query slot][grid_x][list_stride], kEmpty padded — for
+// merge_topk_kernel.
+constexpr uint32_t kGatherTileRows = 64;
+constexpr uint32_t kGatherMaxK = 256;
+constexpr size_t kGatherLdsBudget = 160 * 1024;
+struct FilterGatherGroup {
+    const uint32_t* rows;   // ascending local row ids (device)
+    uint32_t n;             // rows in the list
+    uint32_t q0, nq;        // the group's query slots
+    uint32_t nblocks;       // blocks that share the group's tiles
+};
+struct FilterGatherArgs {
+    const void* slab;                  // [nrows, dim] f16, rows row_stride bytes apart
+    const u64* live;                   // bit r set = row r live; nullptr = all live.  Tested when a row is staged.
+    const float* queries;              // [slots, dim] f32, in group order
+    const FilterGatherGroup* groups;   // [gridDim.y] (device)
+    u64* partial;                      // [slots, grid_x, list_stride]: the first k entries of a list are its result
+    uint32_t list_stride;              // >= k, and >= 64 for k <= 64 (between tiles a block parks one entry per lane there)
+    uint32_t nrows, dim, k, row_base, row_stride;
+    int32_t hreduce;
+};
+bool filter_gather_supported(uint32_t dim, uint32_t k);   // dim % 8 == 0, k <= kGatherMaxK, a tile of this dimension fits the LDS
+hipError_t launch_filter_gather_scan(const FilterGatherArgs& args, uint32_t ngroups, uint32_t grid_x, hipStream_t stream);
+
 }  // namespace fsgpu

@@ -69,7 +69,8 @@ VectorIndex::~VectorIndex() {
                             &i8_slab_, &n4_slab_, &i8_max_, &ws_i8_query_, &ws_cand_packed_, &ws_cand_rows_, &ws_cand_scores_,
                             &mf_max_norm_, &mf_qh_, &mf_delta_, &mf_tau_, &mf_cand_, &mf_dense_, &mf_sel_,
                             &mf_fallback_, &mf_fallback2_, &mf_spill_, &mf_io_, &mf_io2_, &ws_out_, &hits_main_class_, &hits_wal_, &hits_wal_class_, &hits_shadow_, &ws_hits_, &i8_stats_, &n4u_slab_, &mf_cand_count_, &ws_pairs_,
-                            &i8f_slab_, &i8f_max_, &i8f_stats_, &rot_mat_, &rot_q_, &ws_mmr_in_, &ws_mmr_out_, &ws_mmr_sims_, &ws_mmr_vec_, &ws_hub_q_, &ws_hub_out_, &ws_hub_topk_, &ws_knn_[0], &ws_knn_[1]})
+                            &i8f_slab_, &i8f_max_, &i8f_stats_, &rot_mat_, &rot_q_, &ws_mmr_in_, &ws_mmr_out_, &ws_mmr_sims_, &ws_mmr_vec_, &ws_hub_q_, &ws_hub_out_, &ws_hub_topk_, &ws_knn_[0], &ws_knn_[1],
+                            &ws_multi_, &ws_multi_lists_, &ws_multi_io_})
         b->release();
     if (mf_flags_host_) (void)hipHostFree(mf_flags_host_);
     if (io_host_) (void)hipHostFree(io_host_);

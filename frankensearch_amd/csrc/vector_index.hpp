@@ -37,6 +37,25 @@ SearchError write_fsvi_v1(const char* path, const char* embedder_id, const char*
                           const char* const* doc_ids, const uint32_t* doc_id_lens, const float* vectors,
                           uint8_t compaction_gen, int device, uint8_t quantization = 1);
 
+// ---- a filter per query (vector_index_filtered.cpp) --------------------------------------------------------------------
+// What the index needs of a resident filter (fsgpu_allow_bitmap): its words on the device, its popcount and the ascending row list
+// the device built from the words (build_filter_row_list, cached on the handle).
+struct ResidentFilterView {
+    const uint64_t* words_host = nullptr;
+    const uint64_t* words_dev = nullptr;
+    uint64_t allowed = 0;
+    const uint32_t* rows_dev = nullptr;   // [allowed] local row ids, ascending; may be null while allowed * 50 >= record count
+};
+// The row list of a bitmap over nrows rows with `allowed` set bits, built on `device` (filter_gather_kernels.hip) into *rows; blocks.
+SearchError build_filter_row_list(int device, const uint64_t* words_dev, uint64_t nrows, uint64_t allowed, DeviceBuffer* rows);
+// Grouping and path decision of a call, host code only.  Groups are numbered in the order their first query appears; a group's
+// queries keep ascending query order; filter -1 (no filter) is a group like any other; a filter no query names forms no group.
+//   path: unfiltered | dense (allowed * 50 >= nrows: masked batched scan) | gather (0 < allowed * 50 < nrows) | empty (allowed == 0)
+enum MultiFilterPath : int32_t { kMultiUnfiltered = 0, kMultiDense = 1, kMultiGather = 2, kMultiEmpty = 3 };
+SearchError multi_filter_plan(uint64_t nrows, const uint64_t* allowed_per_filter, uint32_t nfilters, const int32_t* filter_of_query,
+                              uint32_t nq, int32_t* out_group_of_query, int32_t* out_path_of_group, int32_t* out_filter_of_group,
+                              uint32_t* out_ngroups);
+
 class VectorIndex {
   public:
     VectorIndex();
@@ -104,6 +123,23 @@ class VectorIndex {
                                      const uint64_t* allow, uint32_t* out_rows, float* out_scores, uint32_t* out_counts,
                                      uint32_t* fallbacks, const uint64_t* allow_resident_dev = nullptr,
                                      bool queries_on_device = false);   // queries: a device pointer (an encoder's device output)
+    // Batched row-level search in which query q names filters[filter_of_query[q]], or none (-1): per query the rows, score bits and
+    // count of search_top_k with that filter's bitmap.  Queries are grouped by filter; unfiltered and dense groups ride
+    // search_top_k_batched_device, the selective groups share ONE launch of the segmented gather scan (filter_gather_kernels.hip),
+    // an empty filter costs no launch.  Selective groups of a shape the gather scan does not cover (F32 slab, MRL view, dim % 8,
+    // k > 256) are answered per query by search_top_k and counted in *fallbacks, together with the batched groups' own fallbacks.
+    // Device pointers (queries, outputs) on `stream`, which is synchronised; filter_of_query is a host array.  The filters were
+    // checked against this index by the caller; a selective filter's rows_dev must be set.
+    SearchError search_top_k_multi_filtered(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
+                                            const ResidentFilterView* filters, uint32_t nfilters, const int32_t* filter_of_query,
+                                            uint32_t* out_rows_dev, float* out_scores_dev, uint32_t* out_counts_dev, hipStream_t stream,
+                                            uint32_t* fallbacks);
+    // ... with host pointers (synchronous)
+    SearchError search_top_k_multi_filtered_host(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                                 const ResidentFilterView* filters, uint32_t nfilters, const int32_t* filter_of_query,
+                                                 uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* fallbacks);
+    // queries of search_top_k_multi_filtered by path: gather scan, dense-group pass, unfiltered, per-query fallback
+    uint64_t multi_gathered = 0, multi_scanned = 0, multi_unfiltered = 0, multi_fallbacks = 0;
     // Batched search_top_k_int8_two_pass (search.rs:514-661): int8 pass 1 on the matrix cores (exact integer scores, so the
     // k*multiplier candidates are exactly the reference's), exact f16 rescore, top-k.  No doc-id dedup (raw row ids).
     SearchError search_top_k_int8_batched_device(const float* queries_dev, uint32_t nq, uint32_t query_len, uint32_t k,
@@ -438,6 +474,10 @@ class VectorIndex {
         ws_cand_rows_, ws_cand_scores_, mf_max_norm_, mf_qh_, mf_delta_, mf_tau_, mf_cand_, mf_dense_, mf_sel_,
         mf_fallback_, mf_fallback2_, mf_spill_, mf_io_, mf_io2_, i8_stats_, n4u_slab_, mf_cand_count_, ws_pairs_;
     DeviceBuffer ws_out_;   // rows | scores | counts of a blocking batched search (one block: one copy up)
+    // search_top_k_multi_filtered: index | descriptors | grouped queries | grouped hits; the (query, block) lists; the host form's
+    // queries and outputs; the host image of the first block's head (alive until the call has synchronised)
+    DeviceBuffer ws_multi_, ws_multi_lists_, ws_multi_io_;
+    std::vector<unsigned char> multi_host_;
     DeviceBuffer ws_mmr_in_, ws_mmr_out_, ws_mmr_sims_, ws_mmr_vec_;   // mmr_rerank_rows: inputs (one copy down), order | counts, matrix, staged rows
     DeviceBuffer ws_hub_q_, ws_hub_out_, ws_hub_topk_;   // compute_query_hubness: the sample, the table, the selected sims (lab)
     DeviceBuffer ws_knn_[2];   // build_knn_graph: per step in flight  queries | sources | hit rows | hit scores | counts | out rows | out sims

@@ -7,6 +7,7 @@
 //   vector_index_compact.cpp  append_batch, compact, vacuum: the plan, the device rewrite of the slab, the tables, the FSVI image
 //   vector_index_lone.cpp     one query at a time: the certified int8 pass, the exact halves, the quantised two-pass lanes
 //   vector_index_hits.cpp     search_hits for a batch: the doc-id class tables, the WAL mirror, the WAL and resolve kernels' launches
+//   vector_index_filtered.cpp a filter per query in one batched call: the plan, the row lists, the segmented gather scan's launch
 #pragma once
 
 #include <algorithm>

@@ -84,6 +84,15 @@ class VacuumStats:
     elapsed_ms: float
 
 
+@dataclass(frozen=True)
+class MultiFilterStats:
+    """fsgpu_index_multi_filter_stats: queries of search_batched_per_query_filters by path."""
+    gathered: int
+    scanned: int
+    unfiltered: int
+    fallbacks: int
+
+
 class VectorIndex:
     # filter of search_batched applied to every new handle (0 = the library's automatic choice); the test-suite pins it to
     # run the same cases under the int8 and the f16 filter
@@ -326,6 +335,44 @@ class VectorIndex:
         check(_lib.lib().fsgpu_search_topk_batched(self._h, _ptr(q), nq, qlen, limit, _ptr(bm), _ptr(rows), _ptr(scores),
                                                    _ptr(counts), C.byref(fb)))
         return rows[:, :limit], scores[:, :limit], counts, fb.value
+
+    def search_batched_per_query_filters(self, queries: np.ndarray, limit: int, filters: Sequence["ResidentFilter"],
+                                         filter_of_query: Sequence[int], queries_ptr: Optional[int] = None, nq: Optional[int] = None,
+                                         out_ptrs: Optional[Tuple[int, int, int]] = None, stream: int = 0):
+        """fsgpu_search_topk_batched_multi_filtered: query q is searched under filters[filter_of_query[q]], or unfiltered (-1);
+        per query the rows, score bits and count of search_batch(q, limit, allow=that mask, exact=True)
+        -> (rows, scores, counts, fallbacks).
+        queries_ptr / out_ptrs (rows, scores, counts) / stream: the device form (fsgpu_..._device_queries) — nq queries and the three
+        outputs in device memory on a HIP stream, which is synchronised; it returns the fallbacks alone."""
+        fq = np.ascontiguousarray(filter_of_query, dtype=np.int32).reshape(-1)
+        handles = (C.c_void_p * max(len(filters), 1))(*[f._h.value for f in filters])
+        fb = C.c_uint32()
+        if queries_ptr is not None:
+            if nq is None or out_ptrs is None or fq.size != nq:
+                raise ValueError("the device form takes nq, one filter_of_query entry per query and the three output pointers")
+            check(_lib.lib().fsgpu_search_topk_batched_multi_filtered_device_queries(
+                self._h, queries_ptr, nq, self.dimension(), limit, handles, len(filters), _ptr(fq), out_ptrs[0], out_ptrs[1], out_ptrs[2],
+                stream or None, C.byref(fb)))
+            return fb.value
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq, qlen = q.shape
+        if fq.size != nq:
+            raise ValueError("filter_of_query needs one entry per query")
+        rows = np.full((nq, max(limit, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.full((nq, max(limit, 1)), np.nan, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        check(_lib.lib().fsgpu_search_topk_batched_multi_filtered(self._h, _ptr(q), nq, qlen, limit, handles, len(filters), _ptr(fq),
+                                                                  _ptr(rows), _ptr(scores), _ptr(counts), C.byref(fb)))
+        return rows[:, :limit], scores[:, :limit], counts, fb.value
+
+    def multi_filter_stats(self):
+        """Queries search_batched_per_query_filters has answered, by path: .gathered (the segmented gather scan), .scanned (a dense
+        filter's masked batched pass), .unfiltered, .fallbacks (selective groups answered query by query)."""
+        v = [C.c_uint64() for _ in range(4)]
+        check(_lib.lib().fsgpu_index_multi_filter_stats(self._h, *[C.byref(x) for x in v]))
+        return MultiFilterStats(*[x.value for x in v])
 
     def search_top_k(self, query: Sequence[float], limit: int, filter: Optional[np.ndarray] = None
                      ) -> List[VectorHit]:
@@ -633,6 +680,13 @@ class ResidentFilter:
 
     def allowed_rows(self) -> int:
         return int(_lib.lib().fsgpu_allow_bitmap_allowed_rows(self._h))
+
+    def rows(self) -> np.ndarray:
+        """The ascending row ids of the set bits as the device built them from the resident bitmap (fsgpu_allow_bitmap_rows)."""
+        out = np.zeros(max(self.allowed_rows(), 1), dtype=np.uint32)
+        n = C.c_uint64()
+        check(_lib.lib().fsgpu_allow_bitmap_rows(self._h, _ptr(out), out.size, C.byref(n)))
+        return out[: n.value]
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -238,6 +238,38 @@ fsgpu_status fsgpu_search_topk_filtered(fsgpu_index *idx, const float *queries, 
 fsgpu_status fsgpu_search_topk_batched_filtered(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_len,
                                                 uint32_t k, const fsgpu_allow_bitmap *filter, uint32_t *out_rows,
                                                 float *out_scores, uint32_t *out_counts, uint32_t *out_fallbacks);
+/* A filter PER QUERY in one batched, row-level call (no WAL merge, no doc-id dedup: as fsgpu_search_topk_batched).  Query q names
+ * filters[filter_of_query[q]], or no filter (-1).  Per query: the rows, f32 score bits and count fsgpu_search_topk_exact returns for
+ * that query with that filter's bitmap — (score desc, NaN as -inf, row asc) over the live allowed rows, count = min(k, their number);
+ * tombstones are tested when rows are scored, so a soft delete after a filter was made is honoured.  Slots beyond the count are padding.
+ * The queries are grouped by filter.  Unfiltered queries ride fsgpu_search_topk_batched; a dense filter's (allowed * 50 >= record count)
+ * ride it with that filter's resident bitmap; ALL selective filters' groups (0 < allowed * 50 < record count, the reference's
+ * GATHER_SELECTIVITY_DIVISOR, search.rs:1667) share one launch of a segmented gather scan that reads each group's rows from the
+ * slab once for all of the group's queries (F16 slab, dense rows, dimension % 8 == 0, k <= 256); an empty filter costs no launch.
+ * A selective group outside that shape is answered query by query by the fsgpu_search_topk_filtered path: still exact.
+ * *out_fallbacks (optional): those queries plus the ones the batched groups handed to the exact kernels.
+ * Refused before anything is launched: query_len != dimension (FSGPU_ERR_DIMENSION_MISMATCH); a filter_of_query entry < -1 or
+ * >= nfilters, a filter of another index or from before a compact / vacuum (FSGPU_ERR_INVALID_CONFIG).  fsgpu_index handles only. */
+fsgpu_status fsgpu_search_topk_batched_multi_filtered(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_len,
+                                                      uint32_t k, const fsgpu_allow_bitmap *const *filters, uint32_t nfilters,
+                                                      const int32_t *filter_of_query, uint32_t *out_rows, float *out_scores,
+                                                      uint32_t *out_counts, uint32_t *out_fallbacks);
+/* ... with the queries and the three outputs in device memory, enqueued on `hip_stream`, which is synchronised before the call
+ * returns (as fsgpu_search_topk_batched_device does); filters and filter_of_query stay host arrays. */
+fsgpu_status fsgpu_search_topk_batched_multi_filtered_device_queries(fsgpu_index *idx, const float *queries_dev, uint32_t nq,
+                                                                     uint32_t query_len, uint32_t k,
+                                                                     const fsgpu_allow_bitmap *const *filters, uint32_t nfilters,
+                                                                     const int32_t *filter_of_query, uint32_t *out_rows_dev,
+                                                                     float *out_scores_dev, uint32_t *out_counts_dev, void *hip_stream,
+                                                                     uint32_t *out_fallbacks);
+/* The ascending row ids of a filter's set bits (bits past the record count ignored), as the DEVICE built them from the resident
+ * bitmap — popcount per 64-bit word, exclusive scan, expand; built at first use and kept on the handle.  *out_n = their number;
+ * the first min(cap, *out_n) are copied to out_rows. */
+fsgpu_status fsgpu_allow_bitmap_rows(const fsgpu_allow_bitmap *filter, uint32_t *out_rows, uint64_t cap, uint64_t *out_n);
+/* Queries fsgpu_search_topk_batched_multi_filtered has answered so far, by path: the gather scan, a dense group's masked pass, no
+ * filter, the per-query fallback of a selective group (any pointer may be null). */
+fsgpu_status fsgpu_index_multi_filter_stats(fsgpu_index *idx, uint64_t *gathered, uint64_t *scanned, uint64_t *unfiltered,
+                                            uint64_t *fallbacks);
 /* Same, all pointers device-resident, enqueued on `hip_stream` (a hipStream_t), no host sync. */
 fsgpu_status fsgpu_search_topk_device(fsgpu_index *idx, const float *queries_dev, uint32_t nq,
                                       uint32_t query_len, uint32_t k, const uint64_t *allow_bitmap_dev,

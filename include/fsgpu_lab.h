@@ -33,6 +33,13 @@ fsgpu_status fsgpu_index_scan_stats(fsgpu_index *idx, double *total_ms, uint64_t
 /* Filtered searches (allow bitmap given) answered by scoring only the allowed rows (try_gather_filtered,
  * crates/frankensearch-index/src/search.rs:1114-1180: taken when allowed * 50 < rows) and by the masked full scan. */
 fsgpu_status fsgpu_index_filter_stats(fsgpu_index *idx, uint64_t *gathered, uint64_t *scanned);
+/* The grouping and path decision of fsgpu_search_topk_batched_multi_filtered on its own, host code only (no device is looked for):
+ * groups are numbered in the order their first query appears, no filter (-1) is a group like any other, a filter no query names
+ * forms none.  out_group_of_query [nq]; out_path_of_group [*out_ngroups <= nfilters + 1]: 0 unfiltered, 1 dense (allowed * 50 >=
+ * nrows), 2 gather (0 < allowed * 50 < nrows), 3 empty (allowed == 0).  An entry < -1 or >= nfilters: FSGPU_ERR_INVALID_CONFIG. */
+fsgpu_status fsgpu_lab_multi_filter_plan(uint64_t nrows, const uint64_t *allowed_per_filter, uint32_t nfilters,
+                                         const int32_t *filter_of_query, uint32_t nq, int32_t *out_group_of_query,
+                                         int32_t *out_path_of_group, uint32_t *out_ngroups);
 /* Name of the template instantiation the last batched main pass launched in this process ran ("" before the first one), spelled as
  * rocprofv3 prints it: lets bench.py tie a committed PMC summary to the kernel that actually ran. */
 const char *fsgpu_last_main_pass_kernel(void);
