@@ -199,6 +199,22 @@ SIGNATURES = {
     "fsgpu_hash_device": (_i32, [_vp]),
     "fsgpu_hash_embed": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "fsgpu_hash_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_lab_wordpiece_encode_stage_ms": (_i32, [_vp, _vp, _vp, _u32, _i32, _u32, _vp, _u64, _vp, _vp]),
+    "fsgpu_wordpiece_create": (_i32, [_i32, _vp, C.POINTER(_vp)]),
+    "fsgpu_wordpiece_destroy": (None, [_vp]),
+    "fsgpu_wordpiece_device": (_i32, [_vp]),
+    "fsgpu_wordpiece_vocab_size": (_u32, [_vp]),
+    "fsgpu_wordpiece_encode": (_i32, [_vp, _vp, _vp, _u32, _i32, _u32, _vp, _u64, _vp, _vp, C.POINTER(_u64), C.POINTER(_u32)]),
+    "fsgpu_wordpiece_encode_device": (_i32, [_vp, _vp, _vp, _u32, _i32, _u32, _vp, _u64, _vp, _vp, C.POINTER(_u64), C.POINTER(_u32)]),
+    "fsgpu_wordpiece_encode_pairs": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, C.POINTER(_u64),
+                                            C.POINTER(_u32)]),
+    "fsgpu_wordpiece_encode_pairs_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, C.POINTER(_u64),
+                                                   C.POINTER(_u32)]),
+    "fsgpu_bert_embed_texts": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "fsgpu_bert_embed_texts_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "fsgpu_reranker_score_texts": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "fsgpu_m2v_embed_texts": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, C.POINTER(_u32)]),
+    "fsgpu_m2v_embed_texts_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, C.POINTER(_u32)]),
     "fsgpu_index_builder_finish": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), _vp]),   # (stats: index_builder._Stats)
     "fsgpu_rerank_apply": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, C.c_float, _vp]),
     "fsgpu_mmr_config_default": (_i32, [_vp]),

@@ -2,6 +2,7 @@
 // Layer order follows encoder_layer_raw (crates/frankensearch-rerank/src/native.rs:587-626).
 #include "lab_env.hpp"
 #include "bert_embedder.hpp"
+#include "wordpiece.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -646,7 +647,7 @@ BertDocsPacking bert_docs_pack(const int32_t* ids, const uint32_t* offs, uint32_
         for (uint32_t i = blk_doc[b]; i < blk_doc[b + 1]; ++i) {
             if (offs[i + 1] == offs[i]) continue;
             for (uint32_t t = offs[i]; t < offs[i + 1]; ++t) {
-                row_id[(size_t)b * 32 + (t - t0)] = ids[t];
+                if (ids) row_id[(size_t)b * 32 + (t - t0)] = ids[t];
                 row_meta[(size_t)b * 32 + (t - t0)] |= ((t - offs[i]) << 8) | local;
             }
             ++local;
@@ -680,13 +681,13 @@ void BertDocsPacking::point(BertDocsArgs& a, const unsigned char* base) const {
 // Every text at most 32 tokens long (a batch of queries): ONE launch for the whole forward (bert_docs_w.hip) over the row blocks of
 // bert_docs_pack.  ids: this call's tokens; offs: the call's offsets rebased to 0.
 SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out,
-                                       float* out_dev) {
+                                       float* out_dev, bool ids_on_device) {
     const size_t H = cfg_.hidden;
-    const BertDocsPacking pk = bert_docs_pack(ids, offs.data(), n, total);
+    const BertDocsPacking pk = bert_docs_pack(ids_on_device ? nullptr : ids, offs.data(), n, total);
     const uint32_t nblocks = pk.nblocks;
     const size_t in_bytes = pk.in_bytes;
     const size_t out_bytes = (size_t)n * H * 4;
-    const bool pinned = in_bytes + out_bytes <= kDocsIoBytes;
+    const bool pinned = !ids_on_device && in_bytes + out_bytes <= kDocsIoBytes;   // (device ids stay on the device)
     if (pinned && !docs_io_ && !docs_io_failed_ && hipHostMalloc(&docs_io_, kDocsIoBytes, hipHostMallocMapped) != hipSuccess) {
         docs_io_ = nullptr;
         docs_io_failed_ = true;
@@ -740,6 +741,9 @@ SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uin
     BERT_TRY(docs_out_.reserve(out_bytes));   // (not out_: captured graphs name that one)
     BERT_HIP(hipMemcpyAsync(docs_in_.ptr, host.data(), in_bytes, hipMemcpyHostToDevice, stream_));
     point(static_cast<const unsigned char*>(docs_in_.ptr));
+    if (ids_on_device)   // the blocks' row ids, from the ids where they lie (the copy above left them at -1)
+        BERT_HIP(launch_wordpiece_block_rows(ids, a.blk_tok, reinterpret_cast<int32_t*>(static_cast<unsigned char*>(docs_in_.ptr) + pk.o_rid),
+                                             nblocks, stream_));
     a.out = out_dev ? out_dev : static_cast<float*>(docs_out_.ptr);
     BERT_HIP(launch_bert_docs_w(a, nblocks, stream_));
     if (out) BERT_HIP(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, stream_));
@@ -748,6 +752,16 @@ SearchError NativeEmbedder::embed_docs(const int32_t* ids, const std::vector<uin
 }
 
 SearchError NativeEmbedder::embed_batch(const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out, float* out_dev) {
+    return embed_any(ids, false, offsets, n, out, out_dev);
+}
+
+SearchError NativeEmbedder::embed_batch_device_ids(const int32_t* ids_dev, const uint32_t* offsets, uint32_t n, float* out, float* out_dev) {
+    return embed_any(ids_dev, true, offsets, n, out, out_dev);
+}
+
+// ids_on_device: `ids` is device memory and is never read on the host (its range is the caller's word: the tokenizer's vocabulary).
+SearchError NativeEmbedder::embed_any(const int32_t* ids, bool ids_on_device, const uint32_t* offsets, uint32_t n, float* out,
+                                      float* out_dev) {
     if (n == 0) return SearchError{};
     if (!offsets || (!out && !out_dev)) return err(FSGPU_ERR_NULL_ARGUMENT, "offsets/out is null");
     std::lock_guard<std::mutex> lock(mu_);
@@ -777,12 +791,14 @@ SearchError NativeEmbedder::embed_batch(const int32_t* ids, const uint32_t* offs
     for (uint32_t i = 0; i <= n; ++i) offs[i] = offsets[i] - base;
     for (uint32_t i = 0; i < n; ++i)
         for (uint32_t t = offs[i]; t < offs[i + 1]; ++t) {
-            const int32_t id = ids[base + t];
-            if (id < 0 || (uint32_t)id >= cfg_.vocab) return err(FSGPU_ERR_INVALID_CONFIG, "token id out of vocabulary");
+            if (!ids_on_device) {
+                const int32_t id = ids[base + t];
+                if (id < 0 || (uint32_t)id >= cfg_.vocab) return err(FSGPU_ERR_INVALID_CONFIG, "token id out of vocabulary");
+            }
             positions[t] = (int32_t)(t - offs[i]);  // positions restart at 0 per input (native.rs:1159-1167)
         }
     BERT_HIP(hipSetDevice(device_));
-    if (docs_path(total, max_seq)) return embed_docs(ids + base, offs, n, total, out, out_dev);
+    if (docs_path(total, max_seq)) return embed_docs(ids + base, offs, n, total, out, out_dev, ids_on_device);
     {
         // (graph-eligible calls share buffers of the graph-eligible maximum: see reserve_workspaces)
         const bool small = total <= kGraphMaxTokens;
@@ -803,7 +819,8 @@ SearchError NativeEmbedder::embed_batch(const int32_t* ids, const uint32_t* offs
     // pooled vectors are read back from pinned memory the pool kernel wrote — no D2H copy.
     const size_t in_bytes = ((size_t)total * 8 + (size_t)(n + 1) * 4 + 255) & ~(size_t)255;
     const size_t out_bytes = (size_t)n * H * 4;
-    if (in_bytes + out_bytes <= kPinnedIoBytes) {
+    const bool small_io = !ids_on_device && in_bytes + out_bytes <= kPinnedIoBytes;   // (device ids: no pinned block, no graph)
+    if (small_io) {
         if (!io_host_ && !io_failed_ && hipHostMalloc(&io_host_, kPinnedIoBytes, hipHostMallocMapped) != hipSuccess) {
             io_host_ = nullptr;
             io_failed_ = true;
@@ -811,7 +828,7 @@ SearchError NativeEmbedder::embed_batch(const int32_t* ids, const uint32_t* offs
         }
     }
     auto run_once = [&]() -> SearchError {
-        if (io_host_ && in_bytes + out_bytes <= kPinnedIoBytes) {
+        if (io_host_ && small_io) {
             unsigned char* io = static_cast<unsigned char*>(io_host_);
             std::memcpy(io, ids + base, (size_t)total * 4);
             std::memcpy(io + (size_t)total * 4, positions.data(), (size_t)total * 4);
@@ -880,7 +897,7 @@ SearchError NativeEmbedder::embed_batch(const int32_t* ids, const uint32_t* offs
             if (out) std::memcpy(out, io + in_bytes, out_bytes);
             return SearchError{};
         }
-        BERT_HIP(hipMemcpyAsync(ids_.ptr, ids + base, (size_t)total * 4, hipMemcpyHostToDevice, stream_));
+        BERT_HIP(hipMemcpyAsync(ids_.ptr, ids + base, (size_t)total * 4, ids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
         BERT_HIP(hipMemcpyAsync(positions_.ptr, positions.data(), (size_t)total * 4, hipMemcpyHostToDevice, stream_));
         BERT_HIP(hipMemcpyAsync(offsets_.ptr, offs.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, stream_));
         pooled_out_ = out_dev;   // (null: the pool kernel writes out_)

@@ -45,7 +45,8 @@ struct BertDocsPacking {
     void fill(unsigned char* dst, const uint32_t* offs) const;           // the input block, for the offsets it was packed from
     void point(BertDocsArgs& a, const unsigned char* base) const;        // the kernel's five input pointers into a copy at `base`
 };
-// ids: the call's tokens; offs [n + 1]: the call's offsets rebased to 0, every text at most 32 tokens; total = offs[n]
+// ids: the call's tokens (null: every row id is left at -1, for a caller that fills them on the device); offs [n + 1]: the call's
+// offsets rebased to 0, every text at most 32 tokens; total = offs[n]
 BertDocsPacking bert_docs_pack(const int32_t* ids, const uint32_t* offs, uint32_t n, uint32_t total);
 
 class NativeEmbedder {
@@ -63,6 +64,11 @@ class NativeEmbedder {
     // out_dev (on this embedder's device, may be null): the pooled vectors are left in device memory — the hand-off to a search that
     // takes device queries; out (may then be null): the host copy.  Either way the call returns when the forward has finished.
     SearchError embed_batch(const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out, float* out_dev = nullptr);
+    // ... over ids that already lie in this embedder's device memory (the device tokenizer's CSR, every id below vocab()); offsets
+    // stay a host array.  The same kernels in the same forms as embed_batch, so the same bits: the row blocks of the short-text
+    // forward are filled from the device ids by a kernel, the other forwards read a device-to-device copy; no pinned block, no graph.
+    SearchError embed_batch_device_ids(const int32_t* ids_dev, const uint32_t* offsets, uint32_t n, float* out, float* out_dev);
+    uint32_t vocab() const { return cfg_.vocab; }
     uint32_t dimension() const { return cfg_.hidden; }
     int device() const { return device_; }
     uint32_t linear_format() const { return int8_ ? FSGPU_BERT_LINEAR_INT8_DYNAMIC : FSGPU_BERT_LINEAR_F16; }
@@ -89,7 +95,9 @@ class NativeEmbedder {
     bool query_path(uint32_t tokens) const;
     bool one_launch_path() const;                                  // ... as ONE launch with grid-wide barriers (experiments builds)
     bool docs_path(uint32_t tokens, uint32_t max_seq) const;       // every text <= 32 tokens: ONE launch (bert_docs_w.hip)
-    SearchError embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out, float* out_dev);
+    SearchError embed_docs(const int32_t* ids, const std::vector<uint32_t>& offs, uint32_t n, uint32_t total, float* out, float* out_dev,
+                           bool ids_on_device);
+    SearchError embed_any(const int32_t* ids, bool ids_on_device, const uint32_t* offsets, uint32_t n, float* out, float* out_dev);
     SearchError reserve_workspaces(uint32_t tokens);
     void drop_graphs();
     // One layer of the fragment-order path, in pieces its callers share: the QKV projection of T rows (f16 Q | K | V out), then — after

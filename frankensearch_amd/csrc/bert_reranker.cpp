@@ -126,6 +126,18 @@ SearchError NativeReranker::forward_chunk(uint32_t p0, uint32_t p1, uint32_t t0,
 
 SearchError NativeReranker::score(const int32_t* ids, const int32_t* type_ids, const uint32_t* offsets, uint32_t n, float* logits,
                                   float* scores) {
+    return score_any(ids, type_ids, false, offsets, n, logits, scores);
+}
+
+SearchError NativeReranker::score_device_ids(const int32_t* ids_dev, const int32_t* type_ids_dev, const uint32_t* offsets, uint32_t n,
+                                             float* logits, float* scores) {
+    return score_any(ids_dev, type_ids_dev, true, offsets, n, logits, scores);
+}
+
+// on_device: ids / type_ids are device memory, never read on the host (their ranges are the caller's word), starting at pair 0's
+// first token, and no pair is empty — so the live pairs' tokens are the call's tokens, in place.
+SearchError NativeReranker::score_any(const int32_t* ids, const int32_t* type_ids, bool on_device, const uint32_t* offsets, uint32_t n,
+                                      float* logits, float* scores) {
     if (n == 0) return SearchError{};
     if (!offsets || !logits || !scores) return rr_err(FSGPU_ERR_NULL_ARGUMENT, "offsets/out_logits/out_scores is null");
     std::lock_guard<std::mutex> lock(mu_);
@@ -139,9 +151,10 @@ SearchError NativeReranker::score(const int32_t* ids, const int32_t* type_ids, c
         if (len > max_len)
             return rr_err(FSGPU_ERR_INVALID_CONFIG, "pair longer than max_position_embeddings (" + std::to_string(len) + " > " +
                                                         std::to_string(max_len) + " tokens: truncate first)");
+        if (len == 0 && on_device) return rr_err(FSGPU_ERR_INVALID_CONFIG, "an empty pair in a device CSR");
         if (len == 0) continue;
         if (!ids || !type_ids) return rr_err(FSGPU_ERR_NULL_ARGUMENT, "ids/type_ids is null");
-        for (uint32_t t = offsets[i]; t < offsets[i + 1]; ++t) {
+        for (uint32_t t = offsets[i]; t < offsets[i + 1] && !on_device; ++t) {
             if (ids[t] < 0 || (uint32_t)ids[t] >= vocab) return rr_err(FSGPU_ERR_INVALID_CONFIG, "token id out of vocabulary");
             if (type_ids[t] < 0 || (uint32_t)type_ids[t] >= type_vocab_)
                 return rr_err(FSGPU_ERR_INVALID_CONFIG, "token type id out of range (type_vocab_size " + std::to_string(type_vocab_) + ")");
@@ -171,8 +184,10 @@ SearchError NativeReranker::score(const int32_t* ids, const int32_t* type_ids, c
         }
         Chunk& c = chunks.back();
         for (uint32_t j = 0; j < len; ++j) {
-            in_host_[t + j] = ids[offsets[i] + j];
-            in_host_[(size_t)total + t + j] = type_ids[offsets[i] + j];
+            if (!on_device) {
+                in_host_[t + j] = ids[offsets[i] + j];
+                in_host_[(size_t)total + t + j] = type_ids[offsets[i] + j];
+            }
             in_host_[2 * (size_t)total + t + j] = (int32_t)j;   // positions restart at 0 per pair
         }
         t += len;
@@ -200,7 +215,14 @@ SearchError NativeReranker::score(const int32_t* ids, const int32_t* type_ids, c
     RR_TRY(xch_.reserve((size_t)chunk_pairs * H * 2));
     RR_TRY(ctxc_.reserve((size_t)chunk_pairs * H * 2));
     hipStream_t stream = enc_.stream_;
-    RR_HIP(hipMemcpyAsync(in_.ptr, in_host_.data(), in_host_.size() * 4, hipMemcpyHostToDevice, stream));
+    if (on_device) {   // ids | types from where they lie, positions from the host
+        int32_t* in = static_cast<int32_t*>(in_.ptr);
+        RR_HIP(hipMemcpyAsync(in, ids + offsets[0], (size_t)total * 4, hipMemcpyDeviceToDevice, stream));
+        RR_HIP(hipMemcpyAsync(in + total, type_ids + offsets[0], (size_t)total * 4, hipMemcpyDeviceToDevice, stream));
+        RR_HIP(hipMemcpyAsync(in + 2 * (size_t)total, in_host_.data() + 2 * (size_t)total, (size_t)total * 4, hipMemcpyHostToDevice, stream));
+    } else {
+        RR_HIP(hipMemcpyAsync(in_.ptr, in_host_.data(), in_host_.size() * 4, hipMemcpyHostToDevice, stream));
+    }
     RR_HIP(hipMemcpyAsync(offs_.ptr, offs_host_.data(), offs_host_.size() * 4, hipMemcpyHostToDevice, stream));
     for (const Chunk& c : chunks) RR_TRY(forward_chunk(c.p0, c.p1, c.t0, c.t1, c.max_seq, c.off_base));
     std::vector<float> lg(m), sc(m);

@@ -22,6 +22,13 @@ class NativeReranker {
     SearchError init_safetensors(int device, const void* blob, uint64_t blob_len, float ln_eps);
     // Pair i is ids[offsets[i]..offsets[i+1]) with type_ids alongside; logits / scores [n].  A zero-length pair gets logit 0, score 0.5.
     SearchError score(const int32_t* ids, const int32_t* type_ids, const uint32_t* offsets, uint32_t n, float* logits, float* scores);
+    // ... over ids and type ids that already lie in this reranker's device memory (the device tokenizer's pair CSR: every id below
+    // vocab(), every type id 0 or 1, no empty pair); offsets stay a host array.  The same chunks and kernels as score(), so the
+    // same bits: the chain reads device-to-device copies of the ids and type ids.
+    SearchError score_device_ids(const int32_t* ids_dev, const int32_t* type_ids_dev, const uint32_t* offsets, uint32_t n, float* logits,
+                                 float* scores);
+    uint32_t vocab() const { return enc_.cfg_.vocab; }
+    uint32_t type_vocab() const { return type_vocab_; }
     int device() const { return enc_.device(); }
     uint32_t max_length() const { return enc_.cfg_.max_pos; }   // min(max_position_embeddings, 512)
 
@@ -30,6 +37,8 @@ class NativeReranker {
     static constexpr uint32_t kChunkTokens = 16384;
 
   private:
+    SearchError score_any(const int32_t* ids, const int32_t* type_ids, bool on_device, const uint32_t* offsets, uint32_t n, float* logits,
+                          float* scores);
     SearchError forward_chunk(uint32_t p0, uint32_t p1, uint32_t t0, uint32_t t1, uint32_t max_seq, uint32_t off_base);
 
     std::mutex mu_;          // one caller at a time (native.rs:1668)

@@ -20,6 +20,7 @@
 #include "bert_reranker.hpp"
 #include "coalescer.hpp"
 #include "hash_embedder.hpp"
+#include "wordpiece.hpp"
 #include "index_builder.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
@@ -107,6 +108,9 @@ struct fsgpu_index_builder {
 };
 struct fsgpu_hash {
     fsgpu::HashEmbedder impl;
+};
+struct fsgpu_wordpiece {
+    fsgpu::WordPieceTokenizer impl;
 };
 namespace {
 
@@ -3279,6 +3283,247 @@ fsgpu_status fsgpu_index_builder_add_hash(fsgpu_index_builder* b, fsgpu_hash* h,
             return e;
         };
         return finish(b->impl.add_embedded(embed, h->impl.device(), h->impl.dimension(), n, doc_ids, doc_id_lens, out_bad_row));
+    });
+}
+
+// ---- the WordPiece tokenizer (wordpiece.cpp): BertNormalizer -> BertPreTokenizer -> WordPiece -> [CLS] ... [SEP] ----
+
+fsgpu_status fsgpu_wordpiece_create(int32_t device, const fsgpu_wordpiece_config* config, fsgpu_wordpiece** out) {
+    if (!out) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    *out = nullptr;
+    if (!config) return fail(FSGPU_ERR_NULL_ARGUMENT, "config is null");
+    return guarded([&]() -> fsgpu_status {
+        auto h = std::make_unique<fsgpu_wordpiece>();
+        fsgpu::SearchError e = h->impl.init(device, *config);
+        if (!e.ok()) return finish(e);
+        *out = h.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_wordpiece_destroy(fsgpu_wordpiece* tok) { delete tok; }
+int32_t fsgpu_wordpiece_device(const fsgpu_wordpiece* tok) { return tok ? tok->impl.device() : -1; }
+uint32_t fsgpu_wordpiece_vocab_size(const fsgpu_wordpiece* tok) { return tok ? tok->impl.vocab_size() : 0; }
+
+namespace {
+
+fsgpu_status wordpiece_encode(fsgpu_wordpiece* tok, fsgpu::WordPieceTokenizer::Request r) {
+    if (!tok) return fail(FSGPU_ERR_NULL_ARGUMENT, "tokenizer is null");
+    return guarded([&]() -> fsgpu_status { return finish(tok->impl.encode(r)); });
+}
+
+}  // namespace
+
+fsgpu_status fsgpu_wordpiece_encode(fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                    int32_t add_special_tokens, uint32_t max_length, uint32_t* out_ids, uint64_t ids_capacity,
+                                    uint32_t* out_offsets, uint8_t* out_status, uint64_t* out_total, uint32_t* out_bad_text) {
+    fsgpu::WordPieceTokenizer::Request r;
+    r.a_bytes = text_bytes;
+    r.a_offsets = offsets;
+    r.n = n;
+    r.add_special = add_special_tokens != 0;
+    r.max_length = max_length;
+    r.ids_capacity = ids_capacity;
+    r.out_ids = out_ids;
+    r.out_offsets = out_offsets;
+    r.out_status = out_status;
+    r.out_total = out_total;
+    r.out_bad_text = out_bad_text;
+    return wordpiece_encode(tok, r);
+}
+
+fsgpu_status fsgpu_lab_wordpiece_encode_stage_ms(fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                                 int32_t add_special_tokens, uint32_t max_length, uint32_t* out_ids, uint64_t ids_capacity,
+                                                 uint32_t* out_offsets, float* out_stage_ms) {
+    if (!out_stage_ms) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_stage_ms is null");
+    fsgpu::WordPieceTokenizer::Request r;
+    r.a_bytes = text_bytes;
+    r.a_offsets = offsets;
+    r.n = n;
+    r.add_special = add_special_tokens != 0;
+    r.max_length = max_length;
+    r.ids_capacity = ids_capacity;
+    r.out_ids = out_ids;
+    r.out_offsets = out_offsets;
+    r.stage_ms = out_stage_ms;
+    return wordpiece_encode(tok, r);
+}
+
+fsgpu_status fsgpu_wordpiece_encode_device(fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                           int32_t add_special_tokens, uint32_t max_length, uint32_t* out_ids_dev, uint64_t ids_capacity,
+                                           uint32_t* out_offsets_dev, uint8_t* out_status, uint64_t* out_total, uint32_t* out_bad_text) {
+    fsgpu::WordPieceTokenizer::Request r;
+    r.a_bytes = text_bytes;
+    r.a_offsets = offsets;
+    r.n = n;
+    r.add_special = add_special_tokens != 0;
+    r.max_length = max_length;
+    r.ids_capacity = ids_capacity;
+    r.device_out = true;
+    r.out_ids = out_ids_dev;
+    r.out_offsets = out_offsets_dev;
+    r.out_status = out_status;
+    r.out_total = out_total;
+    r.out_bad_text = out_bad_text;
+    return wordpiece_encode(tok, r);
+}
+
+fsgpu_status fsgpu_wordpiece_encode_pairs(fsgpu_wordpiece* tok, const uint8_t* a_bytes, const uint32_t* a_offsets, const uint8_t* b_bytes,
+                                          const uint32_t* b_offsets, uint32_t n, uint32_t max_length, uint32_t* out_ids,
+                                          uint32_t* out_type_ids, uint64_t ids_capacity, uint32_t* out_offsets, uint8_t* out_status,
+                                          uint64_t* out_total, uint32_t* out_bad_text) {
+    fsgpu::WordPieceTokenizer::Request r;
+    r.a_bytes = a_bytes;
+    r.a_offsets = a_offsets;
+    r.b_bytes = b_bytes;
+    r.b_offsets = b_offsets;
+    r.n = n;
+    r.pairs = true;
+    r.add_special = true;
+    r.max_length = max_length;
+    r.ids_capacity = ids_capacity;
+    r.out_ids = out_ids;
+    r.out_type_ids = out_type_ids;
+    r.out_offsets = out_offsets;
+    r.out_status = out_status;
+    r.out_total = out_total;
+    r.out_bad_text = out_bad_text;
+    return wordpiece_encode(tok, r);
+}
+
+fsgpu_status fsgpu_wordpiece_encode_pairs_device(fsgpu_wordpiece* tok, const uint8_t* a_bytes, const uint32_t* a_offsets,
+                                                 const uint8_t* b_bytes, const uint32_t* b_offsets, uint32_t n, uint32_t max_length,
+                                                 uint32_t* out_ids_dev, uint32_t* out_type_ids_dev, uint64_t ids_capacity,
+                                                 uint32_t* out_offsets_dev, uint8_t* out_status, uint64_t* out_total,
+                                                 uint32_t* out_bad_text) {
+    fsgpu::WordPieceTokenizer::Request r;
+    r.a_bytes = a_bytes;
+    r.a_offsets = a_offsets;
+    r.b_bytes = b_bytes;
+    r.b_offsets = b_offsets;
+    r.n = n;
+    r.pairs = true;
+    r.add_special = true;
+    r.max_length = max_length;
+    r.ids_capacity = ids_capacity;
+    r.device_out = true;
+    r.out_ids = out_ids_dev;
+    r.out_type_ids = out_type_ids_dev;
+    r.out_offsets = out_offsets_dev;
+    r.out_status = out_status;
+    r.out_total = out_total;
+    r.out_bad_text = out_bad_text;
+    return wordpiece_encode(tok, r);
+}
+
+namespace {
+
+using WpRequest = fsgpu::WordPieceTokenizer::Request;
+using WpCsr = fsgpu::WordPieceTokenizer::OwnCsr;
+
+// what every fused text-in call checks first; FSGPU_OK: go on
+fsgpu_status fused_preamble(const void* model, fsgpu_wordpiece* tok, int model_device, uint32_t* out_bad_text) {
+    if (!model) return fail(FSGPU_ERR_NULL_ARGUMENT, "model is null");
+    if (!tok) return fail(FSGPU_ERR_NULL_ARGUMENT, "tokenizer is null");
+    if (out_bad_text) *out_bad_text = fsgpu::WordPieceTokenizer::kNoBadText;
+    if (tok->impl.device() != model_device) return fail(FSGPU_ERR_INVALID_CONFIG, "the tokenizer and the model are on different devices");
+    return FSGPU_OK;
+}
+
+// raw text -> the tokenizer's device CSR -> the potion kernel, which reads the ids where they lie
+fsgpu_status m2v_embed_texts(fsgpu_m2v* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out,
+                             float* out_dev, uint32_t* out_bad_text) {
+    const fsgpu_status pre = fused_preamble(m, tok, m ? m->impl.device() : -1, out_bad_text);
+    if (pre != FSGPU_OK) return pre;
+    if (n == 0) return FSGPU_OK;
+    if (!out && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    return guarded([&]() -> fsgpu_status {
+        WpRequest r;   // encode_fast(text, false): no special tokens, no truncation
+        r.a_bytes = text_bytes;
+        r.a_offsets = offsets;
+        r.n = n;
+        r.out_bad_text = out_bad_text;
+        return finish(tok->impl.encode_then(r, [&](const WpCsr& c) { return m->impl.embed_batch_device_ids(c.ids_dev, c.offsets_dev, n, out, out_dev); }));
+    });
+}
+
+// ... -> the MiniLM forward over device ids ([CLS] ... [SEP], truncated to max_length)
+fsgpu_status bert_embed_texts(fsgpu_bert* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                              uint32_t max_length, float* out, float* out_dev, uint32_t* out_bad_text) {
+    const fsgpu_status pre = fused_preamble(m, tok, m ? m->impl.device() : -1, out_bad_text);
+    if (pre != FSGPU_OK) return pre;
+    if (tok->impl.vocab_size() > m->impl.vocab()) return fail(FSGPU_ERR_INVALID_CONFIG, "the tokenizer's vocabulary is larger than the model's");
+    if (n == 0) return FSGPU_OK;
+    if (!out && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out is null");
+    return guarded([&]() -> fsgpu_status {
+        WpRequest r;
+        r.a_bytes = text_bytes;
+        r.a_offsets = offsets;
+        r.n = n;
+        r.add_special = true;
+        r.max_length = max_length;
+        r.out_bad_text = out_bad_text;
+        return finish(tok->impl.encode_then(r, [&](const WpCsr& c) {
+            return m->impl.embed_batch_device_ids(reinterpret_cast<const int32_t*>(c.ids_dev), c.offsets_host, n, out, out_dev);
+        }));
+    });
+}
+
+}  // namespace
+
+fsgpu_status fsgpu_m2v_embed_texts(fsgpu_m2v* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                   float* out, uint32_t* out_bad_text) {
+    return m2v_embed_texts(m, tok, text_bytes, offsets, n, out, nullptr, out_bad_text);
+}
+
+fsgpu_status fsgpu_m2v_embed_texts_device(fsgpu_m2v* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                          float* out_dev, uint32_t* out_bad_text) {
+    return m2v_embed_texts(m, tok, text_bytes, offsets, n, nullptr, out_dev, out_bad_text);
+}
+
+fsgpu_status fsgpu_bert_embed_texts(fsgpu_bert* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                    uint32_t max_length, float* out, uint32_t* out_bad_text) {
+    return bert_embed_texts(m, tok, text_bytes, offsets, n, max_length, out, nullptr, out_bad_text);
+}
+
+fsgpu_status fsgpu_bert_embed_texts_device(fsgpu_bert* m, fsgpu_wordpiece* tok, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n,
+                                           uint32_t max_length, float* out_dev, uint32_t* out_bad_text) {
+    return bert_embed_texts(m, tok, text_bytes, offsets, n, max_length, nullptr, out_dev, out_bad_text);
+}
+
+fsgpu_status fsgpu_reranker_score_texts(fsgpu_reranker* m, fsgpu_wordpiece* tok, const uint8_t* query_bytes, uint32_t query_len,
+                                        const uint8_t* doc_bytes, const uint32_t* doc_offsets, uint32_t n, uint32_t max_length,
+                                        float* out_logits, float* out_scores, uint32_t* out_bad_text) {
+    const fsgpu_status pre = fused_preamble(m, tok, m ? m->impl.device() : -1, out_bad_text);
+    if (pre != FSGPU_OK) return pre;
+    if (tok->impl.vocab_size() > m->impl.vocab()) return fail(FSGPU_ERR_INVALID_CONFIG, "the tokenizer's vocabulary is larger than the model's");
+    if (m->impl.type_vocab() < 2) return fail(FSGPU_ERR_INVALID_CONFIG, "the model has no second token type for the document");
+    if (n == 0) return FSGPU_OK;
+    if (!out_logits || !out_scores) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_logits / out_scores is null");
+    if (query_len && !query_bytes) return fail(FSGPU_ERR_NULL_ARGUMENT, "query_bytes is null");
+    if ((uint64_t)query_len * n > 0xffffffffull) return fail(FSGPU_ERR_INVALID_CONFIG, "the query times the documents must stay below 4 GiB");
+    return guarded([&]() -> fsgpu_status {
+        // pair i is (query, document i): the query's bytes once per pair
+        std::vector<uint8_t> a_bytes((size_t)query_len * n);
+        std::vector<uint32_t> a_offsets((size_t)n + 1);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (query_len) std::memcpy(a_bytes.data() + (size_t)i * query_len, query_bytes, query_len);
+            a_offsets[i + 1] = (i + 1) * query_len;
+        }
+        fsgpu::WordPieceTokenizer::Request r;
+        r.a_bytes = a_bytes.data();
+        r.a_offsets = a_offsets.data();
+        r.b_bytes = doc_bytes;
+        r.b_offsets = doc_offsets;
+        r.n = n;
+        r.pairs = true;
+        r.add_special = true;
+        r.max_length = max_length;
+        r.out_bad_text = out_bad_text;
+        return finish(tok->impl.encode_then(r, [&](const fsgpu::WordPieceTokenizer::OwnCsr& c) {
+            return m->impl.score_device_ids(reinterpret_cast<const int32_t*>(c.ids_dev), reinterpret_cast<const int32_t*>(c.type_ids_dev),
+                                            c.offsets_host, n, out_logits, out_scores);
+        }));
     });
 }
 

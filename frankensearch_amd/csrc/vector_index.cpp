@@ -1386,6 +1386,20 @@ SearchError Model2VecEmbedder::embed_batch(const uint32_t* ids, const uint32_t* 
     return ok();
 }
 
+SearchError Model2VecEmbedder::embed_batch_device_ids(const uint32_t* ids_dev, const uint32_t* offsets_dev, uint32_t n, float* out,
+                                                      float* out_dev) {
+    if (n == 0) return ok();
+    if (!ids_dev || !offsets_dev || (!out && !out_dev)) return make_error(FSGPU_ERR_NULL_ARGUMENT, "ids/offsets/out is null");
+    std::lock_guard<std::mutex> lock(mu_);
+    FSGPU_HIP(hipSetDevice(device_));
+    if (!out_dev) FSGPU_TRY(out_.reserve((size_t)n * dim_ * 4));
+    FSGPU_HIP(launch_m2v_embed(static_cast<const float*>(table_.ptr), vocab_, dim_, ids_dev, offsets_dev, n,
+                               out_dev ? out_dev : static_cast<float*>(out_.ptr), stream_));
+    if (out) FSGPU_HIP(hipMemcpyAsync(out, out_dev ? out_dev : out_.ptr, (size_t)n * dim_ * 4, hipMemcpyDeviceToHost, stream_));
+    FSGPU_HIP(hipStreamSynchronize(stream_));
+    return ok();
+}
+
 }  // namespace fsgpu
 
 namespace fsgpu {

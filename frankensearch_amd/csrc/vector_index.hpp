@@ -552,6 +552,8 @@ class Model2VecEmbedder {
     SearchError init(int device, const float* table, uint32_t vocab, uint32_t dim);
     // out_dev (on this embedder's device, may be null): the vectors are left in device memory; out (may then be null): host copy
     SearchError embed_batch(const uint32_t* ids, const uint32_t* offsets, uint32_t n, float* out, float* out_dev = nullptr);
+    // ... over ids and offsets [n + 1] that already lie in this embedder's device memory, complete (the device tokenizer's CSR)
+    SearchError embed_batch_device_ids(const uint32_t* ids_dev, const uint32_t* offsets_dev, uint32_t n, float* out, float* out_dev);
     uint32_t dimension() const { return dim_; }
     int device() const { return device_; }
 

@@ -1,6 +1,7 @@
 """Embedders — host-side mirror of the reference's SyncEmbed implementations
-(crates/frankensearch-core/src/traits.rs:401-582) over libfsgpu.so.  Tokenisation is the caller's
-(third-party `tokenizers` in the reference); the boundary is token ids.
+(crates/frankensearch-core/src/traits.rs:401-582) over libfsgpu.so.  The encoders' boundary is token ids;
+WordPieceTokenizer makes them on the device from raw text (the reference uses third-party `tokenizers`), and
+Model2VecEmbedder.embed_texts takes text straight through.
 """
 from __future__ import annotations
 
@@ -51,6 +52,24 @@ class Model2VecEmbedder:
             out = np.empty((n, self._dim), dtype=np.float32)
         check(_lib.lib().fsgpu_m2v_embed(self._h, ids.ctypes.data, offsets.ctypes.data, n, out.ctypes.data))
         return out
+
+    def embed_texts(self, tokenizer: "WordPieceTokenizer", texts: Sequence[str], out: np.ndarray = None) -> np.ndarray:
+        """embed_batch_sync from raw text (model2vec_embedder.rs:280-335): tokenised on the device without special tokens or
+        truncation (encode_fast(text, false)), the ids never leave it.  A text the device tokenizer leaves to the host raises with
+        `.bad_text` set to its index; nothing is written."""
+        flat, offsets = _text_arrays(texts)
+        n = offsets.shape[0] - 1
+        if out is None:
+            out = np.empty((n, self._dim), dtype=np.float32)
+        _call_with_bad_text(_lib.lib().fsgpu_m2v_embed_texts, self._h, tokenizer._h, flat.ctypes.data, offsets.ctypes.data, n,
+                            out.ctypes.data)
+        return out
+
+    def embed_texts_device(self, tokenizer: "WordPieceTokenizer", texts: Sequence[str], out_ptr: int) -> None:
+        """... into [n, dim] f32 of the embedder's device."""
+        flat, offsets = _text_arrays(texts)
+        _call_with_bad_text(_lib.lib().fsgpu_m2v_embed_texts_device, self._h, tokenizer._h, flat.ctypes.data, offsets.ctypes.data,
+                            offsets.shape[0] - 1, out_ptr)
 
     def set_coalescing(self, max_batch: int, max_wait_us: int = 100) -> None:
         check(_lib.lib().fsgpu_m2v_set_coalescing(self._h, max_batch, max_wait_us))
@@ -212,6 +231,25 @@ class NativeEmbedder:
         check(_lib.lib().fsgpu_bert_embed(self._h, ids.ctypes.data, offsets.ctypes.data, n, out.ctypes.data))
         return out
 
+    def embed_texts(self, tokenizer: "WordPieceTokenizer", texts: Sequence[str], max_length=None, out: np.ndarray = None) -> np.ndarray:
+        """embed_batch_sync from raw text (native_embedder.rs:172-255): `[CLS] pieces [SEP]`, truncated to `max_length` (None: the
+        tokenizer file's truncation, 0: none), tokenised on the device; the forward reads the ids where they lie and gives the
+        bits embed_flat gives for the same ids.  A text the device tokenizer leaves to the host raises with `.bad_text` set to its
+        index; nothing is written."""
+        flat, offsets = _text_arrays(texts)
+        n = offsets.shape[0] - 1
+        if out is None:
+            out = np.empty((n, self._dim), dtype=np.float32)
+        _call_with_bad_text(_lib.lib().fsgpu_bert_embed_texts, self._h, tokenizer._h, flat.ctypes.data, offsets.ctypes.data, n,
+                            tokenizer.max_length if max_length is None else int(max_length), out.ctypes.data)
+        return out
+
+    def embed_texts_device(self, tokenizer: "WordPieceTokenizer", texts: Sequence[str], out_ptr: int, max_length=None) -> None:
+        """... into [n, hidden] f32 of the embedder's device."""
+        flat, offsets = _text_arrays(texts)
+        _call_with_bad_text(_lib.lib().fsgpu_bert_embed_texts_device, self._h, tokenizer._h, flat.ctypes.data, offsets.ctypes.data,
+                            offsets.shape[0] - 1, tokenizer.max_length if max_length is None else int(max_length), out_ptr)
+
     def set_coalescing(self, max_batch: int, max_wait_us: int = 200) -> None:
         check(_lib.lib().fsgpu_bert_set_coalescing(self._h, max_batch, max_wait_us))
 
@@ -326,6 +364,326 @@ class HashEmbedder:
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
             _lib.lib().fsgpu_hash_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _call_with_bad_text(fn, *args):
+    """A C call whose last argument is out_bad_text: a refusal raises with `.bad_text` = the text's index in the call, or None."""
+    from .errors import SearchError
+    bad = C.c_uint32(0xFFFFFFFF)
+    try:
+        check(fn(*args, C.byref(bad)))
+    except SearchError as e:
+        e.bad_text = None if bad.value == 0xFFFFFFFF else int(bad.value)
+        raise
+
+
+# fsgpu_wordpiece_config.cp_info (include/fsgpu.h)
+WP_CODE_POINTS = 0x110000
+WP_VALUE_MASK = 0x1FFFFF
+WP_LEN_SHIFT = 21
+WP_SPACE = 1 << 24
+WP_ISOLATE = 1 << 25
+WP_HOST = 1 << 26
+
+_CP_TABLES = {}
+
+
+def bert_codepoint_table(lowercase: bool = True, strip_accents=None, handle_chinese_chars: bool = True, clean_text: bool = True):
+    """(cp_info uint32[0x110000], expansions uint32[...]) of fsgpu_wordpiece_create, made by driving `tokenizers`' own
+    BertNormalizer and BertPreTokenizer once per code point, so the table carries whatever Unicode data that library was built
+    with.  The only place `tokenizers` is needed; a few seconds, cached per option set.
+
+    An entry is the normalizer's output for the code point alone.  ' X ' (the padding of handle_chinese_chars) is X as a word on
+    its own.  HOST: an output of more than 3 code points, an output of 2..3 that holds a separator or a word on its own, and any
+    surviving code point with a non-zero combining class (NFD may reorder it against its neighbours, which no per-code-point
+    table can express)."""
+    key = (bool(lowercase), strip_accents, bool(handle_chinese_chars), bool(clean_text))
+    if key in _CP_TABLES:
+        return _CP_TABLES[key]
+    import unicodedata
+    from tokenizers.normalizers import BertNormalizer
+    from tokenizers.pre_tokenizers import BertPreTokenizer
+    norm = BertNormalizer(clean_text=clean_text, handle_chinese_chars=handle_chinese_chars, strip_accents=strip_accents,
+                          lowercase=lowercase)
+    pre = BertPreTokenizer()
+    outs = [""] * WP_CODE_POINTS
+    for c in range(WP_CODE_POINTS):
+        if not 0xD800 <= c <= 0xDFFF:   # (no text holds a surrogate)
+            outs[c] = norm.normalize_str(chr(c))
+    # the class of every normalised code point, from the pre-tokenizer itself: "x?x" stays whole, splits in two or in three
+    alphabet = sorted(set("".join(outs)))
+    klass = {}
+    for base in range(0, len(alphabet), 4096):
+        chunk = alphabet[base:base + 4096]
+        toks = [t for t, _ in pre.pre_tokenize_str(" ".join("x" + o + "x" for o in chunk))]
+        at = 0
+        for o in chunk:
+            if toks[at] == "x" + o + "x":
+                klass[o], at = 0, at + 1
+            elif toks[at] == "x" and toks[at + 1] == o and toks[at + 2] == "x":
+                klass[o], at = WP_ISOLATE, at + 3
+            elif toks[at] == "x" and toks[at + 1] == "x":
+                klass[o], at = WP_SPACE, at + 2
+            else:
+                raise RuntimeError(f"BertPreTokenizer treats U+{ord(o):04X} in a way the table cannot express")
+        if at != len(toks):
+            raise RuntimeError("BertPreTokenizer's pieces do not add up")
+    info = np.zeros(WP_CODE_POINTS, dtype=np.uint32)
+    expansions = []
+    memo = {}
+    for c in range(WP_CODE_POINTS):
+        out = outs[c]
+        if not out:
+            continue
+        entry = memo.get(out) if len(out) == 1 else None
+        if entry is None:
+            isolate = 0
+            o = out
+            if len(o) == 3 and o[0] == " " and o[2] == " " and klass[o[1]] != WP_SPACE:
+                o, isolate = o[1], WP_ISOLATE
+            if len(o) > 3 or any(unicodedata.combining(x) for x in o) or (len(o) > 1 and any(klass[x] for x in o)):
+                entry = WP_HOST
+            elif len(o) == 1:
+                entry = ord(o) | (1 << WP_LEN_SHIFT) | klass[o] | isolate
+                if entry & WP_SPACE:
+                    entry &= ~WP_ISOLATE
+            else:
+                entry = len(expansions) | (len(o) << WP_LEN_SHIFT)
+                expansions.extend(ord(x) for x in o)
+            if len(out) == 1:
+                memo[out] = entry
+        info[c] = entry
+    table = (info, np.asarray(expansions or [0], dtype=np.uint32)[:len(expansions)].copy())
+    _CP_TABLES[key] = table
+    return table
+
+
+class _WordPieceConfig(C.Structure):
+    _fields_ = [("vocab_bytes", C.c_void_p), ("vocab_offsets", C.c_void_p), ("vocab_size", C.c_uint32), ("unk_id", C.c_uint32),
+                ("cls_id", C.c_uint32), ("sep_id", C.c_uint32), ("prefix_bytes", C.c_void_p), ("prefix_len", C.c_uint32),
+                ("max_input_chars_per_word", C.c_uint32), ("cp_info", C.c_void_p), ("expansions", C.c_void_p),
+                ("expansions_len", C.c_uint32), ("added_bytes", C.c_void_p), ("added_offsets", C.c_void_p),
+                ("added_count", C.c_uint32), ("reserved", C.c_uint32 * 8)]
+
+
+def _blob(items):
+    """Byte strings -> (uint8 blob, uint32 offsets [len + 1]) of the C ABI."""
+    raw = [x if isinstance(x, (bytes, bytearray)) else str(x).encode("utf-8") for x in items]
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint32)
+    if raw:
+        offsets[1:] = np.cumsum([len(b) for b in raw], dtype=np.uint64).astype(np.uint32)
+    return np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8).copy(), offsets
+
+
+class WordPieceTokenizer:
+    """The BERT WordPiece tokenizer on the device (fsgpu_wordpiece_*): BertNormalizer -> BertPreTokenizer ->
+    WordPiece -> [CLS] ... [SEP], ids equal to `tokenizers`' for the same tokenizer.json.  `vocab` is the tokens in id order;
+    `cp_info` / `expansions` are the per-code-point table (bert_codepoint_table); `added` the added tokens' contents.  A text
+    that holds an added token's content or a code point the table marks HOST is flagged (status 1, no ids): it is the host
+    tokenizer's.  Padding, offsets, word ids and token strings are not produced."""
+
+    def __init__(self, vocab, unk_id: int, cls_id: int, sep_id: int, cp_info, expansions, added=(), prefix="##",
+                 max_input_chars_per_word: int = 100, device: int = 0, max_length: int = 0, reserved=None):
+        self.vocab_bytes, self.vocab_offsets = _blob(vocab)
+        self.added_bytes, self.added_offsets = _blob(added)
+        self.prefix = prefix if isinstance(prefix, (bytes, bytearray)) else str(prefix).encode("utf-8")
+        self.cp_info = np.ascontiguousarray(cp_info, dtype=np.uint32).reshape(-1)
+        if self.cp_info.size != WP_CODE_POINTS:
+            raise ValueError(f"cp_info must hold {WP_CODE_POINTS} entries")
+        self.expansions = np.ascontiguousarray(expansions, dtype=np.uint32).reshape(-1)
+        self.unk_id, self.cls_id, self.sep_id = int(unk_id), int(cls_id), int(sep_id)
+        self.max_input_chars_per_word = int(max_input_chars_per_word)
+        self.max_length = int(max_length)   # the file's truncation, the default of encode / encode_pairs (0: none)
+        self.device = device
+        prefix_arr = np.frombuffer(self.prefix or b"\0", dtype=np.uint8).copy()
+        cfg = _WordPieceConfig(self.vocab_bytes.ctypes.data, self.vocab_offsets.ctypes.data, len(self.vocab_offsets) - 1, self.unk_id,
+                               self.cls_id, self.sep_id, prefix_arr.ctypes.data, len(self.prefix), self.max_input_chars_per_word,
+                               self.cp_info.ctypes.data, self.expansions.ctypes.data if self.expansions.size else None,
+                               self.expansions.size, self.added_bytes.ctypes.data, self.added_offsets.ctypes.data,
+                               len(self.added_offsets) - 1)
+        for i, r in enumerate(reserved or ()):
+            cfg.reserved[i] = r
+        h = C.c_void_p()
+        check(_lib.lib().fsgpu_wordpiece_create(device, C.byref(cfg), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def parse_tokenizer_json(path_or_str) -> dict:
+        """The keyword arguments of the constructor (without the code-point table, whose options come back under "normalizer")
+        from a tokenizer.json, read with the `json` module.  Anything but BertNormalizer -> BertPreTokenizer -> WordPiece ->
+        [CLS] A [SEP] / [CLS] A [SEP] B [SEP], truncated longest_first from the right without stride, is refused."""
+        import json
+        import os
+        text = path_or_str
+        if isinstance(text, (bytes, bytearray)):
+            text = text.decode("utf-8")
+        if not text.lstrip().startswith("{"):
+            with open(os.fspath(path_or_str), encoding="utf-8") as f:
+                text = f.read()
+        doc = json.loads(text)
+
+        def refuse(why):
+            raise ValueError(f"tokenizer.json is not the BERT WordPiece pipeline the device tokenizer serves: {why}")
+
+        model = doc.get("model") or {}
+        kind = model.get("type") or ("BPE" if "merges" in model else "WordPiece" if "continuing_subword_prefix" in model else "?")
+        if kind != "WordPiece":
+            refuse(f"model type {kind}")
+        norm = doc.get("normalizer") or {}
+        if norm.get("type") != "BertNormalizer":
+            refuse(f"normalizer {norm.get('type')}")
+        if (doc.get("pre_tokenizer") or {}).get("type") != "BertPreTokenizer":
+            refuse(f"pre-tokenizer {(doc.get('pre_tokenizer') or {}).get('type')}")
+        trunc = doc.get("truncation")
+        max_length = 0
+        if trunc:
+            squash = lambda s: str(s).replace("_", "").lower()
+            if squash(trunc.get("strategy", "LongestFirst")) != "longestfirst":
+                refuse(f"truncation strategy {trunc.get('strategy')}")
+            if squash(trunc.get("direction", "Right")) != "right":
+                refuse(f"truncation direction {trunc.get('direction')}")
+            if trunc.get("stride", 0) != 0:
+                refuse(f"truncation stride {trunc.get('stride')}")
+            max_length = int(trunc["max_length"])
+        vocab_map = model.get("vocab") or {}
+        vocab = [None] * len(vocab_map)
+        for tok, i in vocab_map.items():
+            if not 0 <= i < len(vocab) or vocab[i] is not None:
+                refuse("the vocabulary's ids are not 0..n-1")
+            vocab[i] = tok
+        unk = model.get("unk_token", "[UNK]")
+        if unk not in vocab_map:
+            refuse(f"the unknown token {unk!r} is not in the vocabulary")
+        post = doc.get("post_processor")
+        if post is None:
+            cls_tok, sep_tok = "[CLS]", "[SEP]"
+        elif post.get("type") == "BertProcessing":
+            cls_tok, sep_tok = post["cls"][0], post["sep"][0]
+        elif post.get("type") == "TemplateProcessing":
+            shape = lambda seq: [("S", p["SpecialToken"]["id"], p["SpecialToken"]["type_id"]) if "SpecialToken" in p
+                                 else ("Q", p["Sequence"]["id"], p["Sequence"]["type_id"]) for p in seq]
+            single, pair = shape(post.get("single", [])), shape(post.get("pair", []))
+            if len(single) != 3 or [k for k, _, _ in single] != ["S", "Q", "S"] or [t for _, _, t in single] != [0, 0, 0]:
+                refuse("the single-sequence template is not [CLS] $A [SEP]")
+            cls_tok, sep_tok = single[0][1], single[2][1]
+            if pair != [("S", cls_tok, 0), ("Q", "A", 0), ("S", sep_tok, 0), ("Q", "B", 1), ("S", sep_tok, 1)]:
+                refuse("the pair template is not [CLS] $A [SEP] $B:1 [SEP]:1")
+            for tok in (cls_tok, sep_tok):
+                if post["special_tokens"][tok]["ids"] != [vocab_map.get(tok)]:
+                    refuse(f"the template's {tok} is not the vocabulary's")
+        else:
+            refuse(f"post-processor {post.get('type')}")
+        for tok in (cls_tok, sep_tok):
+            if tok not in vocab_map:
+                refuse(f"{tok!r} is not in the vocabulary")
+        added = []
+        for a in doc.get("added_tokens") or []:
+            if a.get("normalized"):
+                refuse(f"added token {a.get('content')!r} is matched against normalised text")
+            added.append(a["content"])
+        return {"vocab": vocab, "unk_id": vocab_map[unk], "cls_id": vocab_map[cls_tok], "sep_id": vocab_map[sep_tok], "added": added,
+                "prefix": model.get("continuing_subword_prefix", "##"),
+                "max_input_chars_per_word": int(model.get("max_input_chars_per_word", 100)), "max_length": max_length,
+                "normalizer": {"lowercase": norm.get("lowercase", True), "strip_accents": norm.get("strip_accents"),
+                               "handle_chinese_chars": norm.get("handle_chinese_chars", True),
+                               "clean_text": norm.get("clean_text", True)}}
+
+    @classmethod
+    def from_tokenizer_json(cls, path_or_str, device: int = 0, table=None) -> "WordPieceTokenizer":
+        """From a tokenizer.json (a path or the text itself).  `table` = (cp_info, expansions); without one it is built from
+        `tokenizers` with the file's normalizer options (bert_codepoint_table)."""
+        kw = cls.parse_tokenizer_json(path_or_str)
+        options = kw.pop("normalizer")
+        cp_info, expansions = table if table is not None else bert_codepoint_table(**options)
+        return cls(cp_info=cp_info, expansions=expansions, device=device, **kw)
+
+    def vocab_size(self) -> int:
+        return int(_lib.lib().fsgpu_wordpiece_vocab_size(self._h))
+
+    def _length(self, max_length):
+        return self.max_length if max_length is None else int(max_length)
+
+    def encode_flat(self, flat: np.ndarray, offsets: np.ndarray, add_special_tokens: bool = True, max_length=None, capacity=None):
+        """fsgpu_wordpiece_encode on arrays in the C ABI's shape -> (ids uint32, offsets uint32 [n + 1], status uint8 [n]).
+        `capacity` (ids the output may hold) defaults to a bound no text can pass: its bytes plus the two special tokens."""
+        n = offsets.shape[0] - 1
+        if capacity is None:
+            capacity = int(offsets[-1]) - int(offsets[0]) + 2 * n if n else 0
+        ids = np.zeros(max(capacity, 1), dtype=np.uint32)
+        out_offsets = np.zeros(n + 1, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.uint8)
+        total = C.c_uint64(0)
+        self.last_total = None
+        try:
+            _call_with_bad_text(_lib.lib().fsgpu_wordpiece_encode, self._h, flat.ctypes.data, offsets.ctypes.data, n,
+                                1 if add_special_tokens else 0, self._length(max_length), ids.ctypes.data, capacity,
+                                out_offsets.ctypes.data, status.ctypes.data, C.byref(total))
+        finally:
+            self.last_total = int(total.value)
+        return ids[:total.value], out_offsets, status
+
+    def encode(self, texts: Sequence[str], add_special_tokens: bool = True, max_length=None):
+        """Tokenizer.encode_batch(texts).ids as a CSR: (ids, offsets [n + 1], status [n]); status 1 = left to the host, no ids."""
+        flat, offsets = _text_arrays(texts)
+        return self.encode_flat(flat, offsets, add_special_tokens, max_length)
+
+    def encode_device(self, texts: Sequence[str], ids_ptr: int, capacity: int, offsets_ptr: int, add_special_tokens: bool = True,
+                      max_length=None):
+        """... with ids [capacity] and offsets [n + 1] (uint32) left in memory of the tokenizer's device -> (status, total)."""
+        flat, offsets = _text_arrays(texts)
+        n = offsets.shape[0] - 1
+        status = np.zeros(n, dtype=np.uint8)
+        total = C.c_uint64(0)
+        _call_with_bad_text(_lib.lib().fsgpu_wordpiece_encode_device, self._h, flat.ctypes.data, offsets.ctypes.data, n,
+                            1 if add_special_tokens else 0, self._length(max_length), ids_ptr, capacity, offsets_ptr,
+                            status.ctypes.data, C.byref(total))
+        return status, int(total.value)
+
+    def encode_pairs(self, a_texts: Sequence[str], b_texts: Sequence[str], max_length=None, capacity=None):
+        """Tokenizer.encode_batch(list(zip(a, b))) -> (ids, type_ids, offsets [n + 1], status [n]): [CLS] a [SEP] b [SEP]."""
+        if len(a_texts) != len(b_texts):
+            raise ValueError("a_texts and b_texts must pair up")
+        a_flat, a_off = _text_arrays(a_texts)
+        b_flat, b_off = _text_arrays(b_texts)
+        n = a_off.shape[0] - 1
+        if capacity is None:
+            capacity = int(a_off[-1]) + int(b_off[-1]) + 3 * n
+        ids = np.zeros(max(capacity, 1), dtype=np.uint32)
+        types = np.zeros(max(capacity, 1), dtype=np.uint32)
+        out_offsets = np.zeros(n + 1, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.uint8)
+        total = C.c_uint64(0)
+        self.last_total = None
+        try:
+            _call_with_bad_text(_lib.lib().fsgpu_wordpiece_encode_pairs, self._h, a_flat.ctypes.data, a_off.ctypes.data,
+                                b_flat.ctypes.data, b_off.ctypes.data, n, self._length(max_length), ids.ctypes.data, types.ctypes.data,
+                                capacity, out_offsets.ctypes.data, status.ctypes.data, C.byref(total))
+        finally:
+            self.last_total = int(total.value)
+        return ids[:total.value], types[:total.value], out_offsets, status
+
+    def encode_pairs_device(self, a_texts: Sequence[str], b_texts: Sequence[str], ids_ptr: int, type_ids_ptr: int, capacity: int,
+                            offsets_ptr: int, max_length=None):
+        a_flat, a_off = _text_arrays(a_texts)
+        b_flat, b_off = _text_arrays(b_texts)
+        n = a_off.shape[0] - 1
+        status = np.zeros(n, dtype=np.uint8)
+        total = C.c_uint64(0)
+        _call_with_bad_text(_lib.lib().fsgpu_wordpiece_encode_pairs_device, self._h, a_flat.ctypes.data, a_off.ctypes.data,
+                            b_flat.ctypes.data, b_off.ctypes.data, n, self._length(max_length), ids_ptr, type_ids_ptr, capacity,
+                            offsets_ptr, status.ctypes.data, C.byref(total))
+        return status, int(total.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().fsgpu_wordpiece_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

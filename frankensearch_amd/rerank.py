@@ -141,6 +141,23 @@ class NativeReranker:
                                               logits.ctypes.data, scores.ctypes.data))
         return logits, scores
 
+    def score_texts(self, tokenizer, query: str, docs: Sequence[str], max_length: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(logits, scores) [n] of `[CLS] query [SEP] doc [SEP]` from raw text (native.rs:1652-1666): tokenised and truncated
+        (longest_first to `max_length`; None: the tokenizer file's truncation, 0: none) on the device by `tokenizer`, a
+        WordPieceTokenizer, and scored over the ids where they lie.  A flagged query or document raises with `.bad_text` set to the
+        pair's index; nothing is scored."""
+        from .embed import _call_with_bad_text, _text_arrays
+        q = query if isinstance(query, (bytes, bytearray)) else str(query).encode("utf-8", "surrogatepass")
+        qa = np.frombuffer(bytes(q) or b"\0", dtype=np.uint8)
+        flat, offsets = _text_arrays(docs)
+        n = offsets.shape[0] - 1
+        logits = np.zeros(n, dtype=np.float32)
+        scores = np.zeros(n, dtype=np.float32)
+        _call_with_bad_text(_lib.lib().fsgpu_reranker_score_texts, self._h, tokenizer._h, qa.ctypes.data, len(q), flat.ctypes.data,
+                            offsets.ctypes.data, n, tokenizer.max_length if max_length is None else int(max_length),
+                            logits.ctypes.data, scores.ctypes.data)
+        return logits, scores
+
     def rerank_token_ids(self, pairs: Sequence[Tuple[Sequence[int], Sequence[int]]], doc_ids: Sequence[str]) -> List[RerankScore]:
         """rerank_sync (native.rs:1636-1710) over pre-tokenised pairs: one RerankScore per document, in input order."""
         if len(pairs) != len(doc_ids):

@@ -70,6 +70,7 @@ typedef int32_t fsgpu_status;
 typedef struct fsgpu_index fsgpu_index;     /* device-resident VectorIndex (lib.rs:819) */
 typedef struct fsgpu_m2v fsgpu_m2v;         /* Model2VecEmbedder (embed/src/model2vec_embedder.rs:55) */
 typedef struct fsgpu_hash fsgpu_hash;       /* HashEmbedder (embed/src/hash_embedder.rs:201) */
+typedef struct fsgpu_wordpiece fsgpu_wordpiece; /* the BERT WordPiece tokenizer (third-party `tokenizers` in the reference) */
 typedef struct fsgpu_bert fsgpu_bert;       /* NativeEmbedder (rerank/src/native_embedder.rs:40-50) */
 typedef struct fsgpu_reranker fsgpu_reranker; /* NativeReranker, the cross-encoder (rerank/src/native.rs:1240) */
 
@@ -661,6 +662,122 @@ fsgpu_status fsgpu_hash_embed(fsgpu_hash *h, const uint8_t *text_bytes, const ui
  * fsgpu_search_topk_batched_device_queries and fsgpu_index_builder_add_device take it. */
 fsgpu_status fsgpu_hash_embed_device(fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n, float *out_dev,
                                      uint32_t *out_token_counts_or_null, uint32_t *out_bad_text);
+
+/* ---- WordPiece tokenizer: raw text -> token ids on the device ---- */
+/* The pipeline potion-base, all-MiniLM-L6-v2 and the ms-marco MiniLM cross-encoder ship in tokenizer.json: BertNormalizer ->
+ * BertPreTokenizer -> WordPiece(continuing prefix, unk, max_input_chars_per_word) -> [CLS] ... [SEP].  The ids equal those of the
+ * `tokenizers` crate for the same file, with no tolerance.  Everything that depends on Unicode tables or on the normalizer's
+ * options (lowercase, strip_accents, handle_chinese_chars, clean_text) is the CALLER's table, made from the toolchain the caller
+ * links; the device has no switch for any of them.
+ *
+ * cp_info[c] for input code point c (0 <= c < 0x110000):
+ *   bits  0..20  FSGPU_WP_VALUE   len 1: the normalised code point; len 2..3: index of the first of `len` consecutive code
+ *                                 points in `expansions`; len 0: ignored
+ *   bits 21..23  FSGPU_WP_LEN     normalised length 0..3 (0 = the code point is dropped; above 3 is refused)
+ *   bit  24      FSGPU_WP_SPACE   the (single) normalised code point separates words and belongs to none
+ *   bit  25      FSGPU_WP_ISOLATE the (single) normalised code point is a word on its own (punctuation; a CJK character when the
+ *                                 normalizer pads those with spaces)
+ *   bit  26      FSGPU_WP_HOST    a text holding c cannot be tokenised here (see status below)
+ *   bits 27..31  must be 0
+ * SPACE and ISOLATE describe an entry of length 1; an entry of length 2..3 that would need either is given HOST by its maker.  An
+ * entry whose `len` exceeds the UTF-8 length of c (1 for c < 0x80, 2 below 0x800, else 3) is treated as HOST: it keeps a text's
+ * normalised length, and so its pieces, at or below its byte length.
+ *
+ * vocab_bytes / vocab_offsets[vocab_size + 1]: the tokens' UTF-8 bytes back to back, a token's id is its index.  prefix_bytes is
+ * the continuing-subword prefix ("##", at most 16 bytes).  added_bytes / added_offsets[added_count + 1]: the contents of the added
+ * tokens ("[CLS]", "[SEP]", "[PAD]", "[UNK]", "[MASK]", ...), at most 32 of 1..32 bytes each: `tokenizers` takes these out of the
+ * raw text before it normalises, so a text that holds one is flagged, not tokenised.
+ * FSGPU_ERR_INVALID_CONFIG, decided before a device is looked for: offsets that decrease (vocabulary or added tokens) or do not
+ * start at 0, an empty vocabulary, unk_id / cls_id / sep_id >= vocab_size, two equal vocabulary entries, an expansion index out
+ * of range, a length above 3, bits 27..31 set, a non-zero reserved word, max_input_chars_per_word 0 or above 1,024, a prefix over
+ * 16 bytes, more than 32 added tokens, an added token of 0 or more than 32 bytes.  Then no device is FSGPU_ERR_NO_DEVICE. */
+#define FSGPU_WP_CODE_POINTS 0x110000u
+#define FSGPU_WP_VALUE_MASK 0x1FFFFFu
+#define FSGPU_WP_LEN_SHIFT 21
+#define FSGPU_WP_LEN_MASK 7u
+#define FSGPU_WP_SPACE (1u << 24)
+#define FSGPU_WP_ISOLATE (1u << 25)
+#define FSGPU_WP_HOST (1u << 26)
+typedef struct fsgpu_wordpiece_config {
+    const uint8_t *vocab_bytes;
+    const uint32_t *vocab_offsets; /* [vocab_size + 1] */
+    uint32_t vocab_size;
+    uint32_t unk_id, cls_id, sep_id;
+    const uint8_t *prefix_bytes;
+    uint32_t prefix_len;
+    uint32_t max_input_chars_per_word; /* 100 in the three models' files */
+    const uint32_t *cp_info;           /* [FSGPU_WP_CODE_POINTS] */
+    const uint32_t *expansions;        /* [expansions_len] code points, may be NULL when expansions_len is 0 */
+    uint32_t expansions_len;
+    const uint8_t *added_bytes;
+    const uint32_t *added_offsets;     /* [added_count + 1], may be NULL when added_count is 0 */
+    uint32_t added_count;
+    uint32_t reserved[8];              /* must be 0 */
+} fsgpu_wordpiece_config;
+fsgpu_status fsgpu_wordpiece_create(int32_t device, const fsgpu_wordpiece_config *config, fsgpu_wordpiece **out);
+void fsgpu_wordpiece_destroy(fsgpu_wordpiece *tok);
+int32_t fsgpu_wordpiece_device(const fsgpu_wordpiece *tok);
+uint32_t fsgpu_wordpiece_vocab_size(const fsgpu_wordpiece *tok);
+/* Tokenizer::encode_batch over single sequences, ids only.  Text i owns text_bytes[offsets[i]..offsets[i+1]), as in
+ * fsgpu_hash_embed.  add_special_tokens != 0: [CLS] pieces [SEP].  max_length 0: no truncation; otherwise (truncation strategy
+ * longest_first, direction right, stride 0) the first max_length - 2 * add_special pieces are kept; a max_length below the
+ * special tokens' count is FSGPU_ERR_INVALID_CONFIG.  Output is a dense CSR: text i owns out_ids[out_offsets[i]..out_offsets[i+1]).
+ *   out_status[i] 0: tokenised.  1: the text holds an added token's content or a HOST code point; it gets zero ids (no specials
+ *     either), the other texts are unaffected and the call succeeds: such a text is the host tokenizer's.
+ *   *out_total (nullable) = ids the batch needs.  ids_capacity below that: FSGPU_ERR_INVALID_CONFIG, *out_total set, nothing else
+ *     written.
+ *   Refused with FSGPU_ERR_INVALID_CONFIG, *out_bad_text (nullable) = the first such text, nothing launched and nothing written:
+ *     a text that is not strict UTF-8 or is longer than 32 MiB; decreasing offsets are refused too.  Otherwise *out_bad_text is
+ *     0xFFFFFFFF. */
+fsgpu_status fsgpu_wordpiece_encode(fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n,
+                                    int32_t add_special_tokens, uint32_t max_length, uint32_t *out_ids, uint64_t ids_capacity,
+                                    uint32_t *out_offsets, uint8_t *out_status, uint64_t *out_total, uint32_t *out_bad_text);
+/* ... with out_ids_dev [ids_capacity] and out_offsets_dev [n + 1] left in memory of the tokenizer's device (the shape
+ * fsgpu_m2v_embed takes, without the trip); out_status and out_total stay on the host. */
+fsgpu_status fsgpu_wordpiece_encode_device(fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n,
+                                           int32_t add_special_tokens, uint32_t max_length, uint32_t *out_ids_dev,
+                                           uint64_t ids_capacity, uint32_t *out_offsets_dev, uint8_t *out_status,
+                                           uint64_t *out_total, uint32_t *out_bad_text);
+/* Tokenizer::encode_batch over pairs with special tokens: [CLS] a [SEP] (type 0) b [SEP] (type 1); out_type_ids parallels
+ * out_ids.  max_length 0: no truncation; otherwise it is at least 3 and, with B = max_length - 3 and (la, lb) the pieces of a and
+ * b, longest_first keeps: both when la + lb <= B; otherwise, with n1 <= n2 the two lengths sorted, n2 = n1 when n1 > B, else
+ * max(n1, B - n1); when n1 + n2 still exceeds B, n1 = B / 2 and n2 = n1 + B % 2; the sort is then undone.  A pair is flagged
+ * (status 1, zero ids) when either text is.  *out_bad_text names the pair whose a or b text is refused. */
+fsgpu_status fsgpu_wordpiece_encode_pairs(fsgpu_wordpiece *tok, const uint8_t *a_bytes, const uint32_t *a_offsets,
+                                          const uint8_t *b_bytes, const uint32_t *b_offsets, uint32_t n, uint32_t max_length,
+                                          uint32_t *out_ids, uint32_t *out_type_ids, uint64_t ids_capacity, uint32_t *out_offsets,
+                                          uint8_t *out_status, uint64_t *out_total, uint32_t *out_bad_text);
+fsgpu_status fsgpu_wordpiece_encode_pairs_device(fsgpu_wordpiece *tok, const uint8_t *a_bytes, const uint32_t *a_offsets,
+                                                 const uint8_t *b_bytes, const uint32_t *b_offsets, uint32_t n,
+                                                 uint32_t max_length, uint32_t *out_ids_dev, uint32_t *out_type_ids_dev,
+                                                 uint64_t ids_capacity, uint32_t *out_offsets_dev, uint8_t *out_status,
+                                                 uint64_t *out_total, uint32_t *out_bad_text);
+/* Model2VecEmbedder::embed_batch_sync from raw text (model2vec_embedder.rs:280-335: encode_fast(text, false), no special tokens,
+ * no truncation): the texts are tokenised on the device and fsgpu_m2v_embed's kernel reads the ids where they lie; no id crosses
+ * to the host.  tok and m must be on one device (else FSGPU_ERR_INVALID_CONFIG).  A flagged text is refused:
+ * FSGPU_ERR_INVALID_CONFIG, *out_bad_text (nullable) = its index, the encoder is not run and out is not written. */
+fsgpu_status fsgpu_m2v_embed_texts(fsgpu_m2v *m, fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets,
+                                   uint32_t n, float *out, uint32_t *out_bad_text);
+/* ... with the [n, dim] output left on the device. */
+fsgpu_status fsgpu_m2v_embed_texts_device(fsgpu_m2v *m, fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets,
+                                          uint32_t n, float *out_dev, uint32_t *out_bad_text);
+/* NativeEmbedder::embed_batch_sync from raw text (native_embedder.rs:172-255): [CLS] pieces [SEP], truncated to max_length (0: not
+ * truncated; a text then longer than the model's positions fails as in fsgpu_bert_embed), tokenised on the device; the forward
+ * reads the ids where the tokenizer left them and gives the bits fsgpu_bert_embed gives for the same ids.  Only the n + 1 offsets
+ * come back to the host, where the launches are planned.  tok and m on one device and the tokenizer's vocabulary no larger than the
+ * model's, else FSGPU_ERR_INVALID_CONFIG.  A flagged text is refused as in fsgpu_m2v_embed_texts.  (Calls are not coalesced.) */
+fsgpu_status fsgpu_bert_embed_texts(fsgpu_bert *m, fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets,
+                                    uint32_t n, uint32_t max_length, float *out, uint32_t *out_bad_text);
+fsgpu_status fsgpu_bert_embed_texts_device(fsgpu_bert *m, fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets,
+                                           uint32_t n, uint32_t max_length, float *out_dev, uint32_t *out_bad_text);
+/* NativeReranker::rerank_sync's scoring from raw text (native.rs:1636-1710): pair i is [CLS] query [SEP] document i [SEP],
+ * tokenised and truncated (longest_first to max_length, 0: not truncated) on the device as fsgpu_wordpiece_encode_pairs does; the
+ * chain reads ids and type ids where the tokenizer left them and gives the logits and scores fsgpu_reranker_score gives for the
+ * same pairs.  Document i owns doc_bytes[doc_offsets[i]..doc_offsets[i+1]).  A flagged query or document is refused:
+ * FSGPU_ERR_INVALID_CONFIG, *out_bad_text (nullable) = the pair, nothing scored.  Device and vocabulary rules as above. */
+fsgpu_status fsgpu_reranker_score_texts(fsgpu_reranker *m, fsgpu_wordpiece *tok, const uint8_t *query_bytes, uint32_t query_len,
+                                        const uint8_t *doc_bytes, const uint32_t *doc_offsets, uint32_t n, uint32_t max_length,
+                                        float *out_logits, float *out_scores, uint32_t *out_bad_text);
 
 /* ---- MiniLM-class BERT embedder ---- */
 /* NativeEmbedder::load (native_embedder.rs:60-116): copies the weights to the GPU (linears as f16). */

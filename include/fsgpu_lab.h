@@ -250,6 +250,12 @@ fsgpu_status fsgpu_lab_device_copy_ms(int32_t device, uint64_t bytes, uint32_t r
  * out_stage_ms[3] = {texts and offsets to the device, the kernel, vectors back to `out`}. */
 fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash *h, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n, float *out,
                                            float *out_stage_ms);
+/* fsgpu_wordpiece_encode with the device's own time of its stages, between events on the tokenizer's stream (ms):
+ * out_stage_ms[3] = {texts, offsets and piece regions to the device; the tokenize and offsets kernels, the host's read of the
+ * total, the assemble kernel; ids and offsets back to the host}. */
+fsgpu_status fsgpu_lab_wordpiece_encode_stage_ms(fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n,
+                                                 int32_t add_special_tokens, uint32_t max_length, uint32_t *out_ids,
+                                                 uint64_t ids_capacity, uint32_t *out_offsets, float *out_stage_ms);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
