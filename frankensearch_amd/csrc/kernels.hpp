@@ -253,6 +253,8 @@ bool scan_wide_supported(int dim, int elem_bytes);
 bool scan_wide_group_maxima_supported(int dim, int query_tiles);   // MfmaScanArgs::stage == 3 (int8 rows): see select_groups
 int scan_wide_max_query_tiles(int dim, int elem_bytes);  // 3 for f16 rows of 384 dimensions, 5 for their int8 form
 hipError_t launch_scan_wide(const MfmaScanArgs& args, int query_tiles, int grid, hipStream_t stream, int* occupancy);
+bool scan_wide_barrier_sync();    // FSGPU_WIDE_SYNC=barrier (knobs(), vector_index_batched.cpp): launch_scan_wide's 128-row main pass with a block barrier per tile
+uint32_t scan_wide_poll_timeouts();   // mfma_wide.hip: slot waits of the 128-row main pass that gave up (0 unless a wave stopped advancing); the debug census prints it
 bool scan_wide_flat_priority();   // FSGPU_WIDE_PRIO=off (knobs(), vector_index_batched.cpp): launch_scan_wide's split loop without priority levels
 void note_main_pass_kernel(const char* name);  // remembers the instantiation the last main pass ran (last_main_pass_kernel)
 const char* last_main_pass_kernel();  // template instantiation of the last batched main pass launched, as rocprofv3 names it

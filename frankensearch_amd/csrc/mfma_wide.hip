@@ -9,7 +9,8 @@
 //     no ds_write pass, no ds_bpermute transpose) in the coalesced quad layout of the exact kernels (four consecutive
 //     lanes fetch 64 contiguous bytes), several tiles ahead of the tile being consumed; every wave reads each row tile's
 //     A fragments with ds_read_b128 and multiplies them with its own queries.
-// One s_barrier per tile; the DMA queue is never drained inside the loop (counted s_waitcnt vmcnt).  The DMA and its
+// One s_barrier per tile — or, in the 128-row main pass, none: two counters per ring slot (kOptBarrier below); the DMA queue is
+// never drained inside the loop (counted s_waitcnt vmcnt).  The DMA and its
 // waits are inline asm: hipcc would otherwise wait for the newest LDS-DMA before every ds_read (it cannot tell the ring
 // slots apart), which serialises load and compute.
 //
@@ -113,23 +114,44 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// the arrive / wait counters of kOptFlags (LDS byte addresses; hipcc's s_waitcnt bookkeeping does not see these, so each waits itself)
-[[maybe_unused]] __device__ __forceinline__ void flag_post(uint32_t lds_addr, int lane) {
-    asm volatile("" ::: "memory");   // the wave's earlier LDS reads stay in front of the post (the LDS serves a wave's operations in order)
-    if (lane == 0) {
-        const uint32_t one = 1;
-        asm volatile("ds_add_u32 %0, %1" ::"v"(lds_addr), "v"(one) : "memory");
-    }
+// The arrive / wait counters of the slot-synchronised ring (one 32-bit word in LDS each).
+// slot_post: one ds_add_u32 from one lane, nothing returned, nothing waited for.  The LDS serves a wave's operations in order, so every
+// LDS read the wave issued before the post has been served when the post becomes visible.  The address is wave-uniform and arrives in a
+// scalar register; the two vector registers the instruction needs live only inside the statement (the tile loop has none to spare), and
+// the one lane is chosen by the exec mask, not by a compare on a lane number kept in a register.
+__device__ __forceinline__ void slot_post(uint32_t lds_addr) {
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
+    uint64_t keep;
+    uint32_t va, vone;
+    asm volatile(
+        "s_mov_b64 %0, exec\n\t"
+        "s_mov_b64 exec, 1\n\t"
+        "v_mov_b32 %1, %3\n\t"
+        "v_mov_b32 %2, 1\n\t"
+        "ds_add_u32 %1, %2\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(keep), "=&v"(va), "=&v"(vone)
+        : "s"(a)
+        : "memory");
 }
-[[maybe_unused]] __device__ __forceinline__ void flag_wait(uint32_t lds_addr, uint32_t target) {
-    for (;;) {
-        uint32_t v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds_addr) : "memory");
-        if ((uint32_t)__builtin_amdgcn_readfirstlane(v) >= target) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
+// slot_peek: the counter's ds_read_b32, a load hipcc SEES — it counts it among the wave's LDS reads in flight and puts the counted
+// s_waitcnt lgkmcnt(N) that the reads issued after it imply in front of the first use of the value (slot_reached), never lgkmcnt(0)
+// for its own sake.  Issued a k-step or two before the value is needed, the wait in front of the use finds it long returned.
+__device__ __forceinline__ uint32_t slot_peek(const uint32_t* counter) {
+    return __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+// (wave-uniform) v_readfirstlane + a scalar compare
+__device__ __forceinline__ bool slot_reached(uint32_t seen, uint32_t target) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)seen) >= target;
+}
+// A slot wait polls at most kSlotPollBound times.  The longest single wait the stamps show is 11,896 cycles (a 1.25M-row shard; 9,724 at
+// 10M rows: profiles/wide_slot_sync/slot_sync_ab.txt).  One poll is an LDS round trip + s_sleep 1, at least 64 cycles, so that wait is
+// at most 186 polls and 1,000 times it is 186,000 polls: the bound is 2^20 = 1,048,576 polls, 5.6 times that (some 0.05 s).  A wave
+// that exhausts it does not wait on: see slot_wait_slow in scan_wide_body.
+constexpr uint32_t kSlotPollBound = 1u << 20;
+constexpr uint32_t kSlotOpen = 0x40000000u;   // a counter no target reaches (targets: 8 per use of a slot, below 2^26 for 2^32 rows)
+// slot waits that gave up, over the life of the process (scan_wide_poll_timeouts; the debug census prints it: expected 0)
+__device__ unsigned int g_wide_poll_timeouts;
 
 }  // namespace
 
@@ -161,14 +183,17 @@ __device__ __forceinline__ void wait_vmcnt() {
 //   kOptBig    (with kOptSplit, main pass only) row tiles of 128 rows in a ring of THREE slots (the same 144 KB): half as many
 //              barriers, tile cursors and DMA bookkeeping per row; tile n is consumed while n+1 is landing and n-1's slot takes
 //              n+2 — one tile of lookahead is 4-5 us of matrix work, well past the HBM latency.
-//   kOptFlags  (with kOptBig) no block-wide s_barrier in the tile loop: two LDS counters per ring slot — `landed` (waves whose share
-//              of the tile's DMA is in LDS) and `freed` (waves past their last read of the tile) — are posted EARLY and waited for
-//              LATE.  A wave posts landed(n+1) at the start of tile n (its share went out a whole tile earlier) and needs
-//              everyone's only before it reads tile n+1's first fragments at the END of tile n; it posts freed(n) one sub-tile pair
-//              before the end of tile n and the refill of that slot waits for everyone's a few MFMAs into tile n+1.  The eight
-//              waves therefore drift up to about a tile apart instead of meeting at every tile: a wave held up in the append path
-//              (a scalar bitmap load, an LDS atomic, a store — ~5 events per tile at 10M rows, ~40 on a 1.25M-row shard) no longer
-//              stops the other seven, and the two waves of a SIMD no longer stop together.
+//              The 128-row loop has NO block-wide s_barrier: two LDS counters per ring slot — `landed` (waves whose share of the
+//              tile's DMA is in LDS) and `freed` (waves past their last read of the tile) — are posted EARLY and waited for LATE.
+//              A wave posts landed(n+1) at the start of tile n (its share went out a whole tile earlier) and needs everyone's only
+//              before it reads tile n+1's first fragments at the END of tile n; it posts freed(n) one sub-tile pair before the end
+//              of tile n and the refill of that slot waits for everyone's a few MFMAs into tile n+1.  The eight waves therefore
+//              drift up to about a tile apart instead of meeting at every tile: a wave held up in the append path no longer stops
+//              the other seven, and the two waves of a SIMD no longer stop together.  A wait is a counter read issued two k-steps
+//              ahead (slot_peek), a scalar compare and a branch that is not taken; only a count that is short polls, out of line
+//              and at most kSlotPollBound times.
+//   kOptBarrier (with kOptBig) the 128-row loop with one s_waitcnt vmcnt + s_barrier per tile instead of the slot counters: the loop
+//              as it was before them, instruction for instruction.  FSGPU_WIDE_SYNC=barrier launches these instantiations.
 //   kOptFlat   (with kOptSplit) the split loop WITHOUT its progress-ordered wave priority.  By default a wave of the split loop lowers
 //              its own priority (s_setprio) as it advances through a tile: level 3 at the tile's first sub-tile pair — where the
 //              tile's barrier stands — falling to 0 at its last.  Of a SIMD's two waves the one that is BEHIND then has the higher or
@@ -176,7 +201,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 //              both were ready, finished the tile early and parked at the barrier while its twin finished alone.  The levels are
 //              compile-time constants of the unrolled loop (no state, no communication); the append excursion runs at level 3 (a wave
 //              in it is the laggard by definition) and restores its place's level.  FSGPU_WIDE_PRIO=off launches these instantiations.
-constexpr int kOptNegTau = 2, kOptSaddr = 4, kOptSplit = 8, kOptBig = 16, kOptFlags = 32, kOptFlat = 64;
+constexpr int kOptNegTau = 2, kOptSaddr = 4, kOptSplit = 8, kOptBig = 16, kOptBarrier = 32, kOptFlat = 64;
 
 // The priority level of half-phase h of H (a tile's sub-tile pairs x the two query-tile halves of each): four levels spread evenly
 // over the tile — one per pair of a 128-row tile, one per half-phase of a 64-row tile.  (Measured against it on the bench shape,
@@ -280,7 +305,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     constexpr int WPB = WPBT, NT = WPB * 64;   // (16 waves of two query tiles — four per SIMD, 128 registers each — spilled in the loop: 4.23 against 2.64 ms)
     constexpr int KS = ROWB / 64;                                   // MFMA k-steps (64 bytes of a row each)
     constexpr bool BIG = wide_big_ok(ROWB, EB, QT, NSLOT, OPT, DBG);
-    constexpr bool FLAGS = BIG && (OPT & kOptFlags) != 0;
+    constexpr bool SLOTSYNC = BIG && (OPT & kOptBarrier) == 0;     // per-slot counters instead of the tile's barrier
     constexpr int TR = BIG ? 128 : ROWB >= 512 ? 32 : 64;           // rows per tile
     constexpr int RS = TR / 16;                                     // 16-row sub-tiles per tile
     constexpr int NI = RS * KS;                                     // DMA instructions per tile (1 KB each)
@@ -315,7 +340,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     // tile loop, the cycles between arriving at a tile's wait + barrier and leaving it, the cycles inside the append path and its
     // entries; written to args.dense as [block][wave][4] 64-bit words.  Answers stay valid; the stamps cost a few percent.
     constexpr bool STAMPS = DBG == 8;
-    [[maybe_unused]] unsigned long long st_loop = 0, st_bar = 0;
+    [[maybe_unused]] unsigned long long st_loop = 0, st_bar = 0, st_max = 0;   // (st_max: the longest single wait)
     static_assert(!SPLIT || (NEGTAU && RS >= 4), "the split loop runs on neg-tau accumulators over tiles of two pairs or more");
     // -ceil(tau) kept in all four registers of an accumulator (the first MFMA of a pair takes it as C: no initialising moves) where
     // 4 x QT more registers fit; else one register per query tile and four moves per accumulator (in the MFMAs' shadow when SPLIT)
@@ -343,14 +368,16 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const uint32_t ring = (uint32_t)(uintptr_t)smem;                // LDS byte address of the ring (low half of the flat address)
     int* lcnt = reinterpret_cast<int*>(smem + (size_t)NSLOT * TILE_BYTES);   // entries appended per query by this block
-    // kOptFlags: landed[slot] at flags + 4 slot, freed[slot] at flags + 16 + 4 slot (counts of waves, monotonic: 8 per use of the slot)
+    // SLOTSYNC: landed[slot] = sync[slot] (LDS byte address flags + 4 slot), freed[slot] = sync[4 + slot] (flags + 16 + 4 slot) — counts
+    // of waves, monotonic: 8 per use of the slot
     const uint32_t flags = ring + (uint32_t)(NSLOT * TILE_BYTES + NQ * 4);
+    uint32_t* const sync = reinterpret_cast<uint32_t*>(lcnt + NQ);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int frow = lane & 15, fk = lane >> 4;
     const int slots = (int)args.slots;
     for (int i = tid; i < NQ; i += NT) lcnt[i] = 0;
-    if (FLAGS && tid < 8) lcnt[NQ + tid] = 0;
+    if (SLOTSYNC && tid < 8) sync[tid] = 0;
     if (STAMPS && tid < 32) lcnt[NQ + 16 + tid] = 0;
 
     // this wave's queries: B fragments for the whole dimension, resident in registers
@@ -696,6 +723,34 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
         if (__builtin_expect(wave_any(any_passes(acc, 0, QT)), 0)) emit_tiles(t, sp, acc, 0, QT, 0);
     };
 
+    // SLOTSYNC: the out-of-line half of a slot wait — counter sync[idx] was short of `target` when the wave peeked at it.  The poll is
+    // bounded: a wave must never be able to wait forever.  One that exhausts the bound reports every query of its block's group as
+    // overflowed (the exact path answers them: whatever this block appends from here on is not trusted), counts the event, opens all
+    // of the block's counters so that neither it nor the block's other waves wait again, and proceeds.
+    [[maybe_unused]] auto slot_wait_slow = [&](uint32_t idx, uint32_t target) {
+        [[maybe_unused]] unsigned long long st_a = 0;
+        if constexpr (STAMPS) st_a = __builtin_readcyclecounter();
+        for (uint32_t polls = 0; !slot_reached(slot_peek(sync + idx), target);) {
+            if (__builtin_expect(++polls > kSlotPollBound, 0)) {
+                // (the lane number is made opaque HERE: hipcc otherwise computes the addresses below in front of the tile loop and
+                // keeps them in registers across it, which has none to spare)
+                uint32_t lane_v = threadIdx.x;
+                asm volatile("" : "+v"(lane_v));
+                lane_v &= 63u;
+                for (uint32_t q = lane_v; q < (uint32_t)NQ; q += 64) args.overflow[q] = 1;
+                if (lane_v == 0) atomicAdd(&g_wide_poll_timeouts, 1u);
+                if (lane_v < 8) __hip_atomic_store(sync + lane_v, kSlotOpen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        if constexpr (STAMPS) {
+            const unsigned long long dt = __builtin_readcyclecounter() - st_a;
+            st_bar += dt;
+            st_max = dt > st_max ? dt : st_max;
+        }
+    };
+
     // The append path reads the tombstone / allow words with SCALAR loads (sload_u64).  The scalar data cache is not invalidated
     // between the kernels of a stream the way the vector L1 is — compiler-made scalar loads only ever touch kernel arguments and
     // constants — so a line cached by an earlier kernel (the previous call's allow bitmap in the same workspace; a closed index's
@@ -765,9 +820,10 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                 for (int nt = nt_lo; nt < nt_hi; ++nt) acc[h][nt] = i32x4{-ctau[nt], -ctau[nt], -ctau[nt], -ctau[nt]};
         };
         wait_vmcnt<PW*(NSLOT - 2)>();          // this wave's share of tile 0 has landed ...
-        if constexpr (FLAGS) {
-            flag_post(flags, lane);
-            flag_wait(flags, WPB);             // ... and everyone's
+        if constexpr (SLOTSYNC) {
+            slot_post(flags);
+            if (!slot_reached(slot_peek(sync), WPB)) slot_wait_slow(0, WPB);   // ... and everyone's
+            asm volatile("" ::: "memory");
         } else {
             __builtin_amdgcn_s_barrier();      // ... and everyone's
             asm volatile("" ::: "memory");
@@ -779,6 +835,8 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
         uint32_t slot = 0, slot_prev = NSLOT - 1;
         const unsigned char* cur = slot_base(0);
         uint32_t tB = ntiles;                   // tile of the pair whose second-half scores are still to be tested (none yet)
+        // SLOTSYNC: what a counter of the current tile's slot reads once all WPB waves have posted for this tile (WPB per use of a slot)
+        [[maybe_unused]] uint32_t sync_cur = WPB;
         // GMAX: the lane's best score per query tile so far and the first row of the sub-tile pair it was seen in
         [[maybe_unused]] int gbest[QT];
         [[maybe_unused]] uint32_t grow[QT];
@@ -838,13 +896,25 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
             const uint32_t slot_next = slot + 1 == NSLOT ? 0 : slot + 1;
             const unsigned char* nxt = slot_base(slot_next);
             const uint32_t t = cursor_tile(cc);   // (a ragged round's missing tile is recognised in the slow path: emit_tiles)
+            // SLOTSYNC: the counts this tile waits for — landed(n+1) in the next slot, freed(n-1) in the previous one (nothing before tile 1)
+            [[maybe_unused]] const uint32_t sync_next = sync_cur + (slot_next == 0 ? WPB : 0);
+            [[maybe_unused]] const uint32_t sync_prev = cc.n >= 1 ? sync_cur - (slot == 0 ? WPB : 0) : 0;
+            [[maybe_unused]] uint32_t seen_freed = 0, seen_landed = 0;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 constexpr int TK = KS >= 4 ? 2 : 0;   // the k-step after which a phase carries the other half's test
                 // the wave's priority falls as it advances through the tile (kOptFlat): one s_setprio where the level changes
                 constexpr int H = 2 * NP;
+#ifdef FSGPU_LAB_LEVEL_PARITY
+                // (lab, profiles/wide_slot_sync/slot_sync_ab.txt) the tile's parity folded into the level: the four levels spread over TWO
+                // tiles — 3, 2 at the halves of an even tile, 1, 0 at the halves of an odd one — so that twins up to a tile apart are
+                // ordered by their progress across every second tile boundary
+                const int lv1 = wide_level(((int)(cc.n & 1u) * NP + p) * 2, 2 * H), lv2 = lv1;
+                if (LEVEL && p % (NP / 2) == 0) set_level(lv1);
+#else
                 const int lv1 = wide_level(2 * p, H), lv2 = wide_level(2 * p + 1, H);
                 if (lv1 != wide_level((2 * p + H - 1) % H, H)) set_level(lv1);
+#endif
                 // ---- phase 1: query tiles [0, QA); the previous pair's tiles [QA, QT) are tested in its shadow
                 init_acc(0, QA);
                 bool anyB = false;
@@ -863,13 +933,18 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                         [[maybe_unused]] unsigned long long st_a = 0;
                         if constexpr (STAMPS) st_a = __builtin_readcyclecounter();
                         wait_vmcnt<PW*(NSLOT - 3)>();
-                        if constexpr (FLAGS) {
-                            flag_post(flags + slot_next * 4, lane);   // this wave's share of tile n+1 is in LDS (posted a tile early)
+                        if constexpr (SLOTSYNC) {
+                            slot_post(flags + slot_next * 4);   // this wave's share of tile n+1 is in LDS (posted a tile early)
+                            seen_freed = slot_peek(sync + 4 + slot_prev);   // (needed two k-steps on: before the refill)
                         } else {
                             __builtin_amdgcn_s_barrier();
                             asm volatile("" ::: "memory");
                         }
-                        if constexpr (STAMPS) st_bar += __builtin_readcyclecounter() - st_a;
+                        if constexpr (STAMPS) {
+                            const unsigned long long dt = __builtin_readcyclecounter() - st_a;
+                            st_bar += dt;
+                            st_max = dt > st_max ? dt : st_max;
+                        }
                     }
                     // the refill of tile n-1's slot: one group of DMA instructions per pair, behind a few MFMAs of its phase 1
                     // (all of them behind the first pair's first MFMAs was measured: 1.43 instead of 1.36 ms — the DMA's LDS writes
@@ -877,13 +952,28 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                     {
                         constexpr int IPP = (PARTS + NP - 1) / NP;   // issue points per pair
                         constexpr int K1 = KS >= 3 ? 2 : KS - 1, K2 = KS >= 5 ? 4 : K1;
-                        if constexpr (FLAGS) {
+                        if constexpr (SLOTSYNC) {
                             // tile n-1's slot takes tile n+2 once EVERY wave is past its last read of tile n-1 (posted a pair before
                             // the end of that tile: in the common case long ago)
-                            if (p == 0 && kk == K1 && cc.n >= 1) flag_wait(flags + 16 + slot_prev * 4, WPB * ((cc.n - 1) / NSLOT + 1));
+                            static_assert(K1 >= 1, "the counter is read at k-step 0 and needed at k-step K1");
+                            if (p == 0 && kk == K1) {
+                                if (__builtin_expect(!slot_reached(seen_freed, sync_prev), 0)) slot_wait_slow(4 + slot_prev, sync_prev);
+                                asm volatile("" ::: "memory");
+                            }
                         }
                         if (kk == K1 && p * IPP < PARTS) fetch_part(slot_prev, p * IPP);
                         if (IPP > 1 && K2 != K1 && kk == K2 && p * IPP + 1 < PARTS) fetch_part(slot_prev, p * IPP + 1);
+                    }
+                    if constexpr (SLOTSYNC) {
+                        // The next tile's first fragments go out in this pair's phase 2: everyone's share of that tile must be in LDS.
+                        // landed(n+1) is read two k-steps before this phase ends and tested at its end — in front of the excursion
+                        // that may follow, so that the value is not one more register alive across the append path.
+                        constexpr int KP = KS >= 3 ? KS - 3 : 0;
+                        if (p + 1 == NP && kk == KP) seen_landed = slot_peek(sync + slot_next);
+                        if (p + 1 == NP && kk == KS - 1) {
+                            if (__builtin_expect(!slot_reached(seen_landed, sync_next), 0)) slot_wait_slow(slot_next, sync_next);
+                            asm volatile("" ::: "memory");
+                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -896,9 +986,6 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
 #pragma unroll
                 for (int kk = 0; kk < KS; ++kk) {
                     mfma_step(kk, QA, QT);
-                    if constexpr (FLAGS) {   // the next tile's first fragments: everyone's share of it must be in LDS
-                        if (p + 1 == NP && kk == 0) flag_wait(flags + slot_next * 4, WPB * ((cc.n + 1) / NSLOT + 1));
-                    }
                     if (p + 1 < NP) read_frag(cur, p + 1, kk);
                     else read_frag(nxt, 0, kk);
                     if constexpr (GMAX) {
@@ -908,8 +995,8 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr (FLAGS) {   // this wave's last read of the tile is out (the last pair's fragments): its slot may be refilled
-                    if (p + 2 == NP) flag_post(flags + 16 + slot * 4, lane);
+                if constexpr (SLOTSYNC) {   // this wave's last read of the tile is out (the last pair's fragments): its slot may be refilled
+                    if (p + 2 == NP) slot_post(flags + 16 + slot * 4);
                 }
                 if (__builtin_expect(wave_any(anyA), 0)) emit_tiles(t, p * 2, acc, 0, QA, lv2);
                 tB = t;
@@ -918,6 +1005,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
             slot_prev = slot;
             slot = slot_next;
             cur = nxt;
+            if constexpr (SLOTSYNC) sync_cur = sync_next;
         }
         if constexpr (GMAX) {
             gmax_update(tB, (NP - 1) * 2, QA, QT);
@@ -1005,7 +1093,7 @@ __device__ __forceinline__ void scan_wide_body(MfmaScanArgs args, const int q0_w
             out[0] = __builtin_readcyclecounter() - st_loop;
             out[1] = st_bar;
             out[2] = st[0];
-            out[3] = st[1];
+            out[3] = st[1] | ((st_max < 0xffffffffull ? st_max : 0xffffffffull) << 32);   // (entries below 2^32)
         }
     }
     if (args.cand_count) {
@@ -1085,10 +1173,13 @@ hipError_t launch_wide_k(const MfmaScanArgs& args, int grid, hipStream_t stream,
     return hipGetLastError();
 }
 
-// (kOptFlat names a kernel of its own only where the split loop runs: everything else has no priority levels to leave out)
+// (kOptFlat names a kernel of its own only where the split loop runs: everything else has no priority levels to leave out;
+// kOptBarrier only where the 128-row loop runs: everything else has a barrier per tile anyway)
 template <int ROWB, int EB, int QT, int NSLOT, int OPT, int DBG = 0>
 hipError_t launch_wide_t(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
-    return launch_wide_k<ROWB, EB, QT, NSLOT, wide_split_ok(ROWB, EB, QT, OPT, DBG) ? OPT : (OPT & ~kOptFlat), DBG>(args, grid, stream, occupancy);
+    constexpr int O1 = wide_split_ok(ROWB, EB, QT, OPT, DBG) ? OPT : (OPT & ~kOptFlat);
+    constexpr int O2 = wide_big_ok(ROWB, EB, QT, NSLOT, OPT, DBG) ? O1 : (O1 & ~kOptBarrier);
+    return launch_wide_k<ROWB, EB, QT, NSLOT, O2, DBG>(args, grid, stream, occupancy);
 }
 
 #ifdef FSGPU_LAB_ASYM
@@ -1114,7 +1205,7 @@ hipError_t launch_wide_asym(const MfmaScanArgs& args, int grid, hipStream_t stre
 template <int ROWB, int EB, int QT, int NSLOT, int O, int MODE>
 hipError_t launch_wide_pick(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
     if constexpr (MODE == 0 && wide_big_ok(ROWB, EB, QT, 3, O, 0)) return launch_wide_t<ROWB, EB, QT, 3, O, 0>(args, grid, stream, occupancy);
-    else return launch_wide_t<ROWB, EB, QT, NSLOT, O & ~(kOptBig | kOptFlags), MODE>(args, grid, stream, occupancy);
+    else return launch_wide_t<ROWB, EB, QT, NSLOT, O & ~kOptBig, MODE>(args, grid, stream, occupancy);
 }
 
 template <int EB, int QT, int MODE, int O>
@@ -1131,9 +1222,9 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
                 if (dbg == 2) return launch_wide_t<768, EB, QT, 6, O, 2>(args, grid, stream, occupancy);
             }
 #endif
-            return launch_wide_t<768, EB, QT, 6, O & ~(kOptBig | kOptFlags), MODE>(args, grid, stream, occupancy);   // 6 x 24 KB
+            return launch_wide_t<768, EB, QT, 6, O & ~kOptBig, MODE>(args, grid, stream, occupancy);   // 6 x 24 KB
         } else return hipErrorInvalidValue;
-        case 256: if constexpr (QT <= 4 && MODE != 7) return launch_wide_t<512, EB, QT, 8, O & ~kOptFlags, MODE>(args, grid, stream, occupancy);   // 8 x 16 KB
+        case 256: if constexpr (QT <= 4 && MODE != 7) return launch_wide_t<512, EB, QT, 8, O, MODE>(args, grid, stream, occupancy);   // 8 x 16 KB
                   else return hipErrorInvalidValue;
         // Rows of 384 / 256 bytes: the int8 copies of 384- and 256-dimensional slabs (MiniLM / the hash embedders, potion).  Their
         // f16 forms (192 / 128 dimensions) and rows of 128 bytes are not shapes of the reference's embedders: those searches run on
@@ -1158,6 +1249,9 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
                     case 30:   // 128-row tiles, three slots: the main pass only (a sample stage visits 64-row groups)
                         if constexpr (MODE == 0) return launch_wide_t<384, EB, QT, 3, 30, MODE>(args, grid, stream, occupancy);
                         else return launch_wide_t<384, EB, QT, 6, 14, MODE>(args, grid, stream, occupancy);
+                    case 62:   // ... with the block barrier per tile
+                        if constexpr (MODE == 0) return launch_wide_t<384, EB, QT, 3, 62, MODE>(args, grid, stream, occupancy);
+                        else return launch_wide_t<384, EB, QT, 6, 14, MODE>(args, grid, stream, occupancy);
                     default: break;
                 }
                 if constexpr (MODE == 0) {   // the shipped main pass with s_memtime stamps (scripts/r04/wide_stamps.sh): one line per launch
@@ -1176,8 +1270,10 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
                         (void)hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
                         double loop = 0, bar[2] = {0, 0}, slow[2] = {0, 0}, ent[2] = {0, 0}, lp[2] = {0, 0};
                         int hist[10] = {0};
+                        unsigned long long longest = 0;   // the longest single wait of any wave, cycles
                         for (size_t w = 0; w < nwaves; ++w) {
-                            const double L = (double)h[w * 4], B = (double)h[w * 4 + 1], S = (double)h[w * 4 + 2], E = (double)h[w * 4 + 3];
+                            const double L = (double)h[w * 4], B = (double)h[w * 4 + 1], S = (double)h[w * 4 + 2], E = (double)(h[w * 4 + 3] & 0xffffffffull);
+                            longest = std::max(longest, h[w * 4 + 3] >> 32);
                             if (L <= 0) continue;
                             const int half = (w & 7) >= 4;
                             loop += L;
@@ -1188,10 +1284,10 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
                             int b = (int)(10.0 * B / L);
                             ++hist[b < 0 ? 0 : b > 9 ? 9 : b];
                         }
-                        std::fprintf(stderr, "[wide stamps] waves %zu  loop cycles/wave %.0f | at the tile's wait + barrier: waves 0-3 %.1f %%, waves 4-7 %.1f %% | in the append path: "
-                                             "%.1f %% / %.1f %% (%.0f / %.0f entries per wave, %.0f cycles each) | waves by barrier share, deciles:",
+                        std::fprintf(stderr, "[wide stamps] waves %zu  loop cycles/wave %.0f | at the tile's DMA wait + barrier / slot waits: waves 0-3 %.1f %%, waves 4-7 %.1f %% | in the append path: "
+                                             "%.1f %% / %.1f %% (%.0f / %.0f entries per wave, %.0f cycles each) | longest single wait %llu cycles | waves by wait share, deciles:",
                                      nwaves, loop / nwaves, 100 * bar[0] / lp[0], 100 * bar[1] / lp[1], 100 * slow[0] / lp[0], 100 * slow[1] / lp[1],
-                                     ent[0] / (nwaves / 2), ent[1] / (nwaves / 2), (slow[0] + slow[1]) / std::max(1.0, ent[0] + ent[1]));
+                                     ent[0] / (nwaves / 2), ent[1] / (nwaves / 2), (slow[0] + slow[1]) / std::max(1.0, ent[0] + ent[1]), longest);
                         for (int b = 0; b < 10; ++b) std::fprintf(stderr, " %d", hist[b]);
                         std::fprintf(stderr, "\n");
                         return hipSuccess;
@@ -1206,7 +1302,7 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
             }
 #endif
 #ifdef FSGPU_LAB_ASYM   // lab: 5 + 3 query tiles per SIMD pair, 64-row tiles in six slots, no 128-row form (the five-tile waves run the chunk loop)
-            if constexpr (EB == 1 && QT == 4 && MODE == 0) { if (!occupancy) return launch_wide_asym<384, 1, FSGPU_LAB_ASYM, 8 - FSGPU_LAB_ASYM, 6, O & ~(kOptBig | kOptFlags)>(args, grid, stream); }
+            if constexpr (EB == 1 && QT == 4 && MODE == 0) { if (!occupancy) return launch_wide_asym<384, 1, FSGPU_LAB_ASYM, 8 - FSGPU_LAB_ASYM, 6, O & ~kOptBig>(args, grid, stream); }
 #endif
             return launch_wide_pick<384, EB, QT, 6, O, MODE>(args, grid, stream, occupancy);   // 6 x 24 KB (3 x 48 KB)
         }
@@ -1216,11 +1312,19 @@ hipError_t launch_wide_o(const MfmaScanArgs& args, int grid, hipStream_t stream,
     }
 }
 
-// FSGPU_WIDE_PRIO=off: the split-loop kernels without their progress-ordered wave priority (kOptFlat), for timing both from one build
+// FSGPU_WIDE_PRIO=off: the split-loop kernels without their progress-ordered wave priority (kOptFlat); FSGPU_WIDE_SYNC=barrier: the
+// 128-row main pass with its block barrier per tile (kOptBarrier) — for timing both forms of either from one build
+template <int EB, int QT, int MODE, int O>
+hipError_t launch_wide_s(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
+    if constexpr (MODE == 0) {   // (a sample stage never runs the 128-row loop)
+        if (scan_wide_barrier_sync()) return launch_wide_o<EB, QT, MODE, O | kOptBarrier>(args, grid, stream, occupancy);
+    }
+    return launch_wide_o<EB, QT, MODE, O>(args, grid, stream, occupancy);
+}
 template <int EB, int QT, int MODE = 0>
 hipError_t launch_wide_d(const MfmaScanArgs& args, int grid, hipStream_t stream, int* occupancy) {
-    if (scan_wide_flat_priority()) return launch_wide_o<EB, QT, MODE, kWideOptDefault | kOptFlat>(args, grid, stream, occupancy);
-    return launch_wide_o<EB, QT, MODE, kWideOptDefault>(args, grid, stream, occupancy);
+    if (scan_wide_flat_priority()) return launch_wide_s<EB, QT, MODE, kWideOptDefault | kOptFlat>(args, grid, stream, occupancy);
+    return launch_wide_s<EB, QT, MODE, kWideOptDefault>(args, grid, stream, occupancy);
 }
 
 }  // namespace
@@ -1234,6 +1338,12 @@ extern "C" int fsgpu_lab_bitmap_debug(unsigned long long* out, int cap_records) 
     return (int)n;
 }
 #endif
+
+uint32_t scan_wide_poll_timeouts() {
+    unsigned int n = 0;
+    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_wide_poll_timeouts), sizeof n) != hipSuccess) return ~0u;
+    return n;
+}
 
 bool scan_wide_supported(int dim, int elem_bytes) {
     const int rowb = dim * elem_bytes;   // (the shapes launch_wide_d builds)

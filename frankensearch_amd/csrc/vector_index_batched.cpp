@@ -21,6 +21,7 @@ namespace fsgpu {
 using namespace detail;
 
 bool scan_wide_flat_priority() { return knobs().wide_flat_priority; }
+bool scan_wide_barrier_sync() { return knobs().wide_barrier_sync; }
 
 // Batched search on the matrix cores; see mfma_scan.hip for the error bound that makes the result exact.
 SearchError VectorIndex::search_top_k_batched_device(const float* queries_dev, uint32_t nq, uint32_t query_len,
@@ -1187,8 +1188,8 @@ SearchError VectorIndex::batched_fallback(const BatchedPlan& p, BatchedOutcome* 
             if (p.counts_all[i] < k_eff) ++few;
             mx = std::max(mx, p.counts_all[i]);
         }
-        std::fprintf(stderr, "[fsgpu batched] nq=%u k=%u fallbacks=%zu  pool_overflow=%u  slot_or_skip=%u  few=%u  max_cand=%u\n", nq, k,
-                     fb.size(), big, slot, few, mx);
+        std::fprintf(stderr, "[fsgpu batched] nq=%u k=%u fallbacks=%zu  pool_overflow=%u  slot_or_skip=%u  few=%u  max_cand=%u  slot_wait_timeouts=%u\n", nq, k,
+                     fb.size(), big, slot, few, mx, scan_wide_poll_timeouts());
         for (size_t j = 0; j < fb.size() && j < 4; ++j)
             std::fprintf(stderr, "    query %u: overflow=%u candidates=%u\n", fb[j], p.overflow_all[fb[j]], p.counts_all[fb[j]]);
     }

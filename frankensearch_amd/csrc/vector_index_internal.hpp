@@ -65,8 +65,8 @@ inline uint64_t fnv1a(const char* p, size_t n) {
     return h;
 }
 
-// Switches read from the environment ONCE (getenv is not safe against concurrent setenv).  A default build reads five:
-// FSGPU_WIDE, FSGPU_WIDE_LAYOUT, FSGPU_WIDE_PRIO, FSGPU_FILTER, FSGPU_DEBUG_BATCHED (documented in include/fsgpu.h).  Everything else is a tuning / A-B knob of the
+// Switches read from the environment ONCE (getenv is not safe against concurrent setenv).  A default build reads six:
+// FSGPU_WIDE, FSGPU_WIDE_LAYOUT, FSGPU_WIDE_PRIO, FSGPU_WIDE_SYNC, FSGPU_FILTER, FSGPU_DEBUG_BATCHED (documented in include/fsgpu.h).  Everything else is a tuning / A-B knob of the
 // lab and exists only in builds with -DFSGPU_EXPERIMENTS (FSGPU_BUILD_DEFS, frankensearch_amd/build.py; scripts/exp_*).
 struct Knobs {
     int grid_blocks = 0, ra = 0, rb = 0, mfma_shape = 0, mfma_shape_i8 = 0, round = 0, i8_per_cu = 0;
@@ -75,6 +75,8 @@ struct Knobs {
                                     // whole grid (the layout before the side-by-side one; both can be timed from one build)
     bool wide_flat_priority = false;   // FSGPU_WIDE_PRIO=off: the wide kernels' split loop without its progress-ordered wave priority
                                        // (mfma_wide.hip, kOptFlat: the loop as it was before; both can be timed from one build)
+    bool wide_barrier_sync = false;    // FSGPU_WIDE_SYNC=barrier: the wide main pass on 128-row tiles with its block barrier per tile instead of the
+                                       // per-slot counters (mfma_wide.hip, kOptBarrier: the loop as it was before; both can be timed from one build)
     int filter = 0;     // FSGPU_FILTER: "f16" (1) / "i8" (2) pin the filter of the exact batched search; unset = automatic
     int slots_b = 0, slots_main = 0;   // FSGPU_SLOTS_B / FSGPU_SLOTS_MAIN: list slots per (query, block) of the wide kernel's stages
     int wide_max = 0;   // FSGPU_WIDE_MAX: cap on the query tiles per wave of the wide main pass (default: what the registers hold)
@@ -90,6 +92,7 @@ struct Knobs {
         if (const char* w = env("FSGPU_WIDE")) wide = std::atoi(w);
         if (const char* l = env("FSGPU_WIDE_LAYOUT")) wide_sequential = std::strcmp(l, "sequential") == 0;
         if (const char* o = env("FSGPU_WIDE_PRIO")) wide_flat_priority = std::strcmp(o, "off") == 0;
+        if (const char* y = env("FSGPU_WIDE_SYNC")) wide_barrier_sync = std::strcmp(y, "barrier") == 0;
         if (const char* f = env("FSGPU_FILTER")) filter = std::strcmp(f, "f16") == 0 ? 1 : std::strcmp(f, "i8") == 0 ? 2 : 0;
         debug_batched = env("FSGPU_DEBUG_BATCHED") != nullptr;
 #ifdef FSGPU_EXPERIMENTS

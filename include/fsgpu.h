@@ -1280,10 +1280,12 @@ fsgpu_status fsgpu_m2v_set_coalescing(fsgpu_m2v *m, uint32_t max_batch, uint32_t
 fsgpu_status fsgpu_bert_set_coalescing(fsgpu_bert *m, uint32_t max_batch, uint32_t max_wait_us);
 
 /* Environment switches (read once, at first use).
- * A default build reads seven:
+ * A default build reads eight:
  *   FSGPU_WIDE=0|2|3            batched main pass: 0 = queries in LDS (128 per pass), 2 / 3 = queries in registers (256 / 384 on f16 rows)
  *   FSGPU_WIDE_PRIO=off         the register-query kernels' split loop without its progress-ordered wave priority (same answers; for
  *                               timing the loop with and without it from one build)
+ *   FSGPU_WIDE_SYNC=barrier     the register-query main pass on 128-row tiles with one block barrier per tile instead of its per-slot
+ *                               counters (same answers; for timing the two forms from one build)
  *   FSGPU_WIDE_LAYOUT=sequential  the query groups of one register-query main-pass launch run one after the other on the whole grid
  *                               instead of side by side on a share of it each (same answers; for timing the two layouts from one build)
  *   FSGPU_FILTER=f16|i8         pin the candidate filter of the exact batched search (as fsgpu_index_set_batched_filter does per index)
