@@ -161,6 +161,7 @@ SIGNATURES = {
     "fsgpu_bert_linear_format": (_u32, [_vp]),
     "fsgpu_lab_linear_int8_dynamic": (_i32, [_i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "fsgpu_lab_bert_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_stage_args: BertStageArgs below)
+    "fsgpu_lab_bert_int8_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_int8_stage_args: BertInt8StageArgs below)
     "fsgpu_lab_bert_short_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_bert_short_args: BertShortArgs below)
     "fsgpu_lab_scan_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_scan_stage_args: ScanStageArgs below)
     "fsgpu_lab_scan_stage_check": (_i32, [_vp]),
@@ -274,6 +275,13 @@ class BertStageArgs(C.Structure):
     _fields_ = [(name, _u32) for name in ("stage", "form", "epilogue", "m", "n", "k", "hidden", "inter", "n_docs", "vocab", "max_pos")] + [
         ("eps", C.c_float), ("scale", C.c_float), ("offsets", _vp), ("ids", _vp), ("positions", _vp), ("types", _vp),
         ("in_", _vp * 12), ("out0", _vp), ("out1", _vp)]
+
+
+class BertInt8StageArgs(C.Structure):
+    """fsgpu_lab_bert_int8_stage_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("stage", "form", "epilogue", "m", "n", "k", "hidden", "vocab", "max_pos")] + [
+        ("eps", C.c_float), ("ids", _vp), ("positions", _vp), ("codes", _vp), ("in_", _vp * 5), ("out_f32", _vp), ("out_codes", _vp),
+        ("out_scales", _vp)]
 
 
 class BertShortArgs(C.Structure):

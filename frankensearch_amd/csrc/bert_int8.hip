@@ -7,6 +7,7 @@
 // i8_code below):
 //   amax = max_k |x[k]|;  inv = 127.0f / amax;  q[k] = clamp(round_half_away(x[k] * inv), -127, 127);  scale = amax / 127.0f
 //   an all-zero row gives q = 0 and scale = 0.  Both divisions are IEEE f32 (this file is built without fast-math).
+//   a row with 0 < amax < 127 / FLT_MAX has inv = +inf: its zeros code to 0, its other elements to +-127 (NaN and Inf inputs: undefined).
 // Epilogue: y = ((float)acc * (sx[m] * sw[n])) + b[n] as separate multiplies and an add (-ffp-contract=off).
 //
 // GEMM: v_mfma_i32_16x16x64_i8, A = the activation codes [M, K] row-major, B = the weight codes pre-packed in fragment order (a
@@ -47,10 +48,13 @@ __device__ __forceinline__ float i8_gelu(float x) {
 }
 
 // The quantisation contract, shared by the weight packer and every activation quantiser.  amax == 0: inv = 0, every code 0.
+// 0 < amax < 127 / FLT_MAX (~ 3.7e-37): inv = +inf; a non-zero element's product is +-inf and its code +-127, a zero element's
+// product is NaN and its code 0 (the tiny-amax rule of DESIGN §3.8: a zero codes to 0 in every row).
 __device__ __forceinline__ float i8_row_inv(float amax) { return amax > 0.f ? 127.0f / amax : 0.f; }
 __device__ __forceinline__ float i8_row_scale(float amax) { return amax / 127.0f; }
 __device__ __forceinline__ int8_t i8_code(float v, float inv) {
-    const float r = roundf(v * inv);   // half away from zero (Rust f32::round)
+    const float p = v * inv;
+    const float r = roundf(p == p ? p : 0.f);   // half away from zero (Rust f32::round); NaN only as 0 * inf
     return (int8_t)(int)fminf(fmaxf(r, -127.0f), 127.0f);
 }
 
@@ -239,6 +243,8 @@ __global__ __launch_bounds__(256) void bert_i8_gemm_kernel(const int8_t* __restr
 
 // ---- launchers ------------------------------------------------------------------------------------------
 
+// The shape rule alone.  The accumulator is i32 and 127 x 127 x K must stay below 2^31: K <= 133,120.  The encoder's K is at most its
+// intermediate width, and the lab entry (fsgpu_lab_bert_int8_stage) caps K at 4096.
 bool bert_i8_gemm_supported(int N, int K) { return N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0; }
 
 size_t bert_i8_packed_bytes(int N, int K) { return (size_t)N * K; }

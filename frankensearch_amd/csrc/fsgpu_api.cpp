@@ -2091,7 +2091,8 @@ struct LabStage {
         unsigned char* base = nullptr;
         size_t rows = 0, cols = 0, elem = 0;
         size_t slab_rows = 0;   // non-zero: rows is slabs x 32 workspace rows of which the first slab_rows of each slab go to the host
-        float* host = nullptr;
+        bool untouched = false; // the launch must leave the whole body as it was filled (nothing goes to the host)
+        void* host = nullptr;
         void* ptr() const { return base + kGuardRows * cols * elem; }
     };
     std::vector<fsgpu::DeviceBuffer> bufs;
@@ -2132,8 +2133,9 @@ struct LabStage {
         if (ok()) he = fsgpu::launch_bert_pack_w(h, d, N, K, nullptr);
         return d;
     }
-    // an output of rows x cols elements of elem bytes (2: f16, 4: f32) for the caller's `host`; init: f32 rows the kernel updates in place
-    void* out(size_t rows, size_t cols, size_t elem, float* host, const float* init = nullptr) {
+    // an output of rows x cols elements of elem bytes (1: int8 codes, copied as they are, 2: f16, 4: f32) for the caller's `host`; init: f32
+    // rows the kernel updates in place
+    void* out(size_t rows, size_t cols, size_t elem, void* host, const float* init = nullptr) {
         Out o;
         o.rows = rows, o.cols = cols, o.elem = elem, o.host = host;
         const size_t bytes = (rows + 2 * kGuardRows) * cols * elem;
@@ -2155,6 +2157,12 @@ struct LabStage {
         outs.back().slab_rows = m;
         return p;
     }
+    // a buffer the launch is handed (or not) and must not write: guard bytes throughout, checked whole
+    void* out_untouched(size_t rows, size_t cols, size_t elem) {
+        void* p = out(rows, cols, elem, nullptr);
+        outs.back().untouched = true;
+        return p;
+    }
     void collect() {
         hip(hipStreamSynchronize(nullptr));
         for (const Out& o : outs) {
@@ -2165,7 +2173,10 @@ struct LabStage {
             if (!ok()) return;
             for (size_t i = 0; i < band; ++i)
                 if (h[i] != kGuardByte || h[band + body + i] != kGuardByte) guard_hit = true;
-            if (o.slab_rows) {
+            if (o.untouched) {
+                for (size_t i = 0; i < body; ++i)
+                    if (h[band + i] != kGuardByte) guard_hit = true;
+            } else if (o.slab_rows) {
                 const size_t row = o.cols * o.elem;
                 for (size_t sl = 0; sl < o.rows / 32; ++sl) {
                     const unsigned char* slab = h.data() + band + sl * 32 * row;
@@ -2173,11 +2184,11 @@ struct LabStage {
                     for (size_t i = o.slab_rows * row; i < 32 * row; ++i)
                         if (slab[i] != kGuardByte) guard_hit = true;
                 }
-            } else if (o.elem == 4) {
+            } else if (o.elem != 2) {
                 std::memcpy(o.host, h.data() + band, body);
             } else {
                 const _Float16* s = reinterpret_cast<const _Float16*>(h.data() + band);
-                for (size_t i = 0; i < o.rows * o.cols; ++i) o.host[i] = (float)s[i];
+                for (size_t i = 0; i < o.rows * o.cols; ++i) static_cast<float*>(o.host)[i] = (float)s[i];
             }
         }
     }
@@ -2205,17 +2216,21 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
     const int M = (int)a.m, N = (int)a.n, K = (int)a.k, H = (int)a.hidden, I = (int)a.inter;
     auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
     if (a.m == 0 || a.m > (1u << 20)) return bad("bert stage: m must be in 1..=2^20");
-    if (st > FSGPU_LAB_BERT_POOL || form > 2) return bad("bert stage: unknown stage or form");
-    static const int n_in[] = {1, 3, 6, 12, 5, 1};
+    if (st > FSGPU_LAB_BERT_CLS_HEAD || form > 2) return bad("bert stage: unknown stage or form");
+    static const int n_in[] = {1, 3, 6, 12, 5, 1, 5};
     const int need = n_in[st] + ((st == FSGPU_LAB_BERT_ATTENTION && form == 2) ? 1 : 0);
     for (int i = 0; i < need; ++i)
         if (!a.in[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: missing input");
     if (!a.out0) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: out0 is null");
     const bool two_outs = st == FSGPU_LAB_BERT_LINEAR_LN || st == FSGPU_LAB_BERT_POST_ATTN || st == FSGPU_LAB_BERT_EMBED_LN ||
-                          (st == FSGPU_LAB_BERT_ATTENTION && form == 2);
+                          st == FSGPU_LAB_BERT_CLS_HEAD || (st == FSGPU_LAB_BERT_ATTENTION && form == 2);
     if (two_outs && !a.out1) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert stage: out1 is null");
-    // the encoder's own shape rule (NativeEmbedder::init); the linear stage has no hidden
-    if (st != FSGPU_LAB_BERT_LINEAR && (H <= 0 || H % 128 != 0 || H > 1024)) return bad("bert stage: hidden must be a multiple of 128 and <= 1024");
+    // the encoder's own shape rule (NativeEmbedder::init); the linear stage has no hidden, the head has the reranker's rule
+    if (st == FSGPU_LAB_BERT_CLS_HEAD) {
+        if (form != 0 || !fsgpu::bert_rerank_supported(H)) return bad("bert stage: the head takes a hidden that is a multiple of 64 and <= 1024");
+    } else if (st != FSGPU_LAB_BERT_LINEAR && (H <= 0 || H % 128 != 0 || H > 1024)) {
+        return bad("bert stage: hidden must be a multiple of 128 and <= 1024");
+    }
     uint32_t max_seq = 0, min_seq = 0;
     switch (st) {
         case FSGPU_LAB_BERT_ATTENTION:
@@ -2244,6 +2259,8 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
                 if (a.ids[t] < 0 || (uint32_t)a.ids[t] >= a.vocab || a.positions[t] < 0 || (uint32_t)a.positions[t] >= a.max_pos ||
                     (form == 1 && (a.types[t] < 0 || a.types[t] > 1)))
                     return bad("bert stage: token id, position or type out of range");
+            break;
+        case FSGPU_LAB_BERT_CLS_HEAD:
             break;
         default:
             if (!lab_offsets(a.offsets, a.n_docs, a.m, &max_seq, &min_seq)) return bad("bert stage: offsets must run from 0 to m");
@@ -2353,6 +2370,15 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
             } else {
                 s.hip(fsgpu::launch_bert_embed_typed_ln(ids, types, positions, word, pos, type, lnw, lnb, x, x_h, M, H, a.eps, nullptr));
             }
+        } else if (st == FSGPU_LAB_BERT_CLS_HEAD) {
+            const float* x_cls = s.f32(a.in[0], m * h);
+            const float* pool_w = s.f32(a.in[1], h * h);
+            const float* pool_b = s.f32(a.in[2], h);
+            const float* cls_w = s.f32(a.in[3], h);
+            const float* cls_b = s.f32(a.in[4], 1);
+            float* logits = static_cast<float*>(s.out(m, 1, 4, a.out0));
+            float* scores = static_cast<float*>(s.out(m, 1, 4, a.out1));
+            if (s.ok()) s.hip(fsgpu::launch_bert_cls_head(x_cls, pool_w, pool_b, cls_w, cls_b, logits, scores, M, H, nullptr));
         } else {
             const uint32_t* offs = static_cast<const uint32_t*>(s.raw(a.offsets, ((size_t)a.n_docs + 1) * 4));
             const float* x = s.f32(a.in[0], m * h);
@@ -2363,6 +2389,100 @@ fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_arg
         if (!s.e.ok()) return finish(s.e);
         if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
         if (s.guard_hit) return fail(FSGPU_ERR_DEVICE, "bert stage: a kernel wrote into a guard band of its output");
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_lab_bert_int8_stage(int32_t device, const fsgpu_lab_bert_int8_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_bert_int8_stage_args& a = *args;
+    const uint32_t st = a.stage, form = a.form;
+    const int M = (int)a.m, N = (int)a.n, K = (int)a.k, H = (int)a.hidden;
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    if (st > FSGPU_LAB_BERT_I8_ADD_LN_QUANT) return bad("bert int8 stage: unknown stage");
+    const bool two_forms = st == FSGPU_LAB_BERT_I8_QUANT_ROWS || st == FSGPU_LAB_BERT_I8_ADD_LN_QUANT;
+    if (form > (two_forms ? 1u : 0u)) return bad("bert int8 stage: unknown form");
+    static const int n_in[] = {1, 1, 3, 5, 4};
+    for (int i = 0; i < n_in[st]; ++i)
+        if (!a.in[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "bert int8 stage: missing input");
+    const bool no_q = st == FSGPU_LAB_BERT_I8_ADD_LN_QUANT && form == 1;
+    const bool f32_out = st >= FSGPU_LAB_BERT_I8_GEMM, q_out = st != FSGPU_LAB_BERT_I8_GEMM && !no_q;
+    if ((f32_out && !a.out_f32) || (q_out && (!a.out_codes || !a.out_scales)) || (st == FSGPU_LAB_BERT_I8_GEMM && !a.codes))
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "bert int8 stage: missing output or codes");
+    if (st != FSGPU_LAB_BERT_I8_PACK_W && (a.m == 0 || a.m > (1u << 20))) return bad("bert int8 stage: m must be in 1..=2^20");
+    if (st <= FSGPU_LAB_BERT_I8_GEMM) {
+        // 127 x 127 x K < 2^31 (the i32 accumulator): K <= 4096 here
+        if (K <= 0 || K % 64 != 0 || K > 4096) return bad("bert int8 stage: k must be a multiple of 64 and <= 4096");
+        if (st != FSGPU_LAB_BERT_I8_QUANT_ROWS && (a.n > (1u << 20) || !fsgpu::bert_i8_gemm_supported(N, K)))
+            return bad("bert int8 stage: n must be a multiple of 64");
+        if (st == FSGPU_LAB_BERT_I8_GEMM && a.epilogue > 1) return bad("bert int8 stage: unknown epilogue");
+    } else {
+        if (H <= 0 || H % 64 != 0 || H > 1024) return bad("bert int8 stage: hidden must be a multiple of 64 and <= 1024");
+        if (st == FSGPU_LAB_BERT_I8_EMBED_LN_QUANT) {
+            if (a.vocab == 0 || a.max_pos == 0 || !a.ids || !a.positions) return bad("bert int8 stage: embedding needs ids, positions, vocab and max_pos");
+            for (uint32_t t = 0; t < a.m; ++t)
+                if (a.ids[t] < 0 || (uint32_t)a.ids[t] >= a.vocab || a.positions[t] < 0 || (uint32_t)a.positions[t] >= a.max_pos)
+                    return bad("bert int8 stage: token id or position out of range");
+        }
+    }
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        const size_t m = a.m, n = a.n, k = a.k, h = a.hidden;
+        if (st == FSGPU_LAB_BERT_I8_QUANT_ROWS) {
+            const void* x = form == 1 ? s.f16(a.in[0], m * k) : static_cast<const void*>(s.f32(a.in[0], m * k));
+            void* q = s.out(m, k, 1, a.out_codes);
+            float* sc = static_cast<float*>(s.out(m, 1, 4, a.out_scales));
+            if (!s.ok()) {
+                // (an upload failed: nothing is launched)
+            } else if (form == 1) {
+                s.hip(fsgpu::launch_bert_i8_quant_rows_h(x, q, sc, M, K, nullptr));
+            } else {
+                s.hip(fsgpu::launch_bert_i8_quant_rows(static_cast<const float*>(x), q, sc, M, K, nullptr));
+            }
+        } else if (st == FSGPU_LAB_BERT_I8_PACK_W) {
+            const float* w = s.f32(a.in[0], n * k);
+            void* wp = s.out(n, k, 1, a.out_codes);
+            float* sw = static_cast<float*>(s.out(n, 1, 4, a.out_scales));
+            if (s.ok()) s.hip(fsgpu::launch_bert_i8_pack_w(w, wp, sw, N, K, nullptr));
+        } else if (st == FSGPU_LAB_BERT_I8_GEMM) {
+            const void* qa = s.raw(a.codes, m * k);
+            const float* sa = s.f32(a.in[0], m);
+            const float* w = s.f32(a.in[1], n * k);
+            const float* bias = s.f32(a.in[2], n);
+            void* wp = s.alloc(fsgpu::bert_i8_packed_bytes(N, K));
+            float* sw = static_cast<float*>(s.alloc(n * 4));
+            float* y = static_cast<float*>(s.out(m, n, 4, a.out_f32));
+            if (s.ok()) s.hip(fsgpu::launch_bert_i8_pack_w(w, wp, sw, N, K, nullptr));
+            if (s.ok()) s.hip(fsgpu::launch_bert_i8_gemm(qa, sa, wp, sw, bias, y, M, N, K, a.epilogue == 1, nullptr));
+        } else if (st == FSGPU_LAB_BERT_I8_EMBED_LN_QUANT) {
+            const int32_t* ids = static_cast<const int32_t*>(s.raw(a.ids, m * 4));
+            const int32_t* positions = static_cast<const int32_t*>(s.raw(a.positions, m * 4));
+            const float* word = s.f32(a.in[0], (size_t)a.vocab * h);
+            const float* pos = s.f32(a.in[1], (size_t)a.max_pos * h);
+            const float* type0 = s.f32(a.in[2], h);
+            const float* lnw = s.f32(a.in[3], h);
+            const float* lnb = s.f32(a.in[4], h);
+            float* x = static_cast<float*>(s.out(m, h, 4, a.out_f32));
+            void* q = s.out(m, h, 1, a.out_codes);
+            float* sc = static_cast<float*>(s.out(m, 1, 4, a.out_scales));
+            if (s.ok()) s.hip(fsgpu::launch_bert_i8_embed_ln_quant(ids, positions, word, pos, type0, lnw, lnb, x, q, sc, M, H, a.eps, nullptr));
+        } else {
+            const float* delta = s.f32(a.in[1], m * h);
+            const float* lnw = s.f32(a.in[2], h);
+            const float* lnb = s.f32(a.in[3], h);
+            float* x = static_cast<float*>(s.out(m, h, 4, a.out_f32, a.in[0]));
+            void* q = no_q ? s.out_untouched(m, h, 1) : s.out(m, h, 1, a.out_codes);
+            float* sc = static_cast<float*>(no_q ? s.out_untouched(m, 1, 4) : s.out(m, 1, 4, a.out_scales));
+            if (s.ok()) s.hip(fsgpu::launch_bert_i8_add_ln_quant(x, delta, lnw, lnb, no_q ? nullptr : q, sc, M, H, a.eps, nullptr));
+        }
+        s.collect();
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (s.guard_hit) return fail(FSGPU_ERR_DEVICE, "bert int8 stage: a kernel wrote into a guard band or into a buffer it must leave alone");
         return FSGPU_OK;
     });
 }

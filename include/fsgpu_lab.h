@@ -71,13 +71,17 @@ fsgpu_status fsgpu_lab_linear_int8_dynamic(int32_t device, const float *x, const
  *               1 launch_bert_post_attn_w_fixed, 2 launch_bert_gemm_ln_w then launch_bert_ffn_w
  *   EMBED_LN    in: word [vocab, hidden], pos [max_pos, hidden], type [1 | 2, hidden], ln_w, ln_b; ids, positions (, types) [m];
  *               form 0 launch_bert_embed_ln, 1 launch_bert_embed_typed_ln; out0 / out1 as LINEAR_LN
- *   POOL        in: x [m, hidden]; offsets; launch_bert_pool: out0 = [n_docs, hidden] */
+ *   POOL        in: x [m, hidden]; offsets; launch_bert_pool: out0 = [n_docs, hidden]
+ *   CLS_HEAD    the cross-encoder's head, launch_bert_cls_head over m pairs: in: x_cls [m, hidden], pool_w [hidden, hidden], pool_b [hidden],
+ *               cls_w [hidden], cls_b [1]; out0 = logits [m], out1 = scores [m].  hidden as bert_rerank_supported has it (a multiple of 64,
+ *               <= 1024) */
 #define FSGPU_LAB_BERT_ATTENTION 0
 #define FSGPU_LAB_BERT_LINEAR 1
 #define FSGPU_LAB_BERT_LINEAR_LN 2
 #define FSGPU_LAB_BERT_POST_ATTN 3
 #define FSGPU_LAB_BERT_EMBED_LN 4
 #define FSGPU_LAB_BERT_POOL 5
+#define FSGPU_LAB_BERT_CLS_HEAD 6
 typedef struct fsgpu_lab_bert_stage_args {
     uint32_t stage, form, epilogue;
     uint32_t m, n, k, hidden, inter, n_docs, vocab, max_pos;
@@ -88,6 +92,39 @@ typedef struct fsgpu_lab_bert_stage_args {
     float *out0, *out1;
 } fsgpu_lab_bert_stage_args;
 fsgpu_status fsgpu_lab_bert_stage(int32_t device, const fsgpu_lab_bert_stage_args *args);
+/* ONE launch of the encoder's int8 dynamic-quant mode (bert_int8.hip) on host arrays, through the launch_bert_i8_* function
+ * NativeEmbedder::forward_int8 calls: for kernel-level tests against tests/int8_stage_ref.py.  int8 codes cross the boundary as they are
+ * (one byte each), f32 as they are.  Shapes are the launchers' own: n and k multiples of 64, hidden a multiple of 64 and <= 1024; k is
+ * capped at 4096 here (127 x 127 x k must stay below 2^31: the accumulator is i32); anything else is FSGPU_ERR_INVALID_CONFIG with nothing
+ * launched.  Arguments are checked before a device is looked for.  Every output lies between guard bands as for fsgpu_lab_bert_stage.
+ *   QUANT_ROWS     in: x [m, k].  form 0 launch_bert_i8_quant_rows (f32 rows); form 1 launch_bert_i8_quant_rows_h: x is rounded to f16 on
+ *                  the device (launch_bert_to_half) first.  out_codes [m, k], out_scales [m]
+ *   PACK_W         launch_bert_i8_pack_w.  in: w [n, k]; out_codes = the n k packed bytes in fragment order, out_scales = sw [n]
+ *   GEMM           launch_bert_i8_pack_w then launch_bert_i8_gemm.  codes [m, k] (the activation codes, given directly), in: sa [m],
+ *                  w [n, k], bias [n]; epilogue 0 bias, 1 bias + GELU; out_f32 = y [m, n]
+ *   EMBED_LN_QUANT launch_bert_i8_embed_ln_quant.  ids, positions [m]; in: word [vocab, hidden], pos [max_pos, hidden], type0 [hidden],
+ *                  ln_w, ln_b; out_f32 = x [m, hidden], out_codes [m, hidden], out_scales [m]
+ *   ADD_LN_QUANT   launch_bert_i8_add_ln_quant.  in: x [m, hidden] (updated in place on the device), delta [m, hidden], ln_w, ln_b;
+ *                  out_f32 = x.  form 0: out_codes, out_scales as above.  form 1 passes q = NULL as the last layer does: out_codes and
+ *                  out_scales are not written (they may be NULL); the lab still holds guard-filled code and scale buffers and returns
+ *                  FSGPU_ERR_DEVICE if the kernel touched them */
+#define FSGPU_LAB_BERT_I8_QUANT_ROWS 0
+#define FSGPU_LAB_BERT_I8_PACK_W 1
+#define FSGPU_LAB_BERT_I8_GEMM 2
+#define FSGPU_LAB_BERT_I8_EMBED_LN_QUANT 3
+#define FSGPU_LAB_BERT_I8_ADD_LN_QUANT 4
+typedef struct fsgpu_lab_bert_int8_stage_args {
+    uint32_t stage, form, epilogue;
+    uint32_t m, n, k, hidden, vocab, max_pos;
+    float eps;
+    const int32_t *ids, *positions;
+    const int8_t *codes;
+    const float *in[5];
+    float *out_f32;
+    int8_t *out_codes;
+    float *out_scales;
+} fsgpu_lab_bert_int8_stage_args;
+fsgpu_status fsgpu_lab_bert_int8_stage(int32_t device, const fsgpu_lab_bert_int8_stage_args *args);
 /* ONE stage of the two short-text forwards on host arrays, through the launcher the embedder calls and with the argument block filled
  * as NativeEmbedder::forward_query / embed_docs fill it: for kernel-level tests against tests/encoder_short_ref.py.  MiniLM-L6 shape
  * only (hidden 384, inter 1536, heads 12; anything else is FSGPU_ERR_INVALID_CONFIG, nothing launched; arguments are checked before a

@@ -4,6 +4,7 @@ collected.
 Per row (a weight's output channel, or a row of a linear's input):
     amax = max |x|;  inv = 127.0f / amax;  q = clamp(round_half_away(x * inv), -127, 127);  scale = amax / 127.0f
     an all-zero row: q = 0, scale = 0.  Both divisions and the product are IEEE f32.
+    a row with 0 < amax < 127 / FLT_MAX has inv = +inf: its zeros code to 0, its other elements to +-127.
 Linear:  acc = sum_k qx * qw (exact);  y = ((float)acc * (sx[m] * sw[n])) + b[n], each an f32 operation.
 
 The quotient x * inv is formed in f32 and rounded half away from zero in f64 (exact: |x * inv| < 2^8 has at most 24 significant
@@ -32,8 +33,10 @@ def quantize_rows(x: np.ndarray):
     s = np.zeros(x.shape[0], F)
     nz = amax > 0
     if np.any(nz):
-        inv = (F(127.0) / amax[nz]).astype(F)
-        v = (x[nz] * inv[:, None]).astype(F)
+        # 0 < amax < 127 / FLT_MAX: inv = +inf (the tiny-amax rule): a non-zero element goes to +-inf and codes to +-127, a zero stays 0
+        with np.errstate(over="ignore", invalid="ignore"):
+            inv = (F(127.0) / amax[nz]).astype(F)
+            v = np.where(x[nz] == 0, F(0.0), (x[nz] * inv[:, None]).astype(F))
         q[nz] = np.clip(round_half_away(v), -127, 127).astype(np.int8)
         s[nz] = (amax[nz] / F(127.0)).astype(F)
     return q, s
