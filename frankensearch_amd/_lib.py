@@ -234,6 +234,21 @@ SIGNATURES = {
     "fsgpu_index_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
     "fsgpu_sharded_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
     "fsgpu_lab_index_knn_build_stats": (_i32, [_vp, _vp]),
+    "fsgpu_ann_config_default": (_i32, [_vp]),
+    "fsgpu_ann_create": (_i32, [_vp, _vp, _u64, _u32, _vp, C.POINTER(_vp)]),
+    "fsgpu_ann_destroy": (None, [_vp]),
+    "fsgpu_ann_record_count": (_u64, [_vp]),
+    "fsgpu_ann_device": (_i32, [_vp]),
+    "fsgpu_ann_search_batched": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ann_search_batched_device_queries": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ann_search": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ann_last_stats": (_i32, [_vp, _vp]),
+    "fsgpu_ann_certify_ef": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "fsgpu_conformal_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
+    "fsgpu_mean_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
+    "fsgpu_mean_recall_lower_bound_bernstein": (C.c_double, [_vp, _u64, C.c_double]),
+    "fsgpu_certified_min_ef": (_i32, [_vp, _vp, _vp, _u32, C.c_double, C.c_double, _vp]),
+    "fsgpu_certified_min_ef_mean": (_i32, [_vp, _vp, _vp, _u32, C.c_double, C.c_double, _vp]),
     "fsgpu_smooth_config_default": (_i32, [_vp]),
     "fsgpu_neighbor_smooth": (_i32, [_vp, _u32, _vp, _u64, _u32, _vp, _i32, C.POINTER(C.c_uint8)]),
     "fsgpu_rrf_fuse": (_i32, [_vp, _u32, _vp, _u32, C.c_double, C.c_double, C.c_double, _i32, _u32, _u32, _vp,

@@ -22,6 +22,7 @@
 #include "hash_embedder.hpp"
 #include "wordpiece.hpp"
 #include "index_builder.hpp"
+#include "ann_index.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
 #include "two_tier_index.hpp"
@@ -112,6 +113,10 @@ struct fsgpu_hash {
 struct fsgpu_wordpiece {
     fsgpu::WordPieceTokenizer impl;
 };
+struct fsgpu_ann {   // a k-NN table resident on an index's device; searches take the index's locks
+    fsgpu::AnnIndex impl;
+    fsgpu_index* idx = nullptr;
+};
 namespace {
 
 thread_local std::string g_last_error;
@@ -124,6 +129,27 @@ fsgpu_status finish(const fsgpu::SearchError& e) {
 fsgpu_status fail(fsgpu_status code, const char* detail) {
     g_last_error = detail;
     return code;
+}
+
+void ann_stats_out(const fsgpu::AnnStats& s, fsgpu_ann_stats* out) {
+    out->index_size = s.index_size;
+    out->dimension = s.dimension;
+    out->ef_search = s.ef_search;
+    out->k_requested = s.k_requested;
+    out->launches = s.launches;
+    out->queries = s.queries;
+    out->approximate = s.approximate;
+    out->underfilled = s.underfilled;
+    out->empty_despite_indexed_points = s.empty_despite_indexed_points;
+    out->rows_scored = s.rows_scored;
+    out->steps = s.steps;
+    out->device_ms = s.device_ms;
+}
+
+void certified_out(const fsgpu::CertifiedEf& c, fsgpu_certified_ef* out) {
+    out->ef_search = c.ef_search;
+    out->meets_target = c.meets_target ? 1u : 0u;
+    out->certified_recall = c.certified_recall;
 }
 
 template <typename F>
@@ -1733,6 +1759,140 @@ fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded* sh, uint64_t first_row
         if (n_rows && !out_rows) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_rows is null");
         return finish(sh->impl.build_knn_graph(first_row, n_rows, m, out_rows, out_sims));
     });
+}
+
+// ---- graph ANN search over the k-NN table (ann_index.cpp, ann_kernels.hip; hnsw.rs:842-1330, 1354-1386) ----
+fsgpu_status fsgpu_ann_config_default(fsgpu_ann_config* config) {
+    if (!config) return fail(FSGPU_ERR_NULL_ARGUMENT, "config is null");
+    const fsgpu::AnnConfig d;
+    std::memset(config, 0, sizeof(*config));
+    config->n_entry = d.n_entry;
+    config->degree = d.degree;
+    config->expand = d.expand;
+    config->max_iters = d.max_iters;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_ann_create(fsgpu_index* idx, const uint32_t* graph_rows, uint64_t graph_len, uint32_t graph_width,
+                              const fsgpu_ann_config* config, fsgpu_ann** out) {
+    if (!idx || !out || (!graph_rows && graph_len)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    fsgpu::AnnConfig c;
+    if (config) {
+        for (uint32_t r : config->reserved)
+            if (r) return fail(FSGPU_ERR_INVALID_CONFIG, "reserved words of fsgpu_ann_config must be 0");
+        c.n_entry = config->n_entry;
+        c.degree = config->degree;
+        c.expand = config->expand;
+        c.max_iters = config->max_iters;
+    }
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        auto a = std::make_unique<fsgpu_ann>();
+        a->idx = idx;
+        const fsgpu::SearchError e = a->impl.init(&idx->impl, graph_rows, graph_len, graph_width, c);
+        if (!e.ok()) return finish(e);
+        *out = a.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_ann_destroy(fsgpu_ann* ann) { delete ann; }
+uint64_t fsgpu_ann_record_count(const fsgpu_ann* ann) { return ann ? ann->impl.record_count() : 0; }
+int32_t fsgpu_ann_device(const fsgpu_ann* ann) { return ann ? ann->impl.device() : -1; }
+
+static fsgpu_status ann_search_common(fsgpu_ann* ann, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t ef,
+                                      uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* out_flags, bool on_device,
+                                      fsgpu_ann_stats* stats) {
+    if (!ann) return fail(FSGPU_ERR_NULL_ARGUMENT, "handle is null");
+    if (nq && (!queries || !out_counts || !out_rows || !out_scores)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ann->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ann->idx->impl.mutex());
+        fsgpu::AnnStats st;
+        const fsgpu::SearchError e = ann->impl.search(queries, nq, query_len, k, ef, out_rows, out_scores, out_counts, out_flags, on_device, &st);
+        if (e.ok() && stats) ann_stats_out(st, stats);
+        return finish(e);
+    });
+}
+
+fsgpu_status fsgpu_ann_search_batched(fsgpu_ann* ann, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t ef,
+                                      uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* out_flags,
+                                      fsgpu_ann_stats* stats) {
+    return ann_search_common(ann, queries, nq, query_len, k, ef, out_rows, out_scores, out_counts, out_flags, false, stats);
+}
+
+fsgpu_status fsgpu_ann_search_batched_device_queries(fsgpu_ann* ann, const float* queries_dev, uint32_t nq, uint32_t query_len,
+                                                     uint32_t k, uint32_t ef, uint32_t* out_rows_dev, float* out_scores_dev,
+                                                     uint32_t* out_counts_dev, uint32_t* out_flags_dev, fsgpu_ann_stats* stats) {
+    return ann_search_common(ann, queries_dev, nq, query_len, k, ef, out_rows_dev, out_scores_dev, out_counts_dev, out_flags_dev, true, stats);
+}
+
+fsgpu_status fsgpu_ann_search(fsgpu_ann* ann, const float* query, uint32_t query_len, uint32_t k, uint32_t ef, uint32_t* out_rows,
+                              float* out_scores, uint32_t* out_count, uint32_t* out_flag, fsgpu_ann_stats* stats) {
+    return ann_search_common(ann, query, 1, query_len, k, ef, out_rows, out_scores, out_count, out_flag, false, stats);
+}
+
+fsgpu_status fsgpu_ann_last_stats(const fsgpu_ann* ann, fsgpu_ann_stats* stats) {
+    if (!ann || !stats) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(ann->idx->impl.mutex());
+    ann_stats_out(ann->impl.last_stats(), stats);
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_ann_certify_ef(fsgpu_ann* ann, const float* queries, uint32_t nq, const uint32_t* candidate_efs, uint32_t n_efs,
+                                  uint32_t k, double target, double alpha, fsgpu_certified_ef* chosen, fsgpu_certified_ef* sweep_out,
+                                  uint32_t* n_swept) {
+    if (!ann || !chosen || !sweep_out || !n_swept || (!queries && nq) || (!candidate_efs && n_efs))
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ann->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ann->idx->impl.mutex());
+        std::vector<fsgpu::CertifiedEf> sweep(n_efs);
+        fsgpu::CertifiedEf best;
+        uint32_t swept = 0;
+        const fsgpu::SearchError e = ann->impl.certify_ef(queries, nq, candidate_efs, n_efs, k, target, alpha, &best, sweep.data(), &swept);
+        if (!e.ok()) return finish(e);
+        for (uint32_t i = 0; i < swept; ++i) certified_out(sweep[i], &sweep_out[i]);
+        certified_out(best, chosen);
+        *n_swept = swept;
+        return FSGPU_OK;
+    });
+}
+
+double fsgpu_conformal_recall_lower_bound(const double* recalls, uint64_t n, double alpha) {
+    return (recalls || !n) ? fsgpu::conformal_recall_lower_bound(recalls, n, alpha) : 0.0;
+}
+double fsgpu_mean_recall_lower_bound(const double* recalls, uint64_t n, double delta) {
+    return (recalls || !n) ? fsgpu::mean_recall_lower_bound(recalls, n, delta) : 0.0;
+}
+double fsgpu_mean_recall_lower_bound_bernstein(const double* recalls, uint64_t n, double delta) {
+    return (recalls || !n) ? fsgpu::mean_recall_lower_bound_bernstein(recalls, n, delta) : 0.0;
+}
+
+static fsgpu_status certified_min_ef_common(const uint32_t* efs, const double* const* recalls, const uint64_t* lens, uint32_t n, double target,
+                                            double level, bool mean_bound, fsgpu_certified_ef* out) {
+    if (!out || (n && (!efs || !recalls || !lens))) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    for (uint32_t i = 0; i < n; ++i)
+        if (!recalls[i] && lens[i]) return fail(FSGPU_ERR_NULL_ARGUMENT, "a recall sample is null");
+    return guarded([&]() -> fsgpu_status {
+        fsgpu::CertifiedEf c;
+        if (!fsgpu::certified_min_ef(efs, recalls, lens, n, target, level, mean_bound, &c))
+            return fail(FSGPU_ERR_INVALID_CONFIG, "the calibration is empty");
+        certified_out(c, out);
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_certified_min_ef(const uint32_t* efs, const double* const* recalls, const uint64_t* lens, uint32_t n, double target,
+                                    double alpha, fsgpu_certified_ef* out) {
+    return certified_min_ef_common(efs, recalls, lens, n, target, alpha, false, out);
+}
+
+fsgpu_status fsgpu_certified_min_ef_mean(const uint32_t* efs, const double* const* recalls, const uint64_t* lens, uint32_t n,
+                                         double target, double delta, fsgpu_certified_ef* out) {
+    return certified_min_ef_common(efs, recalls, lens, n, target, delta, true, out);
 }
 
 // The same pairing over two row-sharded handles: the walk runs over their catalogs (fsgpu_sharded_open_fsvi) — raw shards pair by

@@ -555,6 +555,34 @@ struct KnnEmitArgs {
 };
 hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
 
+// ann_kernels.hip: the beam search over a k-NN table (ann_index.cpp; include/fsgpu.h, "graph ANN search").  One
+// workgroup per query; everything of a query but its slab rows lives in LDS.
+constexpr uint32_t kAnnMaxEf = 256;             // beam entries
+constexpr uint32_t kAnnMaxExpand = 8;
+constexpr uint32_t kAnnMaxStepRows = 512;       // expand * degree: the rows one step can walk
+constexpr uint32_t kAnnMaxAdmitted = 4096;      // max_iters * expand * degree: the rows the steps of a query can admit ...
+constexpr uint32_t kAnnTableSlots = 8192;       // ... into an open-addressing table that stays at most half full
+constexpr uint32_t kAnnMaxEntry = 65536;        // entry rows (they do not occupy the table)
+constexpr uint32_t kAnnMaxDim = 16384;          // the query sits in LDS as f32
+struct AnnSearchArgs {
+    const void* slab;            // the index's rows (f16 or f32)
+    const u64* live;             // bit r set = row r live; nullptr = all live
+    const uint32_t* graph;       // [nrows, width] global row ids, kKnnPadRow ends a list (device)
+    const float* queries;        // [nq, dim] f32 (device)
+    uint32_t nrows, dim, row_base, row_stride, slab_f32;
+    int32_t hreduce;
+    uint32_t width, degree, expand, max_iters, n_entry;   // 1 <= degree <= width, n_entry <= nrows
+    uint32_t k, ef;              // 1 <= k <= ef <= kAnnMaxEf
+    uint32_t* out_rows;          // [nq, k] global rows, best first; kKnnPadRow past the count
+    float* out_scores;           // [nq, k]; 0.0f past the count
+    uint32_t* out_counts;        // [nq]
+    uint32_t* out_scored;        // [nq] rows scored (entry rows and admitted rows)
+    uint32_t* out_steps;         // [nq] steps taken
+};
+bool ann_args_ok(const AnnSearchArgs& args);   // what the launcher refuses with hipErrorInvalidValue (host code, no device needed)
+size_t ann_lds_bytes(uint32_t dim);
+hipError_t launch_ann_search(const AnnSearchArgs& args, uint32_t nq, hipStream_t stream);
+
 // search_hits_kernels.hip: the WAL half and the resolve step of the batched search_hits (vector_index_hits.cpp)
 constexpr uint32_t kHitsMaxK = 256;
 struct WalTopkArgs {

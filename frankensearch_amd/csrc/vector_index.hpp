@@ -265,6 +265,10 @@ class VectorIndex {
     KnnBuildStats last_knn_build;
     // ... a row shard's half of the sharded build: n live local rows (src_local) widened to f32 into a host block [n, dim]
     SearchError knn_stage_rows_host(const uint32_t* src_local, uint32_t n, float* out);
+    // The beam search over a k-NN table of this index (ann_index.cpp, ann_kernels.hip): `a` arrives with the table, the parameters,
+    // the queries and the outputs; the slab, the live bitmap AS IT IS NOW, the shape and the hreduce order are filled in here.
+    // Refused before the launch when the caps of ann_args_ok do not hold.  Enqueues on `stream`.
+    SearchError ann_launch(AnnSearchArgs a, uint32_t nq, hipStream_t stream);
 
     // VectorIndex::append_batch (lib.rs:2546-2720): every entry validated before anything changes, last-wins dedup inside the batch,
     // resident copies superseded, the first live main row of each doc id tombstoned, ONE live-bitmap upload.  wal_append is a batch of one.

@@ -566,6 +566,12 @@ class VectorIndex:
                                                      _ptr(rows) if rows.size else None, _ptr(sims) if want_sims and sims.size else None))
         return (rows, sims) if want_sims else rows
 
+    def build_ann(self, m: int = 16, **config):
+        """build_knn_graph(m) followed by fsgpu_ann_create: an AnnIndex over this index's exact k-NN table (ann.py; n_entry, degree,
+        expand and max_iters as keywords)."""
+        from .ann import AnnConfig, AnnIndex
+        return AnnIndex(self, self.build_knn_graph(m), AnnConfig(**config))
+
     def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
         """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes
         into `rows` (and the pool x pool f64 similarity matrix with want_sims)."""

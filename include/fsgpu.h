@@ -1238,6 +1238,129 @@ fsgpu_status fsgpu_smooth_config_default(fsgpu_smooth_config *config);
 fsgpu_status fsgpu_neighbor_smooth(fsgpu_scored_doc *hits, uint32_t n, const uint32_t *graph_rows, uint64_t graph_len,
                                    uint32_t graph_width, const fsgpu_smooth_config *config, int32_t resort, uint8_t *out_applied);
 
+/* ---- graph ANN search over the k-NN table, with certified recall ---- */
+/* The reference's `ann` feature: HnswIndex::knn_search_with_stats (crates/frankensearch-index/src/hnsw.rs:842-1330), which
+ * TwoTierIndex::search_fast prefers when a sidecar exists, and the certificate that turns it on without a human sign-off
+ * (recall_certificate.rs, HnswIndex::certify_ef_search, hnsw.rs:1354-1386).  The graph here is NOT an HNSW: it is the exact [N, m]
+ * neighbour table of fsgpu_index_build_knn_graph, searched with a beam.  What is kept of the reference is the interface: k and ef per
+ * call, the underfill fallback to the exact search (hnsw.rs:299-309, 1150-1190), the stats, the certificate.
+ * THE ANSWER IS A PURE FUNCTION of (slab, live bitmap, table, query, parameters), returned bit for bit in any batch:
+ *   scores  every score is the exact search's: dot_product_f16_bytes_f32 / dot_product_f32_bytes_f32 in the index's current hreduce
+ *           order — the bits fsgpu_gather_dot returns for that row.
+ *   order   the reference's total order (search.rs:91-126): score descending with NaN as -inf, row ascending.
+ *   entry   the rows e_i = floor(i * N / n_entry), i < n_entry; the live ones are scored and become VISITED; the beam is the best ef
+ *           of them, none expanded yet.
+ *   step    take the first `expand` unexpanded beam entries in beam order (none: stop) and mark them expanded; walk each one's list
+ *           in the table — the first `degree` columns, stopping at the first 0xffffffff; a walked row is ADMITTED if it lies inside
+ *           the index, is live (the bitmap is read at search time: deletes made after the build are honoured) and is not visited;
+ *           admitted rows become visited and are scored, a row reached twice in one step counts once; the beam becomes the best ef of
+ *           (beam + admitted), entries keep their expanded flag.
+ *   end     at most max_iters steps; the answer is the first min(k, |beam|) entries, rows and scores, and that count.  Entries of
+ *           out_rows / out_scores past the count are unspecified.  Row ids are global (row_base is added, as in the table).
+ * Visited is a set: nothing depends on insertion order, hash layout or which lane won a race.
+ * FALLBACK (hnsw.rs:299-309): a query whose count is below min(k, live rows) is answered again by the handle's exact batched search
+ * and flagged FSGPU_ANN_UNDERFILLED, or FSGPU_ANN_EMPTY_DESPITE_INDEXED_POINTS when its count was 0.  Flag 0: the answer is the
+ * approximate one.  AnnSearchStats::estimated_recall (0.9 + 0.1 log2(ef / k), which the reference itself calls ungrounded) is left
+ * out: the certificate below replaces it.
+ * LIMITS, checked before any launch (FSGPU_ERR_INVALID_CONFIG): 1 <= k <= ef <= 256; 1 <= expand <= 8; max_iters >= 1;
+ * expand * degree <= 512 (the rows of one step); max_iters * expand * degree <= 4,096 (the visited set is an open-addressing table
+ * of 8,192 rows in LDS, at most half full; entry rows do not occupy it: membership in the strided entry set is arithmetic);
+ * n_entry <= 65,536 after clamping to N; dimension <= 16,384 (the query sits in LDS as f32).
+ * HOW IT RUNS (ann_kernels.hip): one workgroup of 256 threads per query; a quad of lanes scores one row, 64 rows per pass; the beam
+ * and the step's admitted keys are packed 64-bit keys in LDS, the step's keys are sorted with the block sort and merged into the
+ * beam by rank; the expanded flags lie beside the keys.  Every table, list and row index is checked against N before it is used as
+ * an address: the table is the caller's.  No inter-workgroup communication.  F16 and F32 slabs, every hreduce order, any dimension.
+ * Out of scope: allow-bitmap filters, WAL entries and doc-id dedup (row-level, like fsgpu_search_topk), sharded handles. */
+typedef struct fsgpu_ann fsgpu_ann;
+typedef struct fsgpu_ann_config {
+    uint32_t n_entry;   /* entry rows; clamped to record_count.  Default 1,024 */
+    uint32_t degree;    /* columns of a list that are walked; 0 = the table's width.  Default 0 */
+    uint32_t expand;    /* beam entries expanded per step, 1 .. 8.  Default 4 */
+    uint32_t max_iters; /* steps at most, >= 1.  Default 64 */
+    uint32_t reserved[4]; /* must be 0 */
+} fsgpu_ann_config;
+enum {
+    FSGPU_ANN_APPROXIMATE = 0,
+    FSGPU_ANN_UNDERFILLED = 1,                  /* AnnFallbackReason::Underfilled (hnsw.rs:304) */
+    FSGPU_ANN_EMPTY_DESPITE_INDEXED_POINTS = 2  /* AnnFallbackReason::EmptyDespiteIndexedPoints (hnsw.rs:308) */
+};
+/* AnnSearchStats (hnsw.rs:266-297) summed over one call.  For fsgpu_ann_certify_ef: summed over the launches of the sweep, with
+ * ef_search the LARGEST ef that was launched. */
+typedef struct fsgpu_ann_stats {
+    uint64_t index_size;   /* record_count */
+    uint32_t dimension;
+    uint32_t ef_search;
+    uint32_t k_requested;
+    uint32_t launches;     /* launches of the ANN kernel */
+    uint64_t queries;
+    uint64_t approximate, underfilled, empty_despite_indexed_points; /* queries per flag value */
+    uint64_t rows_scored;  /* entry rows and admitted rows */
+    uint64_t steps;
+    double device_ms;      /* the ANN kernel's launches, by device events (the fallback's exact search is not in it) */
+} fsgpu_ann_stats;
+fsgpu_status fsgpu_ann_config_default(fsgpu_ann_config *config);
+/* HnswIndex::load over an index's table (hnsw.rs:700-840 is the sidecar loader): graph_rows [graph_len, graph_width] is the HOST
+ * table fsgpu_index_build_knn_graph wrote (its out_rows, first_row 0), uploaded once to the index's device.  graph_len must equal
+ * record_count and graph_width >= 1; a NULL config means the defaults.  The handle records fsgpu_index_generation: after a compaction
+ * or a vacuum that moved rows every call on it is FSGPU_ERR_INVALID_CONFIG, as for an fsgpu_allow_bitmap.  The index must outlive the
+ * handle. */
+fsgpu_status fsgpu_ann_create(fsgpu_index *idx, const uint32_t *graph_rows, uint64_t graph_len, uint32_t graph_width,
+                              const fsgpu_ann_config *config, fsgpu_ann **out);
+void fsgpu_ann_destroy(fsgpu_ann *ann);
+uint64_t fsgpu_ann_record_count(const fsgpu_ann *ann);
+int32_t fsgpu_ann_device(const fsgpu_ann *ann);
+/* HnswIndex::knn_search_with_stats (hnsw.rs:842-1330) for nq queries: queries [nq, query_len] f32, out_rows / out_scores [nq, k],
+ * out_counts / out_flags [nq] (out_flags and stats may be NULL), HOST pointers; the call blocks.  query_len must equal the index's
+ * dimension (FSGPU_ERR_DIMENSION_MISMATCH), as in fsgpu_search_topk_batched.  On any error nothing is written. */
+fsgpu_status fsgpu_ann_search_batched(fsgpu_ann *ann, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t ef,
+                                      uint32_t *out_rows, float *out_scores, uint32_t *out_counts, uint32_t *out_flags,
+                                      fsgpu_ann_stats *stats);
+/* The same with queries and outputs in the memory of the index's device (an encoder's output in, a reranker's input out); stats is
+ * a host struct.  Same bits as the host form.  Blocks: the fallback decision is taken on the host. */
+fsgpu_status fsgpu_ann_search_batched_device_queries(fsgpu_ann *ann, const float *queries_dev, uint32_t nq, uint32_t query_len,
+                                                     uint32_t k, uint32_t ef, uint32_t *out_rows_dev, float *out_scores_dev,
+                                                     uint32_t *out_counts_dev, uint32_t *out_flags_dev, fsgpu_ann_stats *stats);
+/* A batch of one (hnsw.rs:842). */
+fsgpu_status fsgpu_ann_search(fsgpu_ann *ann, const float *query, uint32_t query_len, uint32_t k, uint32_t ef, uint32_t *out_rows,
+                              float *out_scores, uint32_t *out_count, uint32_t *out_flag, fsgpu_ann_stats *stats);
+/* The stats of the last search or certify call on the handle. */
+fsgpu_status fsgpu_ann_last_stats(const fsgpu_ann *ann, fsgpu_ann_stats *stats);
+
+/* The recall certificates (recall_certificate.rs:50-230) restated in f64, on the host.  Non-finite entries are ignored.
+ * conformal_recall_lower_bound (:50-73): the floor(alpha (n + 1))-th smallest recall (1-indexed) clamped to [0, 1]; 0 when that rank
+ * is 0, the sample is empty or alpha is outside [0, 1). */
+double fsgpu_conformal_recall_lower_bound(const double *recalls, uint64_t n, double alpha);
+/* mean_recall_lower_bound (:88-102), Hoeffding: mean - sqrt(ln(1 / delta) / (2 n)) clamped to [0, 1]; the sum runs in array order. */
+double fsgpu_mean_recall_lower_bound(const double *recalls, uint64_t n, double delta);
+/* mean_recall_lower_bound_bernstein (:122-138), Maurer and Pontil: mean - sqrt(2 V ln(2 / delta) / n) - 7 ln(2 / delta) / (3 (n - 1))
+ * with V the unbiased sample variance, clamped to [0, 1]; 0 for n < 2. */
+double fsgpu_mean_recall_lower_bound_bernstein(const double *recalls, uint64_t n, double delta);
+/* CertifiedEf (:143-152). */
+typedef struct fsgpu_certified_ef {
+    uint32_t ef_search;
+    uint32_t meets_target;     /* certified_recall >= target */
+    double certified_recall;
+} fsgpu_certified_ef;
+/* certified_min_ef (:165-191): calibration entry i is (efs[i], recalls[i][0 .. lens[i])).  In ascending ef (equal efs in the order
+ * given) the first whose conformal bound meets the target; else the one with the highest bound (the first of equals), with
+ * meets_target = 0.  n == 0 is FSGPU_ERR_INVALID_CONFIG (the reference's None). */
+fsgpu_status fsgpu_certified_min_ef(const uint32_t *efs, const double *const *recalls, const uint64_t *lens, uint32_t n, double target,
+                                    double alpha, fsgpu_certified_ef *out);
+/* certified_min_ef_mean (:206-230): the same over the empirical-Bernstein bound of the mean. */
+fsgpu_status fsgpu_certified_min_ef_mean(const uint32_t *efs, const double *const *recalls, const uint64_t *lens, uint32_t n,
+                                         double target, double delta, fsgpu_certified_ef *out);
+/* HnswIndex::certify_ef_search (hnsw.rs:1354-1386) through calibrate_certified_ef (recall_certificate.rs:259-292).  queries
+ * [nq, dimension] are host values.  The exact top-k comes ONCE per query from the handle's exact batched search; the candidates are
+ * de-duplicated and taken in ascending ef; a query's recall is recall_at_k_of over rows (hnsw.rs:3101-3112: the share of the exact
+ * rows that the approximate answer holds, 1.0 when the exact answer is empty), and 0.0 when the query was flagged
+ * (certified_ann_recall_sample, hnsw.rs:3114-3122).  The sweep stops at the first ef whose conformal bound meets the target: no ANN
+ * launch happens at a larger ef.  sweep_out holds n_efs entries and receives one per ef measured (*n_swept); *chosen is the last of
+ * them when it meets the target, else the entry with the highest bound.  Every candidate must satisfy k <= ef <= 256 and
+ * n_efs >= 1, checked before any launch. */
+fsgpu_status fsgpu_ann_certify_ef(fsgpu_ann *ann, const float *queries, uint32_t nq, const uint32_t *candidate_efs, uint32_t n_efs,
+                                  uint32_t k, double target, double alpha, fsgpu_certified_ef *chosen, fsgpu_certified_ef *sweep_out,
+                                  uint32_t *n_swept);
+
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */
 typedef struct fsgpu_mrl_stats {
