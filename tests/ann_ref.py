@@ -38,7 +38,6 @@ def search(scores, live, graph, k, ef, n_entry=1024, degree=0, expand=4, max_ite
     alive = np.ones(n, dtype=bool) if live is None else np.asarray(live, dtype=bool)
     ords = score_ord(scores.view(np.uint32)).tolist()
     key = lambda r: (-ords[r], r)   # best first: score key descending, row ascending
-    glist = graph.tolist()
 
     start = [e for e in entry_rows(n, n_entry) if alive[e]]
     visited = set(start)
@@ -54,7 +53,7 @@ def search(scores, live, graph, k, ef, n_entry=1024, degree=0, expand=4, max_ite
         expanded.update(chosen)
         admitted = []
         for p in chosen:
-            for g in glist[p][:degree]:
+            for g in graph[p, :degree].tolist():   # (only the lists that are walked become Python lists: tables of 2^18 rows)
                 if g == PAD:
                     break
                 r = g - row_base

@@ -229,3 +229,111 @@ def test_iid_rows_make_the_search_truly_approximate(oracle):
     print(f"recall@10 over {len(queries)} iid queries: ef 16 {lo:.3f}, ef 128 {hi:.3f}; differing from exact at ef 16: {differing}")
     assert differing >= 1
     assert hi > lo
+
+
+# ---- the hand-made cases of test_gpu_ann_shapes.py can see the mistakes they aim at ----
+
+import ann_cases as C  # noqa: E402
+
+
+def test_a_plain_left_to_right_dot_differs_from_the_oracle_at_every_dot_dimension(oracle):
+    """The dot cases compare score BITS, which only proves the kernel's accumulation order if another order gives other bits on the
+    very rows and queries the GPU test uses.  Share of (query, row) pairs whose plain left-to-right f32 dot differs from the oracle's,
+    printed per dimension; above dimension 8 it must not be zero.  Up to 8 there is at most one chunk — one product per accumulator
+    and the horizontal add, or the fused tail alone — and the share is whatever it is: printed, not asserted."""
+    for f32, dims in ((False, list(C.F16_VECTOR_DIMS) + list(C.F16_ELEMENT_DIMS)), (True, list(C.F32_VECTOR_DIMS) + list(C.F32_ELEMENT_DIMS))):
+        for dim in sorted(dims):
+            c = C.dot_case(dim, f32)
+            want = C.score_table(oracle, c["slab"], c["queries"], f32, 0)
+            share = float((bits(C.plain_dot(c["slab"], c["queries"], f32)) != bits(want)).mean())
+            print(f"{'f32' if f32 else 'f16'} slab, dimension {dim}: plain dot differs in {share:.4f} of the scores")
+            if dim > 8:
+                assert share > 0.0, (f32, dim)
+
+
+def _answers(c, scores, k, ef, cfg, mutation):
+    return [C.mutated_search(scores[i], c["live"], c["table"], k, ef, mutation, row_base=c["row_base"], **cfg)
+            for i in range(len(c["queries"]))]
+
+
+def _changed(c, scores, k, ef, cfg, mutation):
+    """Queries whose answer (rows, in order) differs under the mutation."""
+    a, b = _answers(c, scores, k, ef, cfg, None), _answers(c, scores, k, ef, cfg, mutation)
+    return [i for i in range(len(a)) if a[i][2] != b[i][2] or (a[i][0] != b[i][0]).any()]
+
+
+def test_the_restated_search_without_a_mutation_is_ann_ref(oracle):
+    c = C.hostile_case(1000)
+    scores = C.score_table(oracle, c["slab"], c["queries"], False, 0)
+    for cfg in C.HOSTILE_CFGS:
+        for i in range(C.NQ):
+            rows, sc, count = C.mutated_search(scores[i], c["live"], c["table"], 10, 64, None, row_base=1000, **cfg)
+            wr, ws, wc, _, _ = R.search(scores[i], c["live"], c["table"], 10, 64, row_base=1000, **cfg)
+            assert count == wc and (rows == wr).all() and (bits(sc) == bits(ws)).all()
+
+
+def test_each_broken_rule_changes_an_answer_of_the_case_that_aims_at_it(oracle):
+    for row_base in (0, 1000):
+        c = C.hostile_case(row_base)
+        scores = C.score_table(oracle, c["slab"], c["queries"], False, 0)
+        for k, ef in C.K_EF:
+            for cfg in C.HOSTILE_CFGS:
+                pad = _changed(c, scores, k, ef, cfg, "walk past a pad")
+                dup = _changed(c, scores, k, ef, cfg, "no de-duplication within a step")
+                print(f"hostile table, row_base {row_base}, k {k} ef {ef} {cfg}: walking past a pad changes queries {pad}, no de-duplication {dup}")
+                assert pad and dup
+                if (k, ef) == (10, 64):   # a walk long enough to meet them: Y0 surfaces in query 1's answer, X0 twice in query 0's
+                    assert 1 in pad and 0 in dup
+    for identical in (False, True):
+        c = C.tie_case(identical)
+        scores = C.score_table(oracle, c["slab"], c["queries"], False, 0)
+        for k, ef in C.TIE_K_EF:
+            tie = _changed(c, scores, k, ef, dict(n_entry=C.N_ENTRY), "ties by row descending")
+            print(f"ties (identical rows {identical}), k {k} ef {ef}: row-descending ties change {len(tie)} of {C.NQ} queries")
+            assert tie
+    for f32 in (False, True):
+        c = C.nonfinite_case(f32)
+        scores = C.score_table(oracle, c["slab"], c["queries"], f32, 0)
+        for cfg, (k, ef) in C.NONFINITE_CFGS:
+            nan = _changed(c, scores, k, ef, cfg, "NaN above +inf")
+            print(f"non-finite scores (f32 {f32}), k {k} ef {ef} {cfg}: NaN above +inf changes {len(nan)} of {C.NQ} queries")
+            assert nan
+
+
+def test_non_finite_case_brings_every_kind_of_score_into_the_answers(oracle):
+    for f32 in (False, True):
+        c = C.nonfinite_case(f32)
+        scores = C.score_table(oracle, c["slab"], c["queries"], f32, 0)
+        kinds = set()
+        for cfg, (k, ef) in C.NONFINITE_CFGS:
+            for i in range(C.NQ):
+                _, sc, count, _, _ = R.search(scores[i], c["live"], c["table"], k, ef, **cfg)
+                assert R.flag_of(count, k, int(c["live"].sum())) == R.APPROXIMATE
+                kinds |= {"nan"} if np.isnan(sc).any() else set()
+                kinds |= {"+inf"} if np.isposinf(sc).any() else set()
+                kinds |= {"-inf"} if np.isneginf(sc).any() else set()
+        assert kinds == {"nan", "+inf", "-inf"}, (f32, kinds)
+
+
+def test_visited_table_rows_for_the_chain_case():
+    picked = C.chain_rows()
+    h = ((picked.astype(np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(19)
+    assert picked.size >= 40 and set(h.tolist()) == {8190, 8191}
+    assert not set(R.entry_rows(C.CHAIN_N, 1)) & set(picked.tolist())       # n_entry = 1: row 0 alone
+    c = C.chain_case()
+    assert set(c["table"][0].tolist()) <= set(picked.tolist()) and len(set(c["table"][0].tolist())) == C.WIDTH
+    for p in picked:
+        assert set(c["table"][p].tolist()) <= set(picked.tolist()) - {int(p)}
+    assert (np.delete(c["table"], np.concatenate([[0], picked]), axis=0) == PAD).all()
+
+
+def test_lds_boundary_dimensions_follow_from_the_kernel_constants():
+    """ann_cases.ANN_STATE_BYTES restates the kOff* layout of ann_kernels.hip; the constants it is built from are read back from
+    kernels.hpp here, so a changed limit shows up as a failure of this test rather than as a test that silently lost its boundary."""
+    import re
+    text = open(os.path.join(ROOT, "frankensearch_amd", "csrc", "kernels.hpp")).read()
+    const = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr uint32_t (kAnn\w+) = (\d+);", text)}
+    assert (const["kAnnMaxEf"], const["kAnnMaxStepRows"], const["kAnnTableSlots"], const["kAnnMaxDim"]) == (256, 512, 8192, C.ANN_MAX_DIM)
+    assert C.ANN_STATE_BYTES == 45664
+    assert C.ann_lds_bytes(4968) == 64 * 1024 and C.ann_lds_bytes(4969) == 64 * 1024 + 16 and C.ann_lds_bytes(4976) > 64 * 1024
+    assert C.ann_lds_bytes(C.ANN_MAX_DIM) == 111200 <= 160 * 1024

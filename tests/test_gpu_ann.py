@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 
 import ann_ref as R  # noqa: E402
+from ann_cases import assert_device_is_reference, bits, score_table, tombstones  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -24,53 +25,6 @@ def _fa():
     build()
     import frankensearch_amd as fa
     return fa
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(np.uint32)
-
-
-def tombstones(rng, n, n_entry=256):
-    """10 % of the rows, some of them entry rows of the strided entry set."""
-    live = np.ones(n, dtype=bool)
-    live[rng.choice(n, size=n // 10, replace=False)] = False
-    live[np.asarray(R.entry_rows(n, n_entry))[[3, 5, 100]]] = False
-    live[0] = True   # (the one entry row of n_entry = 1)
-    return live
-
-
-def score_table(oracle, slab, queries, f32, hreduce):
-    """[nq, N] exact scores of every row, by the CPU oracle."""
-    n = slab.shape[0]
-    out = np.empty((len(queries), n), dtype=F32)
-    every = np.arange(n, dtype=np.uint32)
-    for i, q in enumerate(queries):
-        if f32:
-            rows, scores = oracle.search_top_k_f32(slab, q, n, hreduce=hreduce)   # k = N: every row with its score
-            assert rows.size == n
-            out[i, rows] = scores
-        else:
-            out[i] = oracle.gather_dot(slab, q, every, hreduce)
-    return out
-
-
-def assert_device_is_reference(ann, table, scores, live, queries, k, ef, cfg, row_base, what):
-    rows, sc, counts, flags = ann.search_batched(queries, k, ef)
-    st = ann.stats
-    live_rows = int(live.sum()) if live is not None else scores.shape[1]
-    bad, want_scored, want_steps = [], 0, 0
-    for i in range(len(queries)):
-        wr, ws, wc, scored, steps = R.search(scores[i], live, table, k, ef, row_base=row_base, **cfg)
-        want_scored += scored
-        want_steps += steps
-        assert R.flag_of(wc, k, live_rows) == R.APPROXIMATE, "the case was meant to stay on the approximate path"
-        if counts[i] != wc or flags[i] != 0 or (rows[i, :wc] != wr).any() or (bits(sc[i, :wc]) != bits(ws)).any():
-            bad.append(i)
-    print(f"{what}: k {k} ef {ef} {cfg}: {len(queries)} queries, differing {len(bad)}, rows scored {st.rows_scored}, steps {st.steps}")
-    assert not bad, (what, bad[:5], rows[bad[0]], counts[bad[0]])
-    assert (st.rows_scored, st.steps) == (want_scored, want_steps)
-    assert (st.queries, st.approximate, st.underfilled, st.empty_despite_indexed_points) == (len(queries), len(queries), 0, 0)
-    assert (st.index_size, st.ef_search, st.k_requested, st.launches) == (scores.shape[1], ef, k, 1)
 
 
 def make_case(fa, oracle, corpus, dim, f32, hreduce, seed, row_base=0):

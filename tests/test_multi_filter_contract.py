@@ -136,3 +136,59 @@ def test_no_kernel_of_the_gather_file_spills(L):
     for l in lines:
         m = re.match(r"vgpr\s+(\d+)\s+vgpr_spill\s+(\d+)\s+sgpr_spill\s+(\d+)\s+private\s+(\d+)", l)
         assert m and (int(m.group(2)), int(m.group(3)), int(m.group(4))) == (0, 0, 0), l
+
+
+# ---- the cases of test_gpu_multi_filter_shapes.py (tests/multi_filter_cases.py) ----
+
+import multi_filter_cases as M  # noqa: E402
+
+
+def test_largest_gathered_dimensions_follow_from_the_lds_formula():
+    """multi_filter_cases restates gather_row_pitch, filter_gather_lds_bytes and filter_gather_supported; the constants are read back
+    from kernels.hpp, and the two limits are found again by trying every multiple of 8."""
+    text = open(os.path.join(ROOT, "frankensearch_amd", "csrc", "kernels.hpp")).read()
+    assert re.search(r"kGatherTileRows = (\d+);", text).group(1) == str(M.TILE_ROWS)
+    assert re.search(r"kGatherMaxK = (\d+);", text).group(1) == str(M.MAX_K)
+    assert re.search(r"kGatherLdsBudget = 160 \* 1024;", text) and M.LDS_BUDGET == 160 * 1024
+    assert [M.row_pitch(d) for d in (64, 384, 8, 96, 104, 928, 1056)] == [320, 832, 64, 320, 320, 1856, 2112]   # 64 mod 256, >= the row
+    dims = range(8, 4096, 8)
+    assert max(d for d in dims if M.gather_supported(d, 64)) == M.MAX_DIM_K64 == 1056
+    assert max(d for d in dims if M.gather_supported(d, 256)) == max(d for d in dims if M.gather_supported(d, 65)) == M.MAX_DIM_K256 == 928
+    assert all(M.gather_supported(d, 64) for d in range(8, M.MAX_DIM_K64 + 8, 8))        # no gap below a limit
+    assert all(M.gather_supported(d, 256) for d in range(8, M.MAX_DIM_K256 + 8, 8))
+    assert (M.lds_bytes(1056, 64), M.lds_bytes(1064, 64), M.lds_bytes(928, 256), M.lds_bytes(936, 256)) == (156416, 172928, 150272, 166784)
+    assert set(M.DIMS[d] for d in M.DIMS) >= {(0, 1), (0, 2), (0, 3), (1, 1)} and all(M.DIMS[d] == (d // 32, d // 8 % 4) for d in M.DIMS)
+
+
+def test_a_plain_left_to_right_dot_differs_from_the_oracle_at_every_gathered_dimension(oracle):
+    """Share of the filters' (query, row) pairs whose plain left-to-right f32 dot differs in bits from the oracle's, per dimension of
+    the shape test, on that test's own rows and queries: printed; above dimension 8 it must not be zero (at 8 there is one product
+    per accumulator and only the horizontal add's order is left: printed, not asserted)."""
+    for dim in sorted(M.DIMS):
+        c = M.shape_case(oracle, dim)
+        rows = np.flatnonzero(np.any(c["masks"], axis=0)).astype(np.uint32)
+        want = np.stack([oracle.gather_dot(c["slab"], q, rows) for q in c["queries"]])
+        plain = M.left_to_right(c["slab"][rows], c["queries"])
+        share = float((plain.view(np.uint32) != want.view(np.uint32)).mean())
+        print(f"dimension {dim}: plain dot differs in {share:.4f} of the scores")
+        if dim > 8:
+            assert share > 0.0, dim
+
+
+def test_tie_case_straddles_the_kth_place_and_holds_every_kind_of_score(oracle):
+    for dim in (40, 384):
+        c = M.tie_case(oracle, dim)
+        nq = c["fq"].size // 2
+        for f, k in ((0, 10), (1, 70)):
+            rows = np.sort(np.flatnonzero(c["masks"][f]))
+            assert np.array_equal(rows[list(M.TIE_DUPS)], c["dups"][f]) and rows.size == M.TIE_ALLOWED and M.TIE_ALLOWED * 50 < M.N
+            assert 60 < M.TILE_ROWS <= 70                                            # the copies lie on both sides of the first tile's end
+            assert np.unique(c["slab"][c["dups"][f]], axis=0).shape[0] == 1
+            live = c["live"] & c["masks"][f]
+            got, _ = oracle.search_top_k(c["slab"], c["queries"][f * nq], k, live=live)
+            inside = np.isin(c["dups"][f], got)
+            print(f"dim {dim} filter {f} k {k}: {int(inside.sum())} of {inside.size} equal rows inside the answer")
+            assert 0 < inside.sum() < inside.size
+            for i in range(nq):
+                _, s = oracle.search_top_k(c["slab"], c["queries"][f * nq + i], 256, live=live)
+                assert np.isnan(s).any() and (i >= 6 or (np.isposinf(s).any() and np.isneginf(s).any())), (dim, f, i)
