@@ -168,6 +168,8 @@ SIGNATURES = {
     "fsgpu_lab_scan_planner_shape": (_i32, [_i32, _i32]),
     "fsgpu_lab_select": (_i32, [_i32, _vp]),   # (fsgpu_lab_select_args: SelectLabArgs below)
     "fsgpu_lab_select_check": (_i32, [_vp]),
+    "fsgpu_lab_lone_stage": (_i32, [_i32, _vp]),   # (fsgpu_lab_lone_stage_args: LoneStageArgs below)
+    "fsgpu_lab_lone_stage_check": (_i32, [_vp]),
     "fsgpu_bert_destroy": (None, [_vp]),
     "fsgpu_bert_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "fsgpu_m2v_embed_device": (_i32, [_vp, _vp, _vp, _u32, _vp]),
@@ -324,6 +326,14 @@ class SelectLabArgs(C.Structure):
         (name, _vp) for name in ("lists", "list_counts", "extra", "spill", "exact_lists", "delta", "anchor_unit", "tau_floor_in", "slab", "live",
                                  "allow", "queries", "spill_count", "pool_flag", "tau_out", "tau_floor_out", "pool_out", "cand_counts",
                                  "overflow", "out_rows", "out_scores", "out_packed", "out_counts", "cand_approx_out", "cand_exact_out")]
+
+
+class LoneStageArgs(C.Structure):
+    """fsgpu_lab_lone_stage_args of include/fsgpu_lab.h."""
+    _fields_ = [(name, _u32) for name in ("kind", "nq", "tier", "dim", "nrows", "row_stride", "row_base", "k", "grid", "force_runtime_dim",
+                                          "plain_loads")] + [("hreduce", _i32)] + [
+        (name, _u32) for name in ("bitmap_words", "nlists", "list_len", "l_stride", "out_stride", "lists_sorted")] + [("q_stride", _u64)] + [
+        (name, _vp) for name in ("slab", "live", "allow", "queries", "partial", "lists", "out_rows", "out_scores", "out_packed", "out_counts")]
 
 
 _lib = None

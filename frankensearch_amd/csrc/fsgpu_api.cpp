@@ -3233,6 +3233,195 @@ fsgpu_status fsgpu_lab_select(int32_t device, const fsgpu_lab_select_args* args)
     });
 }
 
+namespace {
+// What fsgpu_lab_lone_stage derives from its arguments once they have passed: sizes in bytes / elements.
+struct LoneGeom {
+    size_t row_bytes = 0, slab_pitch = 0, query_bytes = 0, bitmap_words = 0, lists_n = 0;
+};
+
+fsgpu_status lone_stage_check(const fsgpu_lab_lone_stage_args& a, LoneGeom* geom) {
+    auto bad = [](const char* what) { return fail(FSGPU_ERR_INVALID_CONFIG, what); };
+    auto null = [](const char* what) { return fail(FSGPU_ERR_NULL_ARGUMENT, what); };
+    LoneGeom g;
+    if (a.kind > FSGPU_LAB_LONE_MERGE) return bad("lone: unknown kind");
+    if (a.kind == FSGPU_LAB_LONE_MERGE) {
+        if (a.nq == 0 || a.nq > 4096) return bad("lone: nq must be in 1..=4096");
+        if (a.nlists == 0 || a.list_len == 0) return bad("lone: a merge needs nlists and list_len");
+        if (a.k == 0 || a.k > 256) return bad("lone: k must be in 1..=256");
+        if (a.out_stride < a.k || a.out_stride > 4096) return bad("lone: out_stride below k, or above 4096");
+        if (a.lists_sorted > 1) return bad("lone: a flag out of range");
+        if ((uint64_t)a.nlists * a.list_len > (1u << 22)) return bad("lone: more than 2^22 entries per query");
+        const uint64_t need = (uint64_t)(a.nlists - 1) * a.l_stride + a.list_len;
+        if (a.l_stride < a.list_len || a.q_stride < need || (uint64_t)a.nq * a.q_stride > (1ull << 25))
+            return bad("lone: q_stride / l_stride do not hold the lists, or they exceed 2^25 entries");
+        g.lists_n = (size_t)a.nq * a.q_stride;
+        if (!a.lists) return null("lone: lists is null");
+        if (geom) *geom = g;
+        return FSGPU_OK;
+    }
+    const int nq = (int)a.nq, tier = (int)a.tier, dim = (int)a.dim;
+    if (a.tier != 64 && a.tier != 256) return bad("lone: tier must be 64 or 256");
+    if (a.k == 0 || a.k > a.tier) return bad("lone: k must be in 1..=tier");
+    if (a.grid == 0 || a.grid > 4096) return bad("lone: grid must be in 1..=4096");
+    if (a.nrows == 0 || a.nrows > (1u << 22)) return bad("lone: nrows must be in 1..=2^22");
+    if (a.dim == 0 || a.dim > 4096 || (a.dim & 7)) return bad("lone: dim must be a multiple of 8 up to 4096");
+    if (a.hreduce < 0 || a.hreduce > 2 || a.force_runtime_dim > 1 || a.plain_loads > 1) return bad("lone: a flag out of range");
+    if (a.kind != FSGPU_LAB_LONE_F16 && (a.force_runtime_dim || a.plain_loads)) return bad("lone: force_runtime_dim / plain_loads are launch_scan_topk's");
+    bool strided_ok = false;
+    switch (a.kind) {
+        case FSGPU_LAB_LONE_F16:
+            if (nq != 1 && nq != 2 && nq != 4) return bad("lone: launch_scan_topk takes 1, 2 or 4 queries per pass");
+            if (fsgpu::scan_lds_bytes(dim, nq, tier) > 160 * 1024) return bad("lone: the queries and lists exceed the LDS");
+            g.row_bytes = (size_t)dim * 2, g.query_bytes = (size_t)nq * dim * 4, strided_ok = true;
+            break;
+        case FSGPU_LAB_LONE_F16_HOST_QUERY:
+            if (nq != 1) return bad("lone: the host-query form takes one query");
+            if (!fsgpu::scan_kernarg_query_supported(dim, tier)) return bad("lone: scan_kernarg_query_supported refuses the shape");
+            g.row_bytes = (size_t)dim * 2, g.query_bytes = (size_t)dim * 4, strided_ok = true;
+            break;
+        case FSGPU_LAB_LONE_F16_MQ:
+            if (!fsgpu::scan_mq_supported(dim, nq, tier)) return bad("lone: scan_mq_supported refuses the shape");
+            g.row_bytes = (size_t)dim * 2, g.query_bytes = (size_t)nq * dim * 4;
+            break;
+        case FSGPU_LAB_LONE_I8:
+            if (nq != 1) return bad("lone: the int8 scan takes one query");
+            if (!fsgpu::scan_i8_fused_supported(dim, tier)) return bad("lone: scan_i8_fused_supported refuses the shape");
+            g.row_bytes = g.query_bytes = (size_t)dim;
+            break;
+        case FSGPU_LAB_LONE_I4:
+            if (nq != 1) return bad("lone: the 4-bit scan takes one query");
+            if (!fsgpu::scan_4bit_fused_supported(dim, tier)) return bad("lone: scan_4bit_fused_supported refuses the shape");
+            g.row_bytes = g.query_bytes = (size_t)dim / 2;
+            break;
+        default:
+            if (nq != 1 && nq != 2 && nq != 4) return bad("lone: launch_scan_topk_f32 takes 1, 2 or 4 queries per pass");
+            if ((size_t)nq * dim * 4 > (size_t)96 * 1024 || fsgpu::scan_lds_bytes(dim, nq, tier) > 160 * 1024)
+                return bad("lone: the queries and lists exceed the LDS");
+            g.row_bytes = (size_t)dim * 4, g.query_bytes = (size_t)nq * dim * 4, strided_ok = true;
+            break;
+    }
+    g.slab_pitch = a.row_stride ? a.row_stride : g.row_bytes;
+    if (g.slab_pitch < g.row_bytes || (g.slab_pitch & 15) || g.slab_pitch > (1u << 16)) return bad("lone: row_stride must be a multiple of 16 bytes that holds a row");
+    if (!strided_ok && g.slab_pitch != g.row_bytes) return bad("lone: this kernel reads dense rows only");
+    if ((uint64_t)a.nrows * g.slab_pitch > (1ull << 30)) return bad("lone: the slab exceeds 1 GB");
+    g.bitmap_words = ((size_t)a.nrows + 63) / 64;
+    if ((a.live || a.allow) && a.bitmap_words < g.bitmap_words) return bad("lone: a bitmap shorter than the rows");
+    if (!a.slab || !a.queries || !a.partial) return null("lone: slab, queries or partial is null");
+    if (geom) *geom = g;
+    return FSGPU_OK;
+}
+}  // namespace
+
+fsgpu_status fsgpu_lab_lone_stage_check(const fsgpu_lab_lone_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return lone_stage_check(*args, nullptr);
+}
+
+fsgpu_status fsgpu_lab_lone_stage(int32_t device, const fsgpu_lab_lone_stage_args* args) {
+    if (!args) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu_lab_lone_stage_args& a = *args;
+    LoneGeom g;
+    if (const fsgpu_status st = lone_stage_check(a, &g); st != FSGPU_OK) return st;
+    return guarded([&]() -> fsgpu_status {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible");
+        if (device < 0 || device >= count) return fail(FSGPU_ERR_INVALID_CONFIG, "device ordinal out of range");
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGPU_ERR_DEVICE, "hipSetDevice failed");
+        LabStage s;
+        // outputs: [band | body | band], the bands of kGuardByte, the body of 0xCD
+        constexpr size_t kBand = 4096;
+        struct Out {
+            unsigned char* base;
+            size_t bytes;
+            void* host;
+        };
+        std::vector<Out> outs;
+        auto out = [&](size_t bytes, void* host) -> void* {
+            if (bytes == 0 || !host) return nullptr;
+            unsigned char* base = static_cast<unsigned char*>(s.alloc(bytes + 2 * kBand));
+            if (s.ok()) s.hip(hipMemset(base, LabStage::kGuardByte, bytes + 2 * kBand));
+            if (s.ok()) s.hip(hipMemset(base + kBand, 0xCD, bytes));
+            outs.push_back({base, bytes, host});
+            return s.ok() ? base + kBand : nullptr;
+        };
+        if (a.kind == FSGPU_LAB_LONE_MERGE) {
+            fsgpu::MergeArgs m;
+            m.lists = static_cast<const fsgpu::u64*>(s.raw(a.lists, g.lists_n * 8));
+            m.q_stride = a.q_stride;
+            m.l_stride = a.l_stride;
+            m.nlists = a.nlists;
+            m.list_len = a.list_len;
+            m.k = a.k;
+            m.out_stride = a.out_stride;
+            m.out_rows = static_cast<uint32_t*>(out((size_t)a.nq * a.out_stride * 4, a.out_rows));
+            m.out_scores = static_cast<float*>(out((size_t)a.nq * a.out_stride * 4, a.out_scores));
+            m.out_counts = static_cast<uint32_t*>(out((size_t)a.nq * 4, a.out_counts));
+            m.out_packed = static_cast<fsgpu::u64*>(out((size_t)a.nq * a.out_stride * 8, a.out_packed));
+            m.lists_sorted = a.lists_sorted;
+            if (s.ok()) s.hip(fsgpu::launch_merge_topk(m, (int)a.nq, nullptr));
+        } else {
+            // the slab with guard rows behind its last row: NaN (f16 0x7e00, f32 0x7fc00000) or 0x7f (int8, 4-bit)
+            constexpr size_t kGuardRows = 64;
+            const size_t body = (size_t)a.nrows * g.slab_pitch, tail = kGuardRows * g.slab_pitch;
+            std::vector<unsigned char> h(body + tail, 0x7f);
+            std::memcpy(h.data(), a.slab, body);
+            if (a.kind == FSGPU_LAB_LONE_F32)
+                for (size_t i = body; i + 3 < body + tail; i += 4) h[i] = 0, h[i + 1] = 0, h[i + 2] = 0xc0, h[i + 3] = 0x7f;
+            else if (a.kind <= FSGPU_LAB_LONE_F16_MQ)
+                for (size_t i = body; i + 1 < body + tail; i += 2) h[i] = 0x00, h[i + 1] = 0x7e;
+            const void* slab = s.raw(h.data(), h.size());
+            auto bitmap = [&](const uint64_t* src) -> const fsgpu::u64* {
+                if (!src) return nullptr;
+                std::vector<uint64_t> w(g.bitmap_words + 2, 0);   // (two zero words behind the last)
+                std::memcpy(w.data(), src, g.bitmap_words * 8);
+                return static_cast<const fsgpu::u64*>(s.raw(w.data(), w.size() * 8));
+            };
+            const bool host_query = a.kind == FSGPU_LAB_LONE_F16_HOST_QUERY;
+            const void* query = host_query ? nullptr : s.raw(a.queries, g.query_bytes);
+            const bool quantised = a.kind == FSGPU_LAB_LONE_I8 || a.kind == FSGPU_LAB_LONE_I4;
+            fsgpu::ScanArgs m{};
+            m.slab = quantised ? nullptr : slab;
+            m.live = bitmap(a.live);
+            m.allow = bitmap(a.allow);
+            m.queries = quantised || host_query ? nullptr : static_cast<const float*>(query);
+            m.partial = static_cast<fsgpu::u64*>(out((size_t)a.nq * a.grid * a.k * 8, a.partial));
+            m.nrows = a.nrows;
+            m.dim = a.dim;
+            m.k = a.k;
+            m.row_base = a.row_base;
+            m.hreduce = a.hreduce;
+            m.row_stride = (uint32_t)g.slab_pitch;
+            const int nq = (int)a.nq, tier = (int)a.tier, grid = (int)a.grid;
+            if (s.ok()) {
+                switch (a.kind) {
+                    case FSGPU_LAB_LONE_F16: s.hip(fsgpu::launch_scan_topk(m, nq, tier, grid, nullptr, a.force_runtime_dim != 0, a.plain_loads != 0)); break;
+                    case FSGPU_LAB_LONE_F16_HOST_QUERY: s.hip(fsgpu::launch_scan_topk_host_query(m, static_cast<const float*>(a.queries), tier, grid, nullptr)); break;
+                    case FSGPU_LAB_LONE_F16_MQ: s.hip(fsgpu::launch_scan_mq(m, nq, tier, grid, nullptr, nullptr)); break;
+                    case FSGPU_LAB_LONE_I8: s.hip(fsgpu::launch_scan_i8(m, slab, query, tier, grid, nullptr, nullptr)); break;
+                    case FSGPU_LAB_LONE_I4: s.hip(fsgpu::launch_scan_4bit(m, slab, query, tier, grid, nullptr, nullptr)); break;
+                    default: s.hip(fsgpu::launch_scan_topk_f32(m, tier, nq, grid, nullptr, nullptr)); break;
+                }
+            }
+        }
+        s.hip(hipStreamSynchronize(nullptr));
+        bool guard_hit = false;
+        for (const Out& o : outs) {
+            if (!s.ok()) break;
+            std::vector<unsigned char> h(o.bytes + 2 * kBand);
+            s.hip(hipMemcpy(h.data(), o.base, h.size(), hipMemcpyDeviceToHost));
+            if (!s.ok()) break;
+            for (size_t i = 0; i < kBand; ++i)
+                if (h[i] != LabStage::kGuardByte || h[kBand + o.bytes + i] != LabStage::kGuardByte) guard_hit = true;
+            std::memcpy(o.host, h.data() + kBand, o.bytes);
+        }
+        if (!s.e.ok()) return finish(s.e);
+        if (s.he == hipErrorInvalidValue) return fail(FSGPU_ERR_INVALID_CONFIG, "lone: the launcher refused the arguments");
+        if (s.he != hipSuccess) return fail(FSGPU_ERR_DEVICE, hipGetErrorString(s.he));
+        if (guard_hit) return fail(FSGPU_ERR_DEVICE, "lone: a kernel wrote into a guard band of its output");
+        return FSGPU_OK;
+    });
+}
+
 fsgpu_status fsgpu_bert_embed_device(fsgpu_bert* m, const int32_t* ids, const uint32_t* offsets, uint32_t n, float* out_dev) {
     if (!m) return fail(FSGPU_ERR_NULL_ARGUMENT, "embedder is null");
     if (n && !out_dev) return fail(FSGPU_ERR_NULL_ARGUMENT, "out_dev is null");

@@ -558,8 +558,12 @@ __global__ __launch_bounds__(NT) void merge_topk_kernel(MergeArgs args) {
                     if (pos1 < MCAP) buf[pos1] = c[u];
                 }
             __syncthreads();
-            if (s_count > MCAP - NT * U) {  // block-uniform
-                const int have = s_count < MCAP ? s_count : MCAP;
+            // every thread reads the count BETWEEN two barriers: without the second one a wave that skips the branch could start the next
+            // round's atomicAdd before a slower wave has read, and the two would disagree about a branch that holds barriers
+            const int filled = s_count;
+            __syncthreads();
+            if (filled > MCAP - NT * U) {  // block-uniform
+                const int have = filled < MCAP ? filled : MCAP;
                 for (int j = have + tid; j < MCAP; j += NT) buf[j] = kEmpty;
                 block_sort_desc<MCAP, NT>(buf, tid);
                 if (tid == 0) {

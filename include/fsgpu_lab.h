@@ -257,6 +257,48 @@ typedef struct fsgpu_lab_select_args {
 } fsgpu_lab_select_args;
 fsgpu_status fsgpu_lab_select_check(const fsgpu_lab_select_args *args);
 fsgpu_status fsgpu_lab_select(int32_t device, const fsgpu_lab_select_args *args);
+/* ONE launch of the per-query search path on host arrays, through the launcher the product calls (launch_scan_topk,
+ * launch_scan_topk_host_query, launch_scan_mq, launch_scan_i8, launch_scan_4bit, launch_scan_topk_f32, launch_merge_topk) with a
+ * ScanArgs / MergeArgs filled field for field from this struct and an EXPLICIT grid: for kernel-level tests against
+ * tests/lone_scan_ref.py.  Default stream, fresh device buffers, no kernel of its own, one synchronisation.
+ *   scans  nq = queries per pass (F16 1 / 2 / 4; F16_HOST_QUERY, I8, I4 1; F16_MQ 4 / 8; F32 1 / 2 / 4), tier = 64 / 256 (the kernels'
+ *          KCAP), 1 <= k <= tier, 1 <= grid <= 4096, nrows >= 1.  slab: nrows rows of row_stride bytes (0 = dense: dim x 2 for f16, dim x 4
+ *          for F32, dim for I8, dim / 2 packed nibbles, low nibble = even dimension, for I4; a strided view — a multiple of 16 bytes that
+ *          holds a row — only where the kernel reads ScanArgs::row_stride: F16, F16_HOST_QUERY, F32).  queries: nq x dim f32 (F16_HOST_QUERY:
+ *          read from this host array at launch), or the quantised query as the kernel reads it (I8: dim int8, I4: dim / 2 bytes).
+ *          live / allow: bitmap_words words each (>= ceil(nrows / 64)) or NULL.  force_runtime_dim / plain_loads: launch_scan_topk's (F16
+ *          only).  partial [nq][grid][k] receives one best-first list per (query, block), kEmpty padded.
+ *   MERGE  lists: nq x q_stride entries (q_stride >= (nlists - 1) l_stride + list_len, l_stride >= list_len >= 1, nlists >= 1),
+ *          1 <= k <= 256, out_stride >= k, lists_sorted 0 / 1; any subset of out_rows / out_scores / out_packed [nq][out_stride] and
+ *          out_counts [nq].
+ * Output areas are prefilled with bytes 0xCD and lie between guard bands (FSGPU_ERR_DEVICE, "guard band", if one is touched); the slab is
+ * followed by guard rows of NaN (f16, f32) or 0x7f (int8, 4-bit).  Arguments are checked before a device is looked for
+ * (fsgpu_lab_lone_stage_check does only that: FSGPU_OK = it would be launched); what the launchers or their *_supported predicates
+ * refuse, and what the kernels cannot hold, is FSGPU_ERR_INVALID_CONFIG with nothing launched. */
+#define FSGPU_LAB_LONE_F16 0
+#define FSGPU_LAB_LONE_F16_HOST_QUERY 1
+#define FSGPU_LAB_LONE_F16_MQ 2
+#define FSGPU_LAB_LONE_I8 3
+#define FSGPU_LAB_LONE_I4 4
+#define FSGPU_LAB_LONE_F32 5
+#define FSGPU_LAB_LONE_MERGE 6
+typedef struct fsgpu_lab_lone_stage_args {
+    uint32_t kind, nq, tier, dim, nrows, row_stride, row_base, k, grid, force_runtime_dim, plain_loads;
+    int32_t hreduce;
+    uint32_t bitmap_words, nlists, list_len, l_stride, out_stride, lists_sorted;
+    uint64_t q_stride;
+    const void *slab;
+    const uint64_t *live, *allow;
+    const void *queries;
+    uint64_t *partial;
+    const uint64_t *lists;
+    uint32_t *out_rows;
+    float *out_scores;
+    uint64_t *out_packed;
+    uint32_t *out_counts;
+} fsgpu_lab_lone_stage_args;
+fsgpu_status fsgpu_lab_lone_stage_check(const fsgpu_lab_lone_stage_args *args);
+fsgpu_status fsgpu_lab_lone_stage(int32_t device, const fsgpu_lab_lone_stage_args *args);
 /* fsgpu_index_compute_query_hubness that also returns what it selected: out_topk[record_count, min(kq, nq)] holds every row's
  * selected similarities, greatest first under total_cmp (for tests of the selection itself; meant for small indexes). */
 fsgpu_status fsgpu_lab_index_query_hubness_topk(fsgpu_index *idx, const float *queries, uint32_t nq, uint32_t query_dim, uint32_t kq,
