@@ -38,6 +38,12 @@ HREDUCE_SEQ = 2
 
 _vp, _u32, _u64, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 
+
+class KnnOptimizeStats(C.Structure):   # fsgpu_knn_optimize_stats
+    _fields_ = [("rows", C.c_uint64), ("forward_edges", C.c_uint64), ("reverse_edges", C.c_uint64), ("zero_in_degree_before", C.c_uint64),
+                ("zero_in_degree_after", C.c_uint64), ("max_detour_count", C.c_uint32), ("reserved", C.c_uint32), ("device_ms", C.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol include/fsgpu.h declares
 SIGNATURES = {
     "fsgpu_version": (C.c_char_p, []),
@@ -236,6 +242,7 @@ SIGNATURES = {
     "fsgpu_index_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
     "fsgpu_sharded_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
     "fsgpu_lab_index_knn_build_stats": (_i32, [_vp, _vp]),
+    "fsgpu_knn_graph_optimize": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "fsgpu_ann_config_default": (_i32, [_vp]),
     "fsgpu_ann_create": (_i32, [_vp, _vp, _u64, _u32, _vp, C.POINTER(_vp)]),
     "fsgpu_ann_destroy": (None, [_vp]),

@@ -1739,6 +1739,36 @@ fsgpu_status fsgpu_index_build_knn_graph(fsgpu_index* idx, uint64_t first_row, u
     });
 }
 
+// the graph optimisation: the shape is judged first, then the device, then the handle and its row count; nothing is written on a refusal
+fsgpu_status fsgpu_knn_graph_optimize(fsgpu_index* idx, const uint32_t* graph_rows, uint64_t graph_len, uint32_t graph_width,
+                                      uint32_t out_degree, uint32_t* out_rows, fsgpu_knn_optimize_stats* stats) {
+    if (graph_width > fsgpu::kKnnOptMaxWidth) return fail(FSGPU_ERR_INVALID_CONFIG, "graph_width must be at most 64 (a list is one wave wide)");
+    if (out_degree < 1 || out_degree > graph_width) return fail(FSGPU_ERR_INVALID_CONFIG, "out_degree must be 1 .. graph_width");
+    if (graph_len && (!graph_rows || !out_rows)) return fail(FSGPU_ERR_INVALID_CONFIG, "the table and the output must not be null");
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        if (graph_len != idx->impl.record_count())
+            return fail(FSGPU_ERR_INVALID_CONFIG, ("graph_len " + std::to_string(graph_len) + " is not record_count " +
+                                                   std::to_string(idx->impl.record_count())).c_str());
+        fsgpu::VectorIndex::KnnOptimizeStats st;
+        const fsgpu_status s = finish(idx->impl.optimize_knn_graph(graph_rows, graph_width, out_degree, out_rows, stats ? &st : nullptr));
+        if (s == FSGPU_OK && stats) {
+            std::memset(stats, 0, sizeof(*stats));
+            stats->rows = st.rows;
+            stats->forward_edges = st.forward_edges;
+            stats->reverse_edges = st.reverse_edges;
+            stats->zero_in_degree_before = st.zero_in_degree_before;
+            stats->zero_in_degree_after = st.zero_in_degree_after;
+            stats->max_detour_count = st.max_detour_count;
+            stats->device_ms = st.device_ms;
+        }
+        return s;
+    });
+}
+
 fsgpu_status fsgpu_lab_index_knn_build_stats(fsgpu_index* idx, uint64_t* out4) {
     if (!idx || !out4) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> lock(idx->impl.mutex());

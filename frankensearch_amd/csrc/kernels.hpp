@@ -555,6 +555,43 @@ struct KnnEmitArgs {
 };
 hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
 
+// knn_optimize_kernels.hip: the graph optimisation over a neighbour table (vector_index_knn_optimize.cpp; include/fsgpu.h,
+// fsgpu_knn_graph_optimize).  All pointers are device memory; n <= 2^32 - 2, 1 <= degree <= width <= kKnnOptMaxWidth.
+constexpr uint32_t kKnnOptMaxWidth = 64;   // a list is one wave wide
+struct KnnOptDetourArgs {
+    const uint32_t* table;       // [n, width] global ids, kKnnPadRow ends a list (the caller's: every id is checked against n)
+    uint64_t n;
+    uint32_t width, degree, row_base;
+    uint32_t* fwd;               // out: [n, degree] F(x) as global ids, dense, then kKnnPadRow
+    uint32_t* max_detour;        // nullable: [1], raised to the greatest detour count
+    uint8_t* seen_before;        // nullable: [n], 1 where an edge of the table's first `degree` columns points
+};
+hipError_t launch_knn_opt_detour(const KnnOptDetourArgs& args, hipStream_t stream);
+struct KnnOptRoundArgs {         // the reverse candidates of one rank, placed in (source ascending) order behind the ranks before it
+    const uint32_t* fwd;         // [n, degree]
+    uint64_t n;
+    uint32_t degree, rank, row_base;
+    u64* keys;                   // [n] scratch: the round's keys
+    u64* sorted;                 // [n] scratch: ... sorted (not `keys`)
+    uint32_t* advance;           // [n] scratch
+    uint32_t* fill;              // [n] candidates placed per target so far (0 before rank 0), capped at degree
+    uint32_t* rev;               // [n, degree] the candidates as global ids; only the first fill[y] of a row are written
+};
+hipError_t launch_knn_opt_round(const KnnOptRoundArgs& args, void* sort_temp, size_t sort_temp_bytes, hipStream_t stream);
+struct KnnOptMergeArgs {
+    const uint32_t* fwd;         // [n, degree]
+    const uint32_t* rev;         // [n, degree]
+    const uint32_t* fill;        // [n]
+    uint64_t n;
+    uint32_t degree, row_base;
+    uint32_t* out;               // [n, degree] global ids, dense, then kKnnPadRow
+    u64* edge_counts;            // nullable: [2] += entries written from F, from the reverse candidates
+    uint8_t* seen_after;         // nullable: [n], 1 where an edge of `out` points
+};
+hipError_t launch_knn_opt_merge(const KnnOptMergeArgs& args, hipStream_t stream);
+// out2[0] += rows with before[i] == 0, out2[1] += rows with after[i] == 0
+hipError_t launch_knn_opt_count_zero(const uint8_t* before, const uint8_t* after, uint64_t n, u64* out2, hipStream_t stream);
+
 // ann_kernels.hip: the beam search over a k-NN table (ann_index.cpp; include/fsgpu.h, "graph ANN search").  One
 // workgroup per query; everything of a query but its slab rows lives in LDS.
 constexpr uint32_t kAnnMaxEf = 256;             // beam entries

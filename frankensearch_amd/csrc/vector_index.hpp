@@ -263,6 +263,16 @@ class VectorIndex {
         uint64_t steps = 0, sources = 0, fallbacks = 0, late_answers = 0;
     };
     KnnBuildStats last_knn_build;
+    // The graph optimisation over a neighbour table of this index (include/fsgpu.h, fsgpu_knn_graph_optimize; DESIGN 3.20;
+    // vector_index_knn_optimize.cpp, knn_optimize_kernels.hip): graph_rows [record_count, width] -> out_rows [record_count, degree],
+    // a pure function of the table and row_base.  Host pointers; blocks; its workspace comes and goes with the call; refused while a
+    // begun search is outstanding.  The caller has checked the shape (1 <= degree <= width <= kKnnOptMaxWidth).
+    struct KnnOptimizeStats {
+        uint64_t rows = 0, forward_edges = 0, reverse_edges = 0, zero_in_degree_before = 0, zero_in_degree_after = 0;
+        uint32_t max_detour_count = 0;
+        double device_ms = 0.0;
+    };
+    SearchError optimize_knn_graph(const uint32_t* graph_rows, uint32_t width, uint32_t degree, uint32_t* out_rows, KnnOptimizeStats* stats);
     // ... a row shard's half of the sharded build: n live local rows (src_local) widened to f32 into a host block [n, dim]
     SearchError knn_stage_rows_host(const uint32_t* src_local, uint32_t n, float* out);
     // The beam search over a k-NN table of this index (ann_index.cpp, ann_kernels.hip): `a` arrives with the table, the parameters,

@@ -566,11 +566,31 @@ class VectorIndex:
                                                      _ptr(rows) if rows.size else None, _ptr(sims) if want_sims and sims.size else None))
         return (rows, sims) if want_sims else rows
 
-    def build_ann(self, m: int = 16, **config):
+    def optimize_knn_graph(self, table, out_degree: int, want_stats: bool = False):
+        """fsgpu_knn_graph_optimize: a [record_count, w] neighbour table (build_knn_graph's) -> the [record_count, out_degree] table
+        of detour-ordered forward edges and reverse edges, a pure function of the table and row_base.  With want_stats
+        also a dict of fsgpu_knn_optimize_stats."""
+        t = np.ascontiguousarray(table, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("the table must be [record_count, width]")
+        out = np.full((t.shape[0], min(max(int(out_degree), 0), 64)), 0xFFFFFFFF, dtype=np.uint32)
+        st = _lib.KnnOptimizeStats()
+        check(_lib.lib().fsgpu_knn_graph_optimize(self._h, _ptr(t) if t.size else None, t.shape[0], t.shape[1],
+                                                  min(max(int(out_degree), 0), 0xFFFFFFFF), _ptr(out) if out.size else None,
+                                                  C.addressof(st) if want_stats else None))
+        if not want_stats:
+            return out
+        return out, {name: getattr(st, name) for name, _ in _lib.KnnOptimizeStats._fields_ if name != "reserved"}
+
+    def build_ann(self, m: int = 16, optimize=None, **config):
         """build_knn_graph(m) followed by fsgpu_ann_create: an AnnIndex over this index's exact k-NN table (ann.py; n_entry, degree,
-        expand and max_iters as keywords)."""
+        expand and max_iters as keywords).  optimize=d: the m-column table is optimised to d columns first (optimize_knn_graph) and
+        the AnnIndex searches that."""
         from .ann import AnnConfig, AnnIndex
-        return AnnIndex(self, self.build_knn_graph(m), AnnConfig(**config))
+        table = self.build_knn_graph(m)
+        if optimize is not None:
+            table = self.optimize_knn_graph(table, optimize)
+        return AnnIndex(self, table, AnnConfig(**config))
 
     def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
         """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes

@@ -1212,6 +1212,43 @@ fsgpu_status fsgpu_index_build_knn_graph(fsgpu_index *idx, uint64_t first_row, u
  * sharded search's own limits apply (dimension a multiple of 8). */
 fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded *sh, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t *out_rows,
                                            float *out_sims);
+/* The graph optimisation: a neighbour table in, a navigable table of lower degree out.  An exact k-NN table is a poor
+ * graph to search: its lists are redundant (a row's nearest neighbours are mostly each other's neighbours), no edge leaves a tight
+ * group, and rows that nobody lists cannot be reached.  The repair is CAGRA's graph optimisation, restated as a PURE FUNCTION of the
+ * table: it reads no vector, computes no distance and does not look at the live bitmap (rows deleted after the build stay in the
+ * lists; the search tests the bitmap when it runs), so the result is the same bytes on every run and every device.
+ * Inputs: T [N, w] global u32 ids with 0xffffffff as the pad, the index's row_base, N = record_count, an output degree d,
+ * 1 <= d <= w <= 64.  Output: [N, d].
+ *   1. clean list C(x): walk T[x] from column 0 to the first pad; keep a global id g if r = g - row_base lies in [0, N), r != x and
+ *      r was not kept before.  Rank i is the position in C(x).  The table is the caller's: every id is checked against N before it
+ *      becomes an address.
+ *   2. detour count: for rank i with y = C(x)[i], cnt[i] is the number of ranks j < i such that, in the raw list of z = C(x)[j]
+ *      (the columns of T[z] before its first pad), y's global id first occurs at a column p < i.  The route x -> z -> y detours the
+ *      edge x -> y when both of its hops rank above it.
+ *   3. forward list F(x): the ranks sorted by (cnt ascending, i ascending), the first d of them.
+ *   4. reverse candidates of y: all pairs (r, x) with F(x)[r] = y, ordered by (r ascending, x ascending); only the first d matter.
+ *      No arrival order of any atomic reaches the result.
+ *   5. output list of x, h = ceil(d / 2): the first h entries of F(x); then the reverse candidates of x in order, skipping rows
+ *      already present, until d entries; then the rest of F(x) in order, skipping rows already present, until d entries.  Written as
+ *      global ids, dense from column 0, then pads: no pad stands before an entry.
+ * graph_rows [graph_len, graph_width] and out_rows [graph_len, out_degree] are HOST arrays (fsgpu_index_build_knn_graph's output,
+ * fsgpu_ann_create's input); the index supplies the device, the stream and row_base; the call blocks, and its workspace comes and goes
+ * with it.  Refused with FSGPU_ERR_INVALID_CONFIG before any work and with nothing written: graph_len != record_count, out_degree 0
+ * or above graph_width, graph_width above 64, a NULL table or output.  Without a device: FSGPU_ERR_NO_DEVICE.  An empty index returns
+ * OK and does nothing.  The call holds the index the way the k-NN build does and is refused (FSGPU_ERR_INVALID_CONFIG) while a begun
+ * search is outstanding.
+ * stats (may be NULL): forward_edges / reverse_edges count the output's entries by origin (F, reverse candidates);
+ * zero_in_degree_before / _after count the rows no edge points at in the first out_degree columns of the input, walked as the search
+ * walks them (to the first pad; an id outside the table or the row itself is no edge), and in the output; max_detour_count is the
+ * greatest cnt[i] of step 2; device_ms is the time between the table's arrival on the device and the last kernel. */
+typedef struct fsgpu_knn_optimize_stats {
+    uint64_t rows, forward_edges, reverse_edges;
+    uint64_t zero_in_degree_before, zero_in_degree_after;
+    uint32_t max_detour_count, reserved;
+    double device_ms;
+} fsgpu_knn_optimize_stats;
+fsgpu_status fsgpu_knn_graph_optimize(fsgpu_index *idx, const uint32_t *graph_rows, uint64_t graph_len, uint32_t graph_width,
+                                      uint32_t out_degree, uint32_t *out_rows, fsgpu_knn_optimize_stats *stats);
 /* SmoothConfig (smooth.rs:38-69): defaults alpha = 0.3, m = 10, mutual = 0; the reserved words must be 0. */
 typedef struct fsgpu_smooth_config {
     float alpha;
