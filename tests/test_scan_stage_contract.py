@@ -98,6 +98,11 @@ def test_arguments_are_refused_before_a_device_is_needed():
     a = S._args(S.REG, **valid_kw(reg, slots=33))
     assert _lib.lib().fsgpu_lab_scan_stage(-7, ctypes.byref(a)) == S.INVALID_CONFIG and "kWideSlots" in _lib.last_error()
     assert _lib.lib().fsgpu_lab_scan_stage(0, None) == S.NULL_ARGUMENT and _lib.lib().fsgpu_lab_scan_stage_check(None) == S.NULL_ARGUMENT
+    # valid arguments, an ordinal that is no device (the device count itself): the failure the lab file reports from behind the argument
+    # check is the thread's last error (FSGPU_ERR_NO_DEVICE on a host without one), not an empty or stale string; no pointer is followed
+    n_dev = _lib.lib().fsgpu_device_count()
+    assert (_lib.lib().fsgpu_lab_scan_stage(n_dev, ctypes.byref(S._args(S.REG, **valid_kw(reg)))), _lib.last_error()) == \
+        ((S.INVALID_CONFIG, "device ordinal out of range") if n_dev else (7, "no HIP device visible"))
     # the prepare form
     p = DUMMY.ctypes.data
     prep = dict(elem_bytes=2, dim=384, nq=3, nq_pad=64, queries_f32=p, prepared=p, delta=p)
