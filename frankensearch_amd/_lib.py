@@ -44,6 +44,16 @@ class KnnOptimizeStats(C.Structure):   # fsgpu_knn_optimize_stats
                 ("zero_in_degree_after", C.c_uint64), ("max_detour_count", C.c_uint32), ("reserved", C.c_uint32), ("device_ms", C.c_double)]
 
 
+class KnnUpdateConfig(C.Structure):   # fsgpu_knn_update_config
+    _fields_ = [("max_added_fraction", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+
+class KnnUpdateStats(C.Structure):   # fsgpu_knn_update_stats
+    _fields_ = [("rows", C.c_uint64), ("dead", C.c_uint64), ("added", C.c_uint64), ("kept_clean", C.c_uint64), ("kept_dirty", C.c_uint64),
+                ("searched_sources", C.c_uint64), ("join_pairs", C.c_uint64), ("join_entries", C.c_uint64), ("rebuilt", C.c_uint32),
+                ("reserved", C.c_uint32), ("device_ms", C.c_double), ("join_ms", C.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol include/fsgpu.h declares
 SIGNATURES = {
     "fsgpu_version": (C.c_char_p, []),
@@ -243,6 +253,10 @@ SIGNATURES = {
     "fsgpu_sharded_build_knn_graph": (_i32, [_vp, _u64, _u64, _u32, _vp, _vp]),
     "fsgpu_lab_index_knn_build_stats": (_i32, [_vp, _vp]),
     "fsgpu_knn_graph_optimize": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, _vp]),
+    "fsgpu_lab_knn_update_join": (_i32, [_i32, _vp, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp, _u32]),
+    "fsgpu_knn_update_config_default": (_i32, [_vp]),
+    "fsgpu_index_update_knn_graph": (_i32, [_vp, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_index_rewrite_sources": (_i32, [_vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "fsgpu_ann_config_default": (_i32, [_vp]),
     "fsgpu_ann_create": (_i32, [_vp, _vp, _u64, _u32, _vp, C.POINTER(_vp)]),
     "fsgpu_ann_destroy": (None, [_vp]),

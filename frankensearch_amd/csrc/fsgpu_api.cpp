@@ -1568,6 +1568,63 @@ fsgpu_status fsgpu_knn_graph_optimize(fsgpu_index* idx, const uint32_t* graph_ro
     });
 }
 
+// ---- the k-NN table across a rewrite or deletes (vector_index_knn_update.cpp): every refusal comes before any work ----
+fsgpu_status fsgpu_knn_update_config_default(fsgpu_knn_update_config* config) {
+    if (!config) return fail(FSGPU_ERR_NULL_ARGUMENT, "config is null");
+    std::memset(config, 0, sizeof(*config));
+    config->max_added_fraction = fsgpu::kKnnUpdDefaultMaxAddedFraction;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_index_update_knn_graph(fsgpu_index* idx, uint32_t m, const uint32_t* old_rows, const float* old_sims, uint64_t old_len,
+                                          uint32_t old_row_base, const uint32_t* new_to_old_or_null,
+                                          const fsgpu_knn_update_config* config_or_null, uint32_t* out_rows, float* out_sims,
+                                          fsgpu_knn_update_stats* stats_or_null) {
+    if (m < 1 || m > fsgpu::kKnnMaxM) return fail(FSGPU_ERR_INVALID_CONFIG, "m must be 1 .. 63 (k = m + 1 stays inside the fused tiers)");
+    if (!old_rows || !old_sims || !out_rows || !out_sims) return fail(FSGPU_ERR_INVALID_CONFIG, "the tables and the outputs must not be null");
+    if (old_len >= 0xffffffffull) return fail(FSGPU_ERR_INVALID_CONFIG, "old_len must be below 2^32 - 1: the table's ids are 32 bits wide");
+    float max_added_fraction = fsgpu::kKnnUpdDefaultMaxAddedFraction;
+    if (config_or_null) {
+        for (uint32_t r : config_or_null->reserved)
+            if (r != 0) return fail(FSGPU_ERR_INVALID_CONFIG, "the reserved words of fsgpu_knn_update_config must be 0");
+        max_added_fraction = config_or_null->max_added_fraction;
+    }
+    if (fsgpu_device_count() <= 0) return fail(FSGPU_ERR_NO_DEVICE, "no HIP device visible (libfsgpu has no CPU fallback)");
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        fsgpu::VectorIndex::KnnUpdateStats st;
+        const fsgpu_status s = finish(idx->impl.update_knn_graph(m, old_rows, old_sims, old_len, old_row_base, new_to_old_or_null,
+                                                                 max_added_fraction, out_rows, out_sims, &st));
+        if (s == FSGPU_OK && stats_or_null) {
+            std::memset(stats_or_null, 0, sizeof(*stats_or_null));
+            stats_or_null->rows = st.rows;
+            stats_or_null->dead = st.dead;
+            stats_or_null->added = st.added;
+            stats_or_null->kept_clean = st.kept_clean;
+            stats_or_null->kept_dirty = st.kept_dirty;
+            stats_or_null->searched_sources = st.searched_sources;
+            stats_or_null->join_pairs = st.join_pairs;
+            stats_or_null->join_entries = st.join_entries;
+            stats_or_null->rebuilt = st.rebuilt;
+            stats_or_null->device_ms = st.device_ms;
+            stats_or_null->join_ms = st.join_ms;
+        }
+        return s;
+    });
+}
+
+fsgpu_status fsgpu_index_rewrite_sources(fsgpu_index* idx, uint32_t* out_new_to_old, uint64_t* generation_before, uint64_t* generation_after,
+                                         uint64_t* old_record_count) {
+    if (!idx) return fail(FSGPU_ERR_NULL_ARGUMENT, "index is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        return finish(idx->impl.rewrite_sources(out_new_to_old, generation_before, generation_after, old_record_count));
+    });
+}
+
 fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded* sh, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t* out_rows,
                                            float* out_sims) {
     if (m < 1 || m > fsgpu::kKnnMaxM) return fail(FSGPU_ERR_INVALID_CONFIG, "m must be 1 .. 63 (k = m + 1 stays inside the fused tiers)");

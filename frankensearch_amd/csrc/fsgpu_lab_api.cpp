@@ -1276,6 +1276,36 @@ fsgpu_status fsgpu_lab_lone_stage(int32_t device, const fsgpu_lab_lone_stage_arg
     });
 }
 
+fsgpu_status fsgpu_lab_knn_update_join(int32_t device, const void* slab, uint32_t slab_f32, uint32_t nrows, uint32_t dim, int32_t hreduce,
+                                       uint32_t m, const uint8_t* classes, uint64_t* work, const float* added, const uint32_t* added_rows,
+                                       uint32_t n_added) {
+    if (!slab || !classes || !work || !added || !added_rows) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (m < 1 || m > fsgpu::kKnnMaxM || dim < 1 || dim > fsgpu::kKnnUpdMaxDim || nrows < 1 || nrows > (1u << 24) || n_added < 1 ||
+        n_added > fsgpu::kKnnUpdBlock || hreduce < 0 || hreduce > 2)
+        return fail(FSGPU_ERR_INVALID_CONFIG, "knn update join: m 1..63, dim 1..1024, 1..2^24 rows, 1..1024 added rows, hreduce 0..2");
+    return guarded([&]() -> fsgpu_status {
+        if (const fsgpu_status opened = LabStage::open(device); opened != FSGPU_OK) return opened;
+        LabStage s;
+        const size_t pitch = (size_t)dim * (slab_f32 ? 4 : 2);
+        fsgpu::KnnUpdJoinArgs a{};
+        a.slab = s.with_tail(slab, (size_t)nrows * pitch, LabStage::kGuardRows * pitch, slab_f32 ? lab::Tail::kF32NaN : lab::Tail::kF16NaN);
+        a.row_stride = (uint32_t)pitch;
+        a.dim = dim;
+        a.slab_f32 = slab_f32 ? 1u : 0u;
+        a.hreduce = hreduce;
+        a.row0 = 0;
+        a.nrows = nrows;
+        a.m = m;
+        a.cls = static_cast<const uint8_t*>(s.raw(classes, nrows));
+        a.work = static_cast<fsgpu::u64*>(s.out_bytes((size_t)nrows * m * 8, 0, work, true));
+        a.added = s.f32(added, (size_t)n_added * dim);
+        a.added_rows = static_cast<const uint32_t*>(s.raw(added_rows, (size_t)n_added * 4));
+        a.n_added = n_added;
+        if (s.ok()) s.hip(fsgpu::launch_knn_update_join(a, nullptr));
+        return s.status("knn update join: the kernel wrote into a guard band of the working table", "knn update join: the launcher refused the shape");
+    });
+}
+
 fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out,
                                            float* out_stage_ms) {
     if (!h || !out_stage_ms) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");

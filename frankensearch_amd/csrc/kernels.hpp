@@ -555,6 +555,69 @@ struct KnnEmitArgs {
 };
 hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
 
+// knn_update_kernels.hip: carrying a k-NN table across a rewrite or deletes (vector_index_knn_update.cpp; include/fsgpu.h,
+// fsgpu_index_update_knn_graph).  All pointers are device memory.  The working table [n, m] holds a row's list as packed
+// entries (device_util.hpp: score bits << 32 | LOCAL current row), best first under sortkey, kEmpty past its end.
+constexpr uint8_t kKnnUpdDead = 0, kKnnUpdAdded = 1, kKnnUpdClean = 2, kKnnUpdDirty = 3;   // the class byte of a current row
+constexpr uint32_t kKnnUpdMaxDim = 1024;           // dimensions the join covers
+constexpr uint32_t kKnnUpdBlock = 1024;            // added rows per join launch (one staged f32 block)
+constexpr uint32_t kKnnUpdRowsPerWave = 16, kKnnUpdChunk = 16;   // a 16-lane group owns 4 rows; added rows per LDS chunk
+constexpr uint32_t kKnnUpdLaunchRows = 1u << 20;   // rows per join launch: no single launch holds a shared card for long
+constexpr size_t kKnnUpdLdsBudget = 159 * 1024;   // dynamic LDS of the join; the block vote's static bytes come on top
+// fsgpu_knn_update_config_default's max_added_fraction: of the swept 0.1 / 0.3 / 1 / 3 % of added rows at 1M x 384, m = 16, the
+// largest at which the update still beat a rebuild was 0.3 % (2.9 x; at 1 % it lost, 0.97 x), halved
+constexpr float kKnnUpdDefaultMaxAddedFraction = 0.0015f;
+// inv[new_to_old[x]] = x for every x with a predecessor (< old_len); inv was filled with 0xff bytes.  No predecessor occurs twice.
+hipError_t launch_knn_update_inverse(const uint32_t* new_to_old, uint64_t n, uint64_t old_len, uint32_t* inv, hipStream_t stream);
+struct KnnUpdClassifyArgs {
+    const uint32_t* old_rows;    // [old_len, m] global ids relative to old_row_base, kKnnPadRow padding
+    const float* old_sims;       // [old_len, m]
+    uint64_t old_len;
+    uint32_t old_row_base;
+    const uint32_t* new_to_old;  // [n] old local row or kKnnPadRow; nullptr = identity (old_len == n)
+    const uint32_t* inv;         // [old_len] current row of an old row or kKnnPadRow; nullptr = identity
+    const u64* live;             // bit r set = row r live; nullptr = all live
+    uint64_t n;                  // current rows
+    uint32_t m;
+    uint32_t all_dirty;          // != 0: the map is not monotone, every kept row is dirty
+    uint8_t* cls;                // out: [n]
+    u64* work;                   // out: [n, m] the remapped, sorted list of a kept-clean row; kEmpty everywhere else
+};
+hipError_t launch_knn_update_classify(const KnnUpdClassifyArgs& args, hipStream_t stream);
+struct KnnUpdScatterArgs {       // a search step's lists (knn_emit_kernel's output) into the working table at their sources' rows
+    const uint32_t* src;         // [n] global source rows
+    const uint32_t* rows;        // [n, m] global ids, kKnnPadRow padding
+    const float* sims;           // [n, m]
+    uint32_t n, m, row_base;
+    uint64_t nrows;              // rows of the working table (every source and id is checked against it)
+    u64* work;
+};
+hipError_t launch_knn_update_scatter(const KnnUpdScatterArgs& args, hipStream_t stream);
+struct KnnUpdJoinArgs {
+    const void* slab;            // the index's rows (f16 or f32)
+    uint32_t row_stride, dim, slab_f32;
+    int32_t hreduce;
+    uint32_t row0, nrows;        // this launch's rows [row0, row0 + nrows)
+    uint32_t m;
+    const uint8_t* cls;          // [slab rows]: only kKnnUpdClean rows are scored into
+    u64* work;                   // [slab rows, m] in and out
+    const float* added;          // [n_added, dim] the added rows widened to f32 (knn_stage_rows_kernel's block)
+    const uint32_t* added_rows;  // [n_added] their LOCAL rows
+    uint32_t n_added;
+};
+hipError_t launch_knn_update_join(const KnnUpdJoinArgs& args, hipStream_t stream);
+struct KnnUpdOutputArgs {
+    const u64* work;             // [n, m]
+    const uint8_t* cls;          // [n]
+    uint64_t n;
+    uint32_t m, row_base;
+    uint32_t* out_rows;          // [n, m] global ids, kKnnPadRow padding
+    float* out_sims;             // [n, m], 0.0f padding
+    uint32_t* join_entries;      // [blocks] per block: entries of kept-clean lists that are added rows (summed by the host)
+};
+uint32_t knn_update_output_blocks(uint64_t n, uint32_t m);
+hipError_t launch_knn_update_output(const KnnUpdOutputArgs& args, hipStream_t stream);
+
 // knn_optimize_kernels.hip: the graph optimisation over a neighbour table (vector_index_knn_optimize.cpp; include/fsgpu.h,
 // fsgpu_knn_graph_optimize).  All pointers are device memory; n <= 2^32 - 2, 1 <= degree <= width <= kKnnOptMaxWidth.
 constexpr uint32_t kKnnOptMaxWidth = 64;   // a list is one wave wide

@@ -275,6 +275,40 @@ class VectorIndex {
     SearchError optimize_knn_graph(const uint32_t* graph_rows, uint32_t width, uint32_t degree, uint32_t* out_rows, KnnOptimizeStats* stats);
     // ... a row shard's half of the sharded build: n live local rows (src_local) widened to f32 into a host block [n, dim]
     SearchError knn_stage_rows_host(const uint32_t* src_local, uint32_t n, float* out);
+    // The build's step loop over a source LIST (vector_index_knn.cpp): next_chunk appends up to cap ascending live local rows and says
+    // whether more may follow; every drained step's [n, m] lists (global ids, kKnnPadRow / 0.0f padding) reach the sink in the step's
+    // pinned block (lists_to_host) or in its device block on `stream`.  The caller has checked m and holds no ticket.
+    struct KnnStepLists {
+        const uint32_t* src;          // [n] local source rows (host)
+        uint32_t n;
+        const uint32_t* rows_host;    // lists_to_host: [n, m]
+        const float* sims_host;       // ... and [n, m] when sims were asked for
+        const uint32_t* src_dev;      // [n] GLOBAL source rows (device)
+        const uint32_t* rows_dev;     // [n, m] (device)
+        const float* sims_dev;        // [n, m] or null (device)
+        hipStream_t stream;           // work on the device lists is enqueued here
+    };
+    using KnnNextChunk = std::function<bool(std::vector<uint32_t>&, uint32_t)>;
+    using KnnStepSink = std::function<SearchError(const KnnStepLists&)>;
+    SearchError knn_search_steps(uint32_t cap, uint32_t m, bool want_sims, bool lists_to_host, const KnnNextChunk& next_chunk,
+                                 const KnnStepSink& sink);
+    // Carrying a k-NN table across a compaction, a vacuum or deletes (include/fsgpu.h, fsgpu_index_update_knn_graph; DESIGN 3.21;
+    // vector_index_knn_update.cpp, knn_update_kernels.hip): the table build_knn_graph(0, record_count, m) would return now, from the
+    // table of the index as it was and the map new row -> old row.  Rows are classified on the device; added and kept-dirty rows are
+    // searched through knn_search_steps; kept-clean lists are the remapped old lists joined against the added rows.  Host pointers;
+    // blocks; takes both tickets; its workspace comes and goes with the call.  The caller has checked m, the pointers and the map.
+    struct KnnUpdateStats {
+        uint64_t rows = 0, dead = 0, added = 0, kept_clean = 0, kept_dirty = 0, searched_sources = 0, join_pairs = 0, join_entries = 0;
+        uint32_t rebuilt = 0;
+        double device_ms = 0.0, join_ms = 0.0;
+    };
+    SearchError update_knn_graph(uint32_t m, const uint32_t* old_rows, const float* old_sims, uint64_t old_len, uint32_t old_row_base,
+                                 const uint32_t* new_to_old, float max_added_fraction, uint32_t* out_rows, float* out_sims,
+                                 KnnUpdateStats* stats);
+    // what fsgpu_index_update_knn_graph refuses before any work: the map's entries (pad or < old_len, no predecessor named twice)
+    SearchError knn_update_check_map(const uint32_t* new_to_old, uint64_t old_len) const;
+    // The last rewrite's map new row -> old main row (kKnnPadRow: from the WAL), kept as runs and expanded here; out [record_count]
+    SearchError rewrite_sources(uint32_t* out_new_to_old, uint64_t* generation_before, uint64_t* generation_after, uint64_t* old_record_count) const;
     // The beam search over a k-NN table of this index (ann_index.cpp, ann_kernels.hip): `a` arrives with the table, the parameters,
     // the queries and the outputs; the slab, the live bitmap AS IT IS NOW, the shape and the hreduce order are filled in here.
     // Refused before the launch when the caps of ann_args_ok do not hold.  Enqueues on `stream`.
@@ -558,6 +592,13 @@ class VectorIndex {
     uint16_t publication_nonce_ = 0;
     bool from_fsvi_ = false;
     uint64_t generation_ = 0;
+    // the last successful rewrite, as runs of consecutive sources (rewrite_sources expands them): a run starts at new row `first` and
+    // copies old main rows from `src` on, or comes from the WAL (src = kWalSource); the last entry is the end marker {record_count, 0}
+    struct RewriteRun {
+        uint64_t first, src;
+    };
+    std::vector<RewriteRun> rewrite_runs_;
+    uint64_t rewrite_old_rows_ = 0, rewrite_generation_ = 0;   // record_count before it; generation_ after it (0: none happened)
 };
 
 class Model2VecEmbedder {

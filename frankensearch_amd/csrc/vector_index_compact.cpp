@@ -269,6 +269,7 @@ SearchError VectorIndex::rewrite(const std::vector<uint64_t>& sources, uint8_t n
     // ---- runs: maximal stretches of consecutive rows of one source; the surviving WAL rows form a block in output order ----
     std::vector<CompactRun> runs;
     std::vector<uint32_t> wal_rows;   // WAL indexes in output order
+    std::vector<RewriteRun> source_runs;   // the same runs in rows, for rewrite_sources
     {
         uint64_t expect = ~0ull;   // the source that would extend the current run
         for (uint64_t i = 0; i < n_new; ++i) {
@@ -280,10 +281,14 @@ SearchError VectorIndex::rewrite(const std::vector<uint64_t>& sources, uint8_t n
             } else {
                 pos = s;
             }
-            if (pos != expect) runs.push_back(CompactRun{(pos & kWalSource) | ((pos & ~kWalSource) * row_bytes), i * row_bytes});
+            if (pos != expect) {
+                runs.push_back(CompactRun{(pos & kWalSource) | ((pos & ~kWalSource) * row_bytes), i * row_bytes});
+                source_runs.push_back(RewriteRun{i, (s & kWalSource) ? kWalSource : s});
+            }
             expect = pos + 1;
         }
         runs.push_back(CompactRun{0, n_new * row_bytes});   // the end marker
+        source_runs.push_back(RewriteRun{n_new, 0});
     }
     const uint64_t nruns = runs.size() - 1;
     last_rewrite.runs = nruns;
@@ -452,6 +457,7 @@ SearchError VectorIndex::rewrite(const std::vector<uint64_t>& sources, uint8_t n
     fresh = DeviceBuffer{};
     slab_dev_ = slab_own_.ptr;
     owns_slab_ = true;
+    const uint64_t old_rows = nrows_;
     nrows_ = n_new;
     live_host_.clear();   // all flags cleared (lib.rs:2919)
     live_dev_ = nullptr;
@@ -464,6 +470,9 @@ SearchError VectorIndex::rewrite(const std::vector<uint64_t>& sources, uint8_t n
     if (clear_wal) wal_.clear();
     compaction_gen_ = new_gen;
     ++generation_;
+    rewrite_old_rows_ = old_rows;
+    rewrite_generation_ = generation_;
+    rewrite_runs_.swap(source_runs);
     release_all();
     t = std::chrono::steady_clock::now();
     drop_derived_state();
@@ -473,6 +482,24 @@ SearchError VectorIndex::rewrite(const std::vector<uint64_t>& sources, uint8_t n
     if (int8_latency && int8_latency_build_now) re = prepare_int8_latency();
     last_rewrite.rebuild_ms = ms_since(t);
     return re;
+}
+
+SearchError VectorIndex::rewrite_sources(uint32_t* out_new_to_old, uint64_t* generation_before, uint64_t* generation_after,
+                                         uint64_t* old_record_count) const {
+    if (rewrite_generation_ == 0 || rewrite_runs_.empty())
+        return make_error(FSGPU_ERR_INVALID_CONFIG, "no compaction or vacuum has rewritten the slab on this handle");
+    if (rewrite_runs_.back().first != nrows_) return make_error(FSGPU_ERR_INVALID_CONFIG, "the kept runs do not describe this slab");
+    if (nrows_ && !out_new_to_old) return make_error(FSGPU_ERR_NULL_ARGUMENT, "out_new_to_old is null");
+    for (size_t r = 0; r + 1 < rewrite_runs_.size(); ++r) {
+        const RewriteRun& run = rewrite_runs_[r];
+        const uint64_t end = rewrite_runs_[r + 1].first;
+        for (uint64_t i = run.first; i < end; ++i)
+            out_new_to_old[i] = (run.src & kWalSource) ? kKnnPadRow : (uint32_t)(run.src + (i - run.first));
+    }
+    if (generation_before) *generation_before = rewrite_generation_ - 1;
+    if (generation_after) *generation_after = rewrite_generation_;
+    if (old_record_count) *old_record_count = rewrite_old_rows_;
+    return ok();
 }
 
 SearchError VectorIndex::lab_attach_synthetic_doc_ids() {

@@ -77,10 +77,50 @@ SearchError VectorIndex::build_knn_graph(uint64_t first_row, uint64_t n_rows, ui
     if (tickets_taken() != 0 || lone_.kind != kLoneNone)
         return make_error(FSGPU_ERR_INVALID_CONFIG, "a begun search is outstanding on this index: end it first (the build takes both tickets)");
     FSGPU_TRY(fetch_live_host());
+
+    const size_t list_bytes = (size_t)m * 4;
+    uint64_t next = first_row;
+    const uint64_t end = first_row + n_rows;
+    // the next chunk's live sources; a tombstoned source costs no scan work: its list is padding, written here
+    auto next_chunk = [&](std::vector<uint32_t>& src, uint32_t cap) {
+        while (next < end && src.size() < cap) {
+            if (row_tombstoned(next)) {
+                const size_t at = (size_t)(next - first_row) * m;
+                for (uint32_t x = 0; x < m; ++x) out_rows[at + x] = kKnnPadRow;
+                if (out_sims)
+                    for (uint32_t x = 0; x < m; ++x) out_sims[at + x] = 0.0f;
+            } else {
+                src.push_back((uint32_t)next);
+            }
+            ++next;
+        }
+        return next < end;
+    };
+    // the chunk's sources are ascending; where they are consecutive rows (no tombstone between them) the lists go in one copy
+    auto sink = [&](const KnnStepLists& s) -> SearchError {
+        uint32_t i = 0;
+        while (i < s.n) {
+            uint32_t j = i + 1;
+            while (j < s.n && s.src[j] == s.src[j - 1] + 1) ++j;
+            const size_t at = (size_t)(s.src[i] - first_row) * m;
+            std::memcpy(out_rows + at, s.rows_host + (size_t)i * m, (size_t)(j - i) * list_bytes);
+            if (out_sims) std::memcpy(out_sims + at, s.sims_host + (size_t)i * m, (size_t)(j - i) * list_bytes);
+            i = j;
+        }
+        return ok();
+    };
+    return knn_search_steps((uint32_t)std::min<uint64_t>(kKnnChunk, n_rows), m, out_sims != nullptr, true, next_chunk, sink);
+}
+
+// The step loop of the build, over whatever sources next_chunk hands out (ascending local rows, up to cap per call; it returns
+// whether more may follow).  A drained step's lists reach `sink` in the pinned block (lists_to_host) or still in the step's device
+// block, on the emit stream, which is synchronised after the sink returns: the block is staged into again two steps later.
+SearchError VectorIndex::knn_search_steps(uint32_t cap, uint32_t m, bool want_sims, bool lists_to_host, const KnnNextChunk& next_chunk,
+                                          const KnnStepSink& sink) {
+    if (cap == 0) return ok();
     FSGPU_HIP(hipSetDevice(device_));
 
     const uint32_t k = m + 1;
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(kKnnChunk, n_rows);
     // device block of a step: queries | global sources | hit rows | hit scores | counts | out rows, out sims (the step's n * m rows,
     // then its n * m sims directly behind them: ONE copy brings both up)
     const size_t o_src = align256((size_t)cap * dim_ * 4), o_hrows = align256(o_src + (size_t)cap * 4),
@@ -150,29 +190,29 @@ SearchError VectorIndex::build_knn_graph(uint64_t first_row, uint64_t n_rows, ui
         e.n = s.n;
         e.m = m;
         e.out_rows = reinterpret_cast<uint32_t*>(s.dev + o_out);
-        e.out_sims = out_sims ? reinterpret_cast<float*>(s.dev + o_out + (size_t)s.n * list_bytes) : nullptr;
+        e.out_sims = want_sims ? reinterpret_cast<float*>(s.dev + o_out + (size_t)s.n * list_bytes) : nullptr;
         FSGPU_HIP(launch_knn_emit(e, sc.emit_stream));
-        FSGPU_HIP(hipMemcpyAsync(s.pin + p_out, s.dev + o_out, (size_t)s.n * list_bytes * (out_sims ? 2 : 1), hipMemcpyDeviceToHost, sc.emit_stream));
-        FSGPU_HIP(hipStreamSynchronize(sc.emit_stream));
-        const unsigned char* rows_pin = s.pin + p_out;
-        const unsigned char* sims_pin = rows_pin + (size_t)s.n * list_bytes;
-        // the chunk's sources are ascending; where they are consecutive rows (no tombstone between them) the lists go in one copy
-        uint32_t i = 0;
-        while (i < s.n) {
-            uint32_t j = i + 1;
-            while (j < s.n && s.src[j] == s.src[j - 1] + 1) ++j;
-            const size_t at = (size_t)(s.src[i] - first_row) * m;
-            std::memcpy(out_rows + at, rows_pin + (size_t)i * list_bytes, (size_t)(j - i) * list_bytes);
-            if (out_sims) std::memcpy(out_sims + at, sims_pin + (size_t)i * list_bytes, (size_t)(j - i) * list_bytes);
-            i = j;
+        KnnStepLists l{};
+        l.src = s.src.data();
+        l.n = s.n;
+        l.src_dev = e.src;
+        l.rows_dev = e.out_rows;
+        l.sims_dev = e.out_sims;
+        l.stream = sc.emit_stream;
+        if (lists_to_host) {
+            FSGPU_HIP(hipMemcpyAsync(s.pin + p_out, s.dev + o_out, (size_t)s.n * list_bytes * (want_sims ? 2 : 1), hipMemcpyDeviceToHost,
+                                     sc.emit_stream));
+            FSGPU_HIP(hipStreamSynchronize(sc.emit_stream));
+            l.rows_host = reinterpret_cast<const uint32_t*>(s.pin + p_out);
+            l.sims_host = want_sims ? reinterpret_cast<const float*>(s.pin + p_out + (size_t)s.n * list_bytes) : nullptr;
         }
+        FSGPU_TRY(sink(l));
+        if (!lists_to_host) FSGPU_HIP(hipStreamSynchronize(sc.emit_stream));
         last_knn_build.steps += 1;
         last_knn_build.sources += s.n;
         return ok();
     };
 
-    uint64_t next = first_row;
-    const uint64_t end = first_row + n_rows;
     uint64_t c = 0;
     bool more = true;
     while (true) {
@@ -180,20 +220,8 @@ SearchError VectorIndex::build_knn_graph(uint64_t first_row, uint64_t n_rows, ui
         cur.n = 0;
         cur.src.clear();
         if (more) {
-            // the next chunk's live sources; a tombstoned source costs no scan work: its list is padding, written here
-            while (next < end && cur.src.size() < cap) {
-                if (row_tombstoned(next)) {
-                    const size_t at = (size_t)(next - first_row) * m;
-                    for (uint32_t x = 0; x < m; ++x) out_rows[at + x] = kKnnPadRow;
-                    if (out_sims)
-                        for (uint32_t x = 0; x < m; ++x) out_sims[at + x] = 0.0f;
-                } else {
-                    cur.src.push_back((uint32_t)next);
-                }
-                ++next;
-            }
+            more = next_chunk(cur.src, cap);
             cur.n = (uint32_t)cur.src.size();
-            more = next < end;
             if (cur.n) {
                 const SearchError e = begin_step(cur);
                 if (!e.ok()) return abandon(e);

@@ -566,6 +566,47 @@ class VectorIndex:
                                                      _ptr(rows) if rows.size else None, _ptr(sims) if want_sims and sims.size else None))
         return (rows, sims) if want_sims else rows
 
+    def rewrite_sources(self):
+        """fsgpu_index_rewrite_sources: (new_to_old, generation_before, generation_after, old_record_count) of the last compact() /
+        vacuum() that changed the slab: new_to_old[x] is the old main row that row x is a copy of, 0xffffffff for a row from the WAL."""
+        out = np.full(self.record_count(), 0xFFFFFFFF, dtype=np.uint32)
+        before, after, old_n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(_lib.lib().fsgpu_index_rewrite_sources(self._h, _ptr(out) if out.size else None, C.byref(before), C.byref(after),
+                                                     C.byref(old_n)))
+        return out, before.value, after.value, old_n.value
+
+    def update_knn_graph(self, old_rows, old_sims, new_to_old=None, old_row_base: int = 0, max_added_fraction=None,
+                         want_stats: bool = False):
+        """fsgpu_index_update_knn_graph: the (rows, sims) build_knn_graph(m, want_sims=True) would return now, from the [old_len, m]
+        table of the index as it was and the map new row -> old row (rewrite_sources; None: nothing was renumbered, only the live
+        bitmap changed).  Only lists that lost an entry are searched again; every other list is the old one renumbered and joined
+        against the added rows.  With want_stats also a dict of fsgpu_knn_update_stats."""
+        r = np.ascontiguousarray(old_rows, dtype=np.uint32)
+        s = np.ascontiguousarray(old_sims, dtype=np.float32)
+        if r.ndim != 2 or s.shape != r.shape:
+            raise ValueError("old_rows and old_sims must both be [old_len, m]")
+        old_len, m = r.shape
+        n = self.record_count()
+        mp = None if new_to_old is None else np.ascontiguousarray(new_to_old, dtype=np.uint32)
+        if mp is not None and mp.shape != (n,):
+            raise ValueError("new_to_old must be [record_count]")
+        cfg = _lib.KnnUpdateConfig()
+        check(_lib.lib().fsgpu_knn_update_config_default(C.addressof(cfg)))
+        if max_added_fraction is not None:
+            cfg.max_added_fraction = float(max_added_fraction)
+        rows = np.full((n, m), 0xFFFFFFFF, dtype=np.uint32)
+        sims = np.zeros((n, m), dtype=np.float32)
+        # (empty arrays still hand over a non-null address: the call's own checks judge the shapes)
+        keep = np.zeros(1, dtype=np.uint32)
+        st = _lib.KnnUpdateStats()
+        check(_lib.lib().fsgpu_index_update_knn_graph(self._h, m, _ptr(r) if r.size else _ptr(keep), _ptr(s) if s.size else _ptr(keep),
+                                                      old_len, int(old_row_base), _ptr(mp) if mp is not None and mp.size else None,
+                                                      C.addressof(cfg), _ptr(rows) if rows.size else _ptr(keep),
+                                                      _ptr(sims) if sims.size else _ptr(keep), C.addressof(st)))
+        if not want_stats:
+            return rows, sims
+        return rows, sims, {name: getattr(st, name) for name, _ in _lib.KnnUpdateStats._fields_ if name != "reserved"}
+
     def optimize_knn_graph(self, table, out_degree: int, want_stats: bool = False):
         """fsgpu_knn_graph_optimize: a [record_count, w] neighbour table (build_knn_graph's) -> the [record_count, out_degree] table
         of detour-ordered forward edges and reverse edges, a pure function of the table and row_base.  With want_stats

@@ -167,7 +167,8 @@ fsgpu_status fsgpu_index_wal_append_batch(fsgpu_index *idx, uint32_t n, const ch
  *   - an fsgpu_allow_bitmap made before is refused (FSGPU_ERR_INVALID_CONFIG): make a new one;
  *   - the CALLER rebuilds what it derived: alignments (fsgpu_alignment_create), hubness tables (fsgpu_index_compute_query_hubness),
  *     k-NN graphs (fsgpu_index_build_knn_graph: after a compaction or a vacuum the rows are renumbered, so every entry of the table
- *     and every list's position names another row), allow bitmaps from fsgpu_index_allow_bitmap_for_hashes, and any fshost_two_tier searcher built over the index (libfshost does
+ *     and every list's position names another row — fsgpu_index_update_knn_graph carries the old table over instead of building
+ *     it again, with the map fsgpu_index_rewrite_sources hands out), allow bitmaps from fsgpu_index_allow_bitmap_for_hashes, and any fshost_two_tier searcher built over the index (libfshost does
  *     not follow a compaction);
  *   - doc-id pointers handed out by fsgpu_index_doc_id before the call are invalid. */
 typedef struct fsgpu_compaction_stats { /* wal::CompactionStats (wal.rs:111) */
@@ -1212,6 +1213,70 @@ fsgpu_status fsgpu_index_build_knn_graph(fsgpu_index *idx, uint64_t first_row, u
  * sharded search's own limits apply (dimension a multiple of 8). */
 fsgpu_status fsgpu_sharded_build_knn_graph(fsgpu_sharded *sh, uint64_t first_row, uint64_t n_rows, uint32_t m, uint32_t *out_rows,
                                            float *out_sims);
+/* ---- carrying the k-NN graph across a compaction, a vacuum or deletes ----
+ * The table is the most expensive object derived from an index and a rewrite renumbers its rows, yet nearly all of it survives: a
+ * compaction with W WAL entries changes the lists of the W new rows, of the sources that listed a dropped row, and of the sources for
+ * which a new row now beats their m-th neighbour.  Every other list is the old list with its ids renumbered.
+ * INPUTS.  The index as it is now (slab, live bitmap, row_base, hreduce order); m, 1 <= m <= 63; an old table old_rows [old_len, m]
+ * u32 and old_sims [old_len, m] f32, BOTH required, global ids relative to old_row_base with 0xffffffff / 0.0f padding; a map
+ * new_to_old [record_count] u32: entry x is the old LOCAL row that current row x is a byte-for-byte copy of, or 0xffffffff when x has
+ * no predecessor.  NULL means the identity with old_len == record_count: nothing was renumbered, only the live bitmap changed.
+ * GUARANTEE.  If old_rows / old_sims are what fsgpu_index_build_knn_graph(.., 0, old_len, m, ..) returned on an index in some state
+ * E0, new_to_old says truthfully which current rows are copies of which E0 rows, and the hreduce order is the same, then out_rows /
+ * out_sims [record_count, m] equal BYTE FOR BYTE what fsgpu_index_build_knn_graph(idx, 0, record_count, m, ..) returns on the
+ * current index.  The old table may come from another handle (an index since closed).  For inputs that break the premise the result
+ * is unspecified but memory-safe: every id of the table and the map is range-checked before it becomes an address.
+ * CLASSES of a current row x, a pure function of the inputs:
+ *   - dead: x is not live now.  Its list is all padding and it is nobody's target.
+ *   - added: x is live and has no predecessor, or its predecessor's old list is empty (column 0 is the pad: a row that was
+ *     tombstoned when the table was built and is live again, or a row of an index that then had one live row).  It gets a full search
+ *     and is a candidate for every other list.
+ *   - kept: x is live and its predecessor has a non-empty list.  Each old entry before the list's first pad is mapped global id ->
+ *     old local row -> current row (the inverse of new_to_old); it is DROPPED if its id lies outside [old_row_base, old_row_base +
+ *     old_len), it has no current row, or its current row is dead now.
+ *       kept-dirty: an entry is dropped.  The list lost a neighbour whose replacement is unknown: a full search.
+ *       kept-clean: otherwise.  The list is the first m under the total order of (the mapped old entries with their OLD sims) u
+ *       (the added rows a with score(x, a)), as global ids, then padding.
+ *   - monotonicity: that a kept-clean list is still the top-m over the kept rows needs ties to break as before, so the predecessors
+ *     must increase with x over the rows that have one (a compaction or a vacuum of a sorted record table guarantees it).  If they
+ *     do not, every kept row is dirty: a full rebuild inside the call, still exact, stats.rebuilt = 1.
+ * score(x, a) comes from a transposed exact join (knn_update_join_kernel): x widened to f32 in LDS, the added rows streamed past.
+ * Each product f32(x_e) * f32(a_e) commutes and the byte dots' accumulation order depends on the element index alone, so the join
+ * reproduces dot_product_f16_bytes_f32 / dot_product_f32_bytes_f32 bit for bit (leftover chunks into accumulator 0 before the tree
+ * for F16, after the tree for F32; a fused tail) in all three hreduce orders.
+ * FALLING BACK TO A REBUILD, the same table either way, every live row searched inside the call: rebuilt = 1 the map is not
+ * monotone; 2 added > max_added_fraction * record_count (compared in f64; the default is fsgpu_knn_update_config_default's); 3 a
+ * shape the join does not cover (dimension above 1,024, an MRL prefix view).  When several hold the first of 1, 3, 2 is reported.
+ * REFUSALS, FSGPU_ERR_INVALID_CONFIG before any work and with nothing written: m outside 1 .. 63; NULL tables or outputs; old_len >=
+ * 2^32 - 1; a new_to_old entry that is neither 0xffffffff nor < old_len; two current rows naming the same predecessor; identity mode
+ * with old_len != record_count; non-zero reserved words; a begun search outstanding (the call holds the index exactly as the graph
+ * build does and takes both tickets).  No device: FSGPU_ERR_NO_DEVICE.  An empty index: OK, nothing done.  out_* must not alias
+ * old_*.  All arrays are HOST arrays; the call blocks.  Sharded handles are not covered. */
+typedef struct fsgpu_knn_update_config {
+    float max_added_fraction;
+    uint32_t reserved[7]; /* must be 0 */
+} fsgpu_knn_update_config;
+fsgpu_status fsgpu_knn_update_config_default(fsgpu_knn_update_config *config);
+typedef struct fsgpu_knn_update_stats {
+    uint64_t rows, dead, added, kept_clean, kept_dirty;
+    uint64_t searched_sources; /* sources answered by the batched search: added + kept_dirty, or every live row when rebuilt */
+    uint64_t join_pairs;       /* kept_clean x added, 0 when rebuilt */
+    uint64_t join_entries;     /* entries of the OUTPUT's kept-clean lists that are added rows */
+    uint32_t rebuilt;          /* 0 incremental; 1 map not monotone; 2 added > max_added_fraction * rows; 3 a shape the join does not cover */
+    uint32_t reserved;
+    double device_ms, join_ms;
+} fsgpu_knn_update_stats;
+fsgpu_status fsgpu_index_update_knn_graph(fsgpu_index *idx, uint32_t m, const uint32_t *old_rows, const float *old_sims, uint64_t old_len,
+                                          uint32_t old_row_base, const uint32_t *new_to_old_or_null,
+                                          const fsgpu_knn_update_config *config_or_null, uint32_t *out_rows, float *out_sims,
+                                          fsgpu_knn_update_stats *stats_or_null);
+/* new row -> the main row of the index BEFORE the last compaction / vacuum that changed the slab it is a copy of, 0xffffffff for a
+ * row that came from the WAL.  out [record_count]; generation_before / _after (may be NULL) are fsgpu_index_generation on both sides;
+ * old_record_count (may be NULL) is the row count before.  The handle keeps the rewrite's runs, not 4 bytes per row.
+ * FSGPU_ERR_INVALID_CONFIG when no rewrite has happened on this handle.  Maps of several rewrites are not composed: update after
+ * each rewrite, or compose them. */
+fsgpu_status fsgpu_index_rewrite_sources(fsgpu_index *idx, uint32_t *out_new_to_old, uint64_t *generation_before, uint64_t *generation_after,
+                                         uint64_t *old_record_count);
 /* The graph optimisation: a neighbour table in, a navigable table of lower degree out.  An exact k-NN table is a poor
  * graph to search: its lists are redundant (a row's nearest neighbours are mostly each other's neighbours), no edge leaves a tight
  * group, and rows that nobody lists cannot be reached.  The repair is CAGRA's graph optimisation, restated as a PURE FUNCTION of the

@@ -335,6 +335,14 @@ fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash *h, const uint8_t *text_by
 fsgpu_status fsgpu_lab_wordpiece_encode_stage_ms(fsgpu_wordpiece *tok, const uint8_t *text_bytes, const uint32_t *offsets, uint32_t n,
                                                  int32_t add_special_tokens, uint32_t max_length, uint32_t *out_ids,
                                                  uint64_t ids_capacity, uint32_t *out_offsets, float *out_stage_ms);
+/* ONE launch of knn_update_join_kernel (fsgpu_index_update_knn_graph) through the guard-band harness: slab [nrows, dim]
+ * f16 (or f32 with slab_f32), dense rows; classes [nrows] (0 dead, 1 added, 2 kept-clean, 3 kept-dirty); work [nrows, m] IN AND OUT,
+ * a row's list as packed entries (score bits << 32 | local row), best first, ~0 past its end; added [n_added, dim] the added rows
+ * widened to f32 and added_rows [n_added] their local rows, 1 <= n_added <= 1,024.  Only kept-clean rows' lists may change.  The
+ * slab is followed by NaN guard rows and the working table sits between guard bands: a touched band is FSGPU_ERR_DEVICE. */
+fsgpu_status fsgpu_lab_knn_update_join(int32_t device, const void *slab, uint32_t slab_f32, uint32_t nrows, uint32_t dim, int32_t hreduce,
+                                       uint32_t m, const uint8_t *classes, uint64_t *work, const float *added, const uint32_t *added_rows,
+                                       uint32_t n_added);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
