@@ -37,8 +37,6 @@ constexpr size_t kOffFlags = kOffAdmit + kAnnMaxStepRows * 4;             // [2]
 constexpr size_t kOffSmall = kOffFlags + 2 * kAnnMaxEf;                   // sel[8] | stop[8] | wave counts[4] | admitted count | pad
 constexpr size_t kAnnStateBytes = kOffSmall + 24 * 4;
 
-__device__ __forceinline__ bool row_live(const u64* live, uint32_t r) { return !live || ((live[r >> 6] >> (r & 63u)) & 1ull); }
-
 // r = floor(i * n / n_entry) for some i < n_entry?  (n_entry <= n: the entry rows are distinct and i is unique)
 __device__ __forceinline__ bool is_entry_row(uint32_t r, uint32_t n, uint32_t n_entry) {
     const u64 i = ((u64)r * n_entry + n - 1) / n;

@@ -40,6 +40,9 @@ __device__ __forceinline__ u64 pack(float score, uint32_t row) {
     return ((u64)__float_as_uint(score) << 32) | row;
 }
 
+// bit r of a liveness bitmap; no bitmap: every row is live
+__device__ __forceinline__ bool row_live(const u64* live, uint64_t r) { return !live || ((live[r >> 6] >> (r & 63u)) & 1ull); }
+
 // Compiler-level ordering of LDS traffic inside ONE wave (DS ops of a wave execute in order in
 // hardware; this only stops hipcc from moving/caching accesses across the point).
 __device__ __forceinline__ void wave_lds_fence() {

@@ -485,10 +485,14 @@ struct MmrPlan {
 MmrPlan mmr_plan(uint32_t max_n, uint32_t dim, bool f32_staging, bool want_sims);
 hipError_t launch_mmr(const MmrArgs& args, uint32_t npools, const MmrPlan& plan, hipStream_t stream);
 
+// join_tile.hpp: the transposed exact join's tile, shared by hubness_kernels.hip and knn_update_kernels.hip.  A 16-lane group owns 4
+// rows, so a wave owns 16 in LDS; the other side streams past them in LDS chunks of 16 vectors.
+constexpr uint32_t kJoinTileRowsPerWave = 16, kJoinTileChunk = 16;
+
 // hubness_kernels.hip: the query-hubness table (hubness.rs:109-138) — per slab row the mean of its k greatest
 // dot_product_f32_f32 similarities to a query sample, selected under f32::total_cmp and summed in the canonical order
 // (include/fsgpu.h).  A workgroup owns 16 rows per wave in LDS and streams the sample past them in chunks of kHubQueryChunk.
-constexpr uint32_t kHubMaxK = 64, kHubMaxDim = 1024, kHubRowsPerWave = 16, kHubQueryChunk = 16;
+constexpr uint32_t kHubMaxK = 64, kHubMaxDim = 1024, kHubRowsPerWave = kJoinTileRowsPerWave, kHubQueryChunk = kJoinTileChunk;
 constexpr uint32_t kHubLaunchRows = 1u << 20;      // rows per launch: no single launch holds a shared card for long
 constexpr size_t kHubLdsBudget = 160 * 1024;
 struct HubnessArgs {
@@ -561,7 +565,7 @@ hipError_t launch_knn_emit(const KnnEmitArgs& args, hipStream_t stream);
 constexpr uint8_t kKnnUpdDead = 0, kKnnUpdAdded = 1, kKnnUpdClean = 2, kKnnUpdDirty = 3;   // the class byte of a current row
 constexpr uint32_t kKnnUpdMaxDim = 1024;           // dimensions the join covers
 constexpr uint32_t kKnnUpdBlock = 1024;            // added rows per join launch (one staged f32 block)
-constexpr uint32_t kKnnUpdRowsPerWave = 16, kKnnUpdChunk = 16;   // a 16-lane group owns 4 rows; added rows per LDS chunk
+constexpr uint32_t kKnnUpdRowsPerWave = kJoinTileRowsPerWave, kKnnUpdChunk = kJoinTileChunk;   // added rows per LDS chunk
 constexpr uint32_t kKnnUpdLaunchRows = 1u << 20;   // rows per join launch: no single launch holds a shared card for long
 constexpr size_t kKnnUpdLdsBudget = 159 * 1024;   // dynamic LDS of the join; the block vote's static bytes come on top
 // fsgpu_knn_update_config_default's max_added_fraction: of the swept 0.1 / 0.3 / 1 / 3 % of added rows at 1M x 384, m = 16, the

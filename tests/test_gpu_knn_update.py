@@ -414,7 +414,10 @@ def test_refusals_leave_the_outputs_untouched():
 
 # ---- 10. the join alone, one launch, between guard bands ----
 
-@pytest.mark.parametrize("dim,f32,mode", [(384, False, 0), (43, False, 2), (99, True, 0), (128, False, 1)])
+# (dim 520: the workgroup drops to 2 waves, one leftover chunk before the tree; 1000: 1 wave, f16; 1003: 1 wave, f32, one leftover chunk
+# after the tree and a fused tail of 3)
+@pytest.mark.parametrize("dim,f32,mode", [(384, False, 0), (43, False, 2), (99, True, 0), (128, False, 1), (520, False, 0), (1000, False, 2),
+                                          (1003, True, 1)])
 def test_one_join_launch_over_tiles_that_mix_all_four_classes(oracle, dim, f32, mode):
     fa = _fa()
     rng = np.random.default_rng(dim)
