@@ -267,6 +267,20 @@ SIGNATURES = {
     "fsgpu_ann_search": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "fsgpu_ann_last_stats": (_i32, [_vp, _vp]),
     "fsgpu_ann_certify_ef": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "fsgpu_ivf_config_default": (_i32, [_vp]),
+    "fsgpu_ivf_create": (_i32, [_vp, _u32, _vp, _vp, C.POINTER(_vp)]),
+    "fsgpu_ivf_destroy": (None, [_vp]),
+    "fsgpu_ivf_record_count": (_u64, [_vp]),
+    "fsgpu_ivf_device": (_i32, [_vp]),
+    "fsgpu_ivf_nlist": (_u32, [_vp]),
+    "fsgpu_ivf_centroids": (_i32, [_vp, _vp]),
+    "fsgpu_ivf_lists": (_i32, [_vp, _vp, _vp]),
+    "fsgpu_ivf_build_stats": (_i32, [_vp, _vp]),
+    "fsgpu_ivf_search_batched": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ivf_search_batched_device_queries": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ivf_search": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "fsgpu_ivf_last_stats": (_i32, [_vp, _vp]),
+    "fsgpu_ivf_certify_nprobe": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, C.c_double, C.c_double, _vp, _vp, _vp]),
     "fsgpu_conformal_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
     "fsgpu_mean_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
     "fsgpu_mean_recall_lower_bound_bernstein": (C.c_double, [_vp, _u64, C.c_double]),

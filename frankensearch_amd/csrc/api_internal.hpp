@@ -19,6 +19,7 @@
 #include "wordpiece.hpp"
 #include "index_builder.hpp"
 #include "ann_index.hpp"
+#include "ivf_index.hpp"
 #include "sharded_index.hpp"
 #include "vector_index.hpp"
 #include "two_tier_index.hpp"
@@ -111,6 +112,10 @@ struct fsgpu_wordpiece {
 };
 struct fsgpu_ann {   // a k-NN table resident on an index's device; searches take the index's locks
     fsgpu::AnnIndex impl;
+    fsgpu_index* idx = nullptr;
+};
+struct fsgpu_ivf {   // centroids and inverted lists resident on an index's device; every call takes the index's locks
+    fsgpu::IvfIndex impl;
     fsgpu_index* idx = nullptr;
 };
 

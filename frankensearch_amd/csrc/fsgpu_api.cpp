@@ -40,6 +40,23 @@ void ann_stats_out(const fsgpu::AnnStats& s, fsgpu_ann_stats* out) {
     out->device_ms = s.device_ms;
 }
 
+void ivf_stats_out(const fsgpu::IvfStats& s, fsgpu_ivf_stats* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->index_size = s.index_size;
+    out->dimension = s.dimension;
+    out->nlist = s.nlist;
+    out->nprobe = s.nprobe;
+    out->k_requested = s.k_requested;
+    out->launches = s.launches;
+    out->queries = s.queries;
+    out->approximate = s.approximate;
+    out->underfilled = s.underfilled;
+    out->empty_despite_indexed_points = s.empty_despite_indexed_points;
+    out->lists_probed = s.lists_probed;
+    out->rows_scored = s.rows_scored;
+    out->device_ms = s.device_ms;
+}
+
 void certified_out(const fsgpu::CertifiedEf& c, fsgpu_certified_ef* out) {
     out->ef_search = c.ef_search;
     out->meets_target = c.meets_target ? 1u : 0u;
@@ -1731,6 +1748,137 @@ fsgpu_status fsgpu_ann_certify_ef(fsgpu_ann* ann, const float* queries, uint32_t
         fsgpu::CertifiedEf best;
         uint32_t swept = 0;
         const fsgpu::SearchError e = ann->impl.certify_ef(queries, nq, candidate_efs, n_efs, k, target, alpha, &best, sweep.data(), &swept);
+        if (!e.ok()) return finish(e);
+        for (uint32_t i = 0; i < swept; ++i) certified_out(sweep[i], &sweep_out[i]);
+        certified_out(best, chosen);
+        *n_swept = swept;
+        return FSGPU_OK;
+    });
+}
+
+// ---- IVF index (ivf_index.cpp, ivf_kernels.hip) ----
+fsgpu_status fsgpu_ivf_config_default(fsgpu_ivf_config* config) {
+    if (!config) return fail(FSGPU_ERR_NULL_ARGUMENT, "config is null");
+    const fsgpu::IvfConfig d;
+    std::memset(config, 0, sizeof(*config));
+    config->iters = d.iters;
+    config->n_train = d.n_train;
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_ivf_create(fsgpu_index* idx, uint32_t nlist, const float* init_centroids, const fsgpu_ivf_config* config, fsgpu_ivf** out) {
+    if (!idx || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    *out = nullptr;
+    fsgpu::IvfConfig c;
+    if (config) {
+        if (config->reserved0) return fail(FSGPU_ERR_INVALID_CONFIG, "reserved words of fsgpu_ivf_config must be 0");
+        for (uint32_t r : config->reserved)
+            if (r) return fail(FSGPU_ERR_INVALID_CONFIG, "reserved words of fsgpu_ivf_config must be 0");
+        c.iters = config->iters;
+        c.n_train = config->n_train;
+    }
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(idx->state_mu);
+        std::lock_guard<std::mutex> lock(idx->impl.mutex());
+        auto a = std::make_unique<fsgpu_ivf>();
+        a->idx = idx;
+        const fsgpu::SearchError e = a->impl.init(&idx->impl, nlist, init_centroids, c);
+        if (!e.ok()) return finish(e);
+        *out = a.release();
+        return FSGPU_OK;
+    });
+}
+
+void fsgpu_ivf_destroy(fsgpu_ivf* ivf) { delete ivf; }
+uint64_t fsgpu_ivf_record_count(const fsgpu_ivf* ivf) { return ivf ? ivf->impl.record_count() : 0; }
+int32_t fsgpu_ivf_device(const fsgpu_ivf* ivf) { return ivf ? ivf->impl.device() : -1; }
+uint32_t fsgpu_ivf_nlist(const fsgpu_ivf* ivf) { return ivf ? ivf->impl.nlist() : 0; }
+
+fsgpu_status fsgpu_ivf_centroids(fsgpu_ivf* ivf, float* out) {
+    if (!ivf || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        return finish(ivf->impl.centroids(out));
+    });
+}
+
+fsgpu_status fsgpu_ivf_lists(fsgpu_ivf* ivf, uint64_t* out_offsets, uint32_t* out_rows) {
+    if (!ivf) return fail(FSGPU_ERR_NULL_ARGUMENT, "handle is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        return finish(ivf->impl.lists(out_offsets, out_rows));
+    });
+}
+
+fsgpu_status fsgpu_ivf_build_stats(const fsgpu_ivf* ivf, fsgpu_ivf_build_info* stats) {
+    if (!ivf || !stats) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    const fsgpu::IvfBuildStats& b = ivf->impl.build_stats();
+    std::memset(stats, 0, sizeof(*stats));
+    stats->iterations = b.iterations;
+    stats->rows_trained = b.rows_trained;
+    stats->rows_changed_last = b.rows_changed_last;
+    stats->empty_lists = b.empty_lists;
+    stats->largest_list = b.largest_list;
+    stats->smallest_list = b.smallest_list;
+    stats->assign_ms = b.assign_ms;
+    stats->update_ms = b.update_ms;
+    stats->lists_ms = b.lists_ms;
+    return FSGPU_OK;
+}
+
+static fsgpu_status ivf_search_common(fsgpu_ivf* ivf, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe,
+                                      uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* out_flags, bool on_device,
+                                      fsgpu_ivf_stats* stats) {
+    if (!ivf) return fail(FSGPU_ERR_NULL_ARGUMENT, "handle is null");
+    if (nq && (!queries || !out_counts || !out_rows || !out_scores)) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        fsgpu::IvfStats st;
+        const fsgpu::SearchError e = ivf->impl.search(queries, nq, query_len, k, nprobe, out_rows, out_scores, out_counts, out_flags, on_device, &st);
+        if (e.ok() && stats) ivf_stats_out(st, stats);
+        return finish(e);
+    });
+}
+
+fsgpu_status fsgpu_ivf_search_batched(fsgpu_ivf* ivf, const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe,
+                                      uint32_t* out_rows, float* out_scores, uint32_t* out_counts, uint32_t* out_flags,
+                                      fsgpu_ivf_stats* stats) {
+    return ivf_search_common(ivf, queries, nq, query_len, k, nprobe, out_rows, out_scores, out_counts, out_flags, false, stats);
+}
+
+fsgpu_status fsgpu_ivf_search_batched_device_queries(fsgpu_ivf* ivf, const float* queries_dev, uint32_t nq, uint32_t query_len,
+                                                     uint32_t k, uint32_t nprobe, uint32_t* out_rows_dev, float* out_scores_dev,
+                                                     uint32_t* out_counts_dev, uint32_t* out_flags_dev, fsgpu_ivf_stats* stats) {
+    return ivf_search_common(ivf, queries_dev, nq, query_len, k, nprobe, out_rows_dev, out_scores_dev, out_counts_dev, out_flags_dev, true, stats);
+}
+
+fsgpu_status fsgpu_ivf_search(fsgpu_ivf* ivf, const float* query, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t* out_rows,
+                              float* out_scores, uint32_t* out_count, uint32_t* out_flag, fsgpu_ivf_stats* stats) {
+    return ivf_search_common(ivf, query, 1, query_len, k, nprobe, out_rows, out_scores, out_count, out_flag, false, stats);
+}
+
+fsgpu_status fsgpu_ivf_last_stats(const fsgpu_ivf* ivf, fsgpu_ivf_stats* stats) {
+    if (!ivf || !stats) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+    ivf_stats_out(ivf->impl.last_stats(), stats);
+    return FSGPU_OK;
+}
+
+fsgpu_status fsgpu_ivf_certify_nprobe(fsgpu_ivf* ivf, const float* queries, uint32_t nq, const uint32_t* candidate_nprobes, uint32_t n_probes,
+                                      uint32_t k, double target, double alpha, fsgpu_certified_ef* chosen, fsgpu_certified_ef* sweep_out,
+                                      uint32_t* n_swept) {
+    if (!ivf || !chosen || !sweep_out || !n_swept || (!queries && nq) || (!candidate_nprobes && n_probes))
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        std::vector<fsgpu::CertifiedEf> sweep(n_probes);
+        fsgpu::CertifiedEf best;
+        uint32_t swept = 0;
+        const fsgpu::SearchError e = ivf->impl.certify_nprobe(queries, nq, candidate_nprobes, n_probes, k, target, alpha, &best, sweep.data(), &swept);
         if (!e.ok()) return finish(e);
         for (uint32_t i = 0; i < swept; ++i) certified_out(sweep[i], &sweep_out[i]);
         certified_out(best, chosen);

@@ -781,4 +781,58 @@ struct FilterGatherArgs {
 bool filter_gather_supported(uint32_t dim, uint32_t k);   // dim % 8 == 0, k <= kGatherMaxK, a tile of this dimension fits the LDS
 hipError_t launch_filter_gather_scan(const FilterGatherArgs& args, uint32_t ngroups, uint32_t grid_x, hipStream_t stream);
 
+// ivf_kernels.hip: the inverted-file index (ivf_index.cpp; include/fsgpu.h, "IVF index").  All pointers are device
+// memory.  The probed lists are scanned by launch_filter_gather_scan as it is: a probed list is a FilterGatherGroup.
+constexpr uint32_t kIvfMaxLists = 65536, kIvfMaxProbe = 256, kIvfMaxIters = 64;
+constexpr uint32_t kIvfMergeMaxEntries = 16384;   // nprobe * k: what the per-query merge sorts in LDS in one pass
+constexpr uint32_t kIvfNoSlot = 0xffffffffu;      // a (query, probed list) pair whose list is empty owns no slot
+constexpr uint32_t kIvfLaunchRows = 1u << 20;     // rows per assignment launch: no single launch holds a shared card for long
+constexpr size_t kIvfLdsBudget = 159 * 1024;      // dynamic LDS of the assignment; the block vote's static bytes come on top
+// Assignment, the third user of join_tile.hpp: slab rows in LDS, the centroids streamed past them, per row a running list of ONE
+// entry keyed (score_ord << 32 | ~centroid) — score descending with NaN as -inf, the lower centroid first.  The score is
+// dot_product_f16_bytes_f32(row, centroid) in the hreduce order: fsgpu_gather_dot's bits.
+struct IvfAssignArgs {
+    const void* slab;            // the index's f16 rows
+    uint32_t row_stride, dim;
+    int32_t hreduce;
+    uint32_t row0, nrows;        // this launch's rows [row0, row0 + nrows)
+    const u64* gate;             // bit r set = row r is assigned; nullptr = every row
+    const float* centroids;      // [nlist, dim]
+    uint32_t nlist;
+    uint32_t* assign;            // [slab rows]; a row outside the gate is not written
+};
+bool ivf_assign_supported(uint32_t dim);   // the tile of one wave fits the LDS
+hipError_t launch_ivf_assign(const IvfAssignArgs& args, hipStream_t stream);
+// rows r < n with gate bit set and assign[r] != prev[r], added to *out (an integer sum: no order reaches it)
+hipError_t launch_ivf_count_changed(const uint32_t* assign, const uint32_t* prev, const u64* gate, uint32_t n, u64* out, hipStream_t stream);
+// Lists from assign[n] (>= nlist: in no list): keys (nlist - list) << 32 | ~row sorted descending by the library's radix sort, i.e.
+// ascending (list, row), then offsets [nlist + 1] from the list boundaries of the sorted keys and rows [offsets[nlist]].  No atomics.
+// keys, sorted: [n] scratch; sort_temp: sort_keys_desc_temp_bytes(n).
+hipError_t launch_ivf_lists(const uint32_t* assign, uint32_t n, uint32_t nlist, u64* keys, u64* sorted, void* sort_temp, size_t sort_temp_bytes,
+                            u64* offsets, uint32_t* rows, hipStream_t stream);
+// Centroid update: per list with members and per dimension the f64 sum of the widened values SEQUENTIAL in ascending row order, the
+// f64 mean, norm2 = the sequential f64 sum over ascending d of mean_d * mean_d (a multiply and an add), and, when norm2 is finite and
+// > 0, centroid_d = (float)(mean_d / sqrt(norm2)); otherwise, and for a list without members, the centroid stays.
+struct IvfUpdateArgs {
+    const void* slab;
+    uint32_t row_stride, dim;
+    const uint32_t* list_rows;
+    const u64* offsets;          // [nlist + 1]
+    uint32_t nlist;
+    float* centroids;            // [nlist, dim] in and out
+};
+hipError_t launch_ivf_update(const IvfUpdateArgs& args, hipStream_t stream);
+// Per-query merge: query q reads the best-first lists (k packed entries each, kEmpty behind the entries) of its nprobe slots and
+// writes its best k — rows, scores, count — under sortkey.  nprobe * k <= kIvfMergeMaxEntries.
+struct IvfMergeArgs {
+    const u64* slot_lists;       // slot s at slot_lists + s * slot_stride
+    uint64_t slot_stride;
+    const uint32_t* qslots;      // [nq, nprobe] slot or kIvfNoSlot
+    uint32_t nprobe, k;
+    uint32_t* out_rows;          // [nq, k], 0xffffffff past the count
+    float* out_scores;           // [nq, k]
+    uint32_t* out_counts;        // [nq]
+};
+hipError_t launch_ivf_merge(const IvfMergeArgs& args, uint32_t nq, hipStream_t stream);
+
 }  // namespace fsgpu

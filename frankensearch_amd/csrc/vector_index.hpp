@@ -313,6 +313,15 @@ class VectorIndex {
     // the queries and the outputs; the slab, the live bitmap AS IT IS NOW, the shape and the hreduce order are filled in here.
     // Refused before the launch when the caps of ann_args_ok do not hold.  Enqueues on `stream`.
     SearchError ann_launch(AnnSearchArgs a, uint32_t nq, hipStream_t stream);
+    // What the IVF handle (ivf_index.cpp) reads of this index for its own launches: the slab, the live bitmap AS IT IS NOW and the
+    // shape.  Refused for an F32 slab, a truncated view, a catalog without a slab.
+    struct IvfSlabView {
+        const void* slab = nullptr;
+        const u64* live = nullptr;   // device; nullptr = all live
+        uint32_t nrows = 0, dim = 0, row_base = 0, row_stride = 0;
+        int num_cus = 0;
+    };
+    SearchError ivf_view(IvfSlabView* out) const;
 
     // VectorIndex::append_batch (lib.rs:2546-2720): every entry validated before anything changes, last-wins dedup inside the batch,
     // resident copies superseded, the first live main row of each doc id tombstoned, ONE live-bitmap upload.  wal_append is a batch of one.

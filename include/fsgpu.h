@@ -1463,6 +1463,104 @@ fsgpu_status fsgpu_ann_certify_ef(fsgpu_ann *ann, const float *queries, uint32_t
                                   uint32_t k, double target, double alpha, fsgpu_certified_ef *chosen, fsgpu_certified_ef *sweep_out,
                                   uint32_t *n_swept);
 
+/* ---- IVF index: device k-means, probed-list search, certified nprobe ---- */
+/* An inverted-file index over an index's rows (the reference pins a Lloyd k-means IVF in
+ * crates/frankensearch-index/tests/ivf_recall_test.rs): the rows are partitioned by a coarse quantiser trained on the device and a
+ * search scores only the lists nearest to the query.  THE INDEX AND EVERY ANSWER ARE PURE FUNCTIONS of their inputs, returned bit
+ * for bit; only recall is statistical, and it is certified (fsgpu_ivf_certify_nprobe), never assumed.
+ *   scope     F16 slabs whose dimension is a multiple of 8 and which the segmented gather scan covers; 1 <= nlist <= 65,536 and
+ *             nlist <= the number of training rows; 0 <= iters <= 64; per call 1 <= k <= 256, 1 <= nprobe <= min(nlist, 256) and
+ *             nprobe * k <= 16,384 (the per-query merge sorts a query's lists in LDS in one pass).  Everything else is
+ *             FSGPU_ERR_INVALID_CONFIG (FSGPU_ERR_DIMENSION_MISMATCH for the query length), refused before any launch; nothing
+ *             is written.  The handle records fsgpu_index_generation and the index's hreduce order at create and refuses every
+ *             call once either has changed, as an fsgpu_allow_bitmap does.
+ *   scores    row against centroid (training, assignment): the bits fsgpu_gather_dot(idx, centroid, [row]) returns —
+ *             dot_product_f16_bytes_f32 in the index's hreduce order with the centroid as the f32 query.  Query against centroid
+ *             (the coarse step): dot_product_f32_bytes_f32(centroid row, query) in the same order — what an F32 index over the
+ *             [nlist, dim] centroid matrix answers.  Row against query: the exact search's bits.
+ *   order     everywhere the reference's total order (search.rs:91-126): score descending with NaN as -inf, the lower id first —
+ *             centroid ids and row ids alike.  A row whose every score is NaN goes to list 0.
+ *   training  the training rows are the live rows among floor(i * N / n_train), i < n_train, ascending (n_train == 0 or >= N:
+ *             every live row); T is their count.  Initial centroid c is init_centroids[c] (every value finite, else refused) or,
+ *             with a NULL init_centroids, the f32 widening of training row number floor(c * T / nlist).  Then, iters times: every
+ *             training row takes its best centroid; per list with members, taken in ascending row order, and per dimension d:
+ *             s = the f64 sum of the widened values, SEQUENTIAL in that order; mean_d = s / count (f64); norm2 = the sequential
+ *             f64 sum over ascending d of mean_d * mean_d (a multiply and an add); when norm2 is finite and > 0 the new value is
+ *             (float)(mean_d / sqrt(norm2)), otherwise the centroid stays.  A list without members keeps its centroid
+ *             (ivf_recall_test.rs:105-112).  Finally ALL live rows are assigned to the final centroids.
+ *   index     list_offsets [nlist + 1] and list_rows: LOCAL row ids, ascending inside a list; dead rows are in no list.
+ *   search    the nprobe best centroids; the candidates are the rows of their lists that are live NOW (deletes made after the
+ *             build are honoured); the answer is the best min(k, |candidates|) by the exact score, row ids global (row_base
+ *             added).  Lists are disjoint and keys unique: neither the order in which lists are scanned nor the batch position
+ *             reaches the result, and nprobe == nlist is the exact search.  Entries past a count are unspecified.
+ *   fallback  (hnsw.rs:299-309) a query whose count is below min(k, live rows) is answered again by the handle's exact batched
+ *             search and flagged FSGPU_ANN_UNDERFILLED, or FSGPU_ANN_EMPTY_DESPITE_INDEXED_POINTS when its count was 0.
+ * Out of scope: F32 slabs, allow-bitmap filters, WAL entries and doc-id dedup (row-level, like fsgpu_search_topk), sharded handles. */
+typedef struct fsgpu_ivf fsgpu_ivf;
+typedef struct fsgpu_ivf_config {
+    uint32_t iters;       /* Lloyd iterations, 0 .. 64.  Default 8 */
+    uint32_t reserved0;   /* must be 0 */
+    uint64_t n_train;     /* strided training sample; 0 or >= record_count: every live row.  Default 0 */
+    uint32_t reserved[4]; /* must be 0 */
+} fsgpu_ivf_config;
+typedef struct fsgpu_ivf_build_info {
+    uint32_t iterations;
+    uint32_t reserved0;
+    uint64_t rows_trained;        /* T */
+    uint64_t rows_changed_last;   /* training rows whose list in the last iteration differs from the one before (first: all) */
+    uint64_t empty_lists, largest_list, smallest_list;   /* of the final lists */
+    double assign_ms, update_ms, lists_ms;   /* device time per stage, summed over the iterations and the final assignment */
+} fsgpu_ivf_build_info;
+/* Summed over one call.  For fsgpu_ivf_certify_nprobe: summed over the searches of the sweep, with nprobe the LARGEST launched. */
+typedef struct fsgpu_ivf_stats {
+    uint64_t index_size;   /* record_count */
+    uint32_t dimension;
+    uint32_t nlist;
+    uint32_t nprobe;
+    uint32_t k_requested;
+    uint32_t launches;     /* coarse searches and gather-scan launches */
+    uint32_t reserved0;
+    uint64_t queries;
+    uint64_t approximate, underfilled, empty_despite_indexed_points; /* queries per flag value */
+    uint64_t lists_probed; /* (query, list) pairs */
+    uint64_t rows_scored;  /* the sum of the list lengths over all (query, list) pairs */
+    double device_ms;      /* from the coarse search to the per-query merge, the host plan between them included */
+} fsgpu_ivf_stats;
+fsgpu_status fsgpu_ivf_config_default(fsgpu_ivf_config *config);
+/* Trains the centroids and builds the lists on the index's device; blocks.  init_centroids: HOST [nlist, dimension] or NULL; a
+ * NULL config means the defaults.  The index must outlive the handle. */
+fsgpu_status fsgpu_ivf_create(fsgpu_index *idx, uint32_t nlist, const float *init_centroids, const fsgpu_ivf_config *config,
+                              fsgpu_ivf **out);
+void fsgpu_ivf_destroy(fsgpu_ivf *ivf);
+uint64_t fsgpu_ivf_record_count(const fsgpu_ivf *ivf);
+int32_t fsgpu_ivf_device(const fsgpu_ivf *ivf);
+uint32_t fsgpu_ivf_nlist(const fsgpu_ivf *ivf);
+/* out: HOST [nlist, dimension], the final centroids.  With iters = 0 and iters = 1 the two getters expose the assignment and the
+ * update one launch at a time. */
+fsgpu_status fsgpu_ivf_centroids(fsgpu_ivf *ivf, float *out);
+/* out_offsets: HOST [nlist + 1]; out_rows: HOST [out_offsets[nlist]] (the live rows at create), either may be NULL. */
+fsgpu_status fsgpu_ivf_lists(fsgpu_ivf *ivf, uint64_t *out_offsets, uint32_t *out_rows);
+/* What the build did and what it cost. */
+fsgpu_status fsgpu_ivf_build_stats(const fsgpu_ivf *ivf, fsgpu_ivf_build_info *stats);
+/* The argument shapes of the fsgpu_ann_search* trio with nprobe for ef: HOST pointers / device pointers / a batch of one. */
+fsgpu_status fsgpu_ivf_search_batched(fsgpu_ivf *ivf, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe,
+                                      uint32_t *out_rows, float *out_scores, uint32_t *out_counts, uint32_t *out_flags,
+                                      fsgpu_ivf_stats *stats);
+fsgpu_status fsgpu_ivf_search_batched_device_queries(fsgpu_ivf *ivf, const float *queries_dev, uint32_t nq, uint32_t query_len,
+                                                     uint32_t k, uint32_t nprobe, uint32_t *out_rows_dev, float *out_scores_dev,
+                                                     uint32_t *out_counts_dev, uint32_t *out_flags_dev, fsgpu_ivf_stats *stats);
+fsgpu_status fsgpu_ivf_search(fsgpu_ivf *ivf, const float *query, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t *out_rows,
+                              float *out_scores, uint32_t *out_count, uint32_t *out_flag, fsgpu_ivf_stats *stats);
+/* The stats of the last search or certify call on the handle. */
+fsgpu_status fsgpu_ivf_last_stats(const fsgpu_ivf *ivf, fsgpu_ivf_stats *stats);
+/* fsgpu_ann_certify_ef with nprobe candidates: the exact top-k ONCE per query from the handle's exact batched search; the candidates
+ * de-duplicated and taken in ascending order; recall_at_k_of over rows, 0.0 for a flagged query; the conformal bound after each;
+ * no launch past the first nprobe that meets the target.  ef_search of fsgpu_certified_ef carries nprobe.  Every candidate must
+ * satisfy the call's limits and n_probes >= 1, checked before any launch. */
+fsgpu_status fsgpu_ivf_certify_nprobe(fsgpu_ivf *ivf, const float *queries, uint32_t nq, const uint32_t *candidate_nprobes,
+                                      uint32_t n_probes, uint32_t k, double target, double alpha, fsgpu_certified_ef *chosen,
+                                      fsgpu_certified_ef *sweep_out, uint32_t *n_swept);
+
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */
 typedef struct fsgpu_mrl_stats {
