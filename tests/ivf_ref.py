@@ -8,13 +8,18 @@ device returns all of it bit for bit.
   pairwise_sum   np.sum (pairwise) in the place of the sequential f64 sum
   no_normalise   the mean is stored as it is
   reseed_empty   a list without members takes the first training row's widening instead of keeping its centroid
-  dead_at_build  the live bitmap of the build is used at search time (deletes made after the build are ignored)"""
+  dead_at_build  the live bitmap of the build is used at search time (deletes made after the build are ignored)
+  stride_k_tiles a probed list's best k are read k entries apart from a table that holds them 64 apart (k < 64, lists of one tile)
+  stop_at_empty  an empty probed list ends the query's candidates: the lists probed after it are dropped
+  first_launch   rows from LAUNCH_ROWS on (the assignment's second launch) are never assigned"""
 import numpy as np
 
 import ann_ref
 
 F32 = np.float32
 APPROXIMATE, UNDERFILLED, EMPTY = 0, 1, 2
+LAUNCH_ROWS = 1 << 20   # kernels.hpp kIvfLaunchRows: rows per assignment launch
+TILE_ROWS = 64          # kernels.hpp kGatherTileRows: a scan block's partial list is 64 entries wide for k <= 64
 
 
 def bits(a):
@@ -67,6 +72,8 @@ def assign(scores, gate, rules=frozenset()):
         keys = (score_ord(scores) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - ids)
     best = np.argmax(keys, axis=0).astype(np.int64)
     best[~np.asarray(gate, dtype=bool)] = -1
+    if "first_launch" in rules:
+        best[LAUNCH_ROWS:] = -1
     return best
 
 
@@ -150,9 +157,25 @@ def search(oracle, slab_u16, index, query, k, nprobe, live_now=None, row_base=0,
     live = index.live if (live_now is None or "dead_at_build" in rules) else np.asarray(live_now, dtype=bool)
     true_live = index.live if live_now is None else np.asarray(live_now, dtype=bool)
     lists = probe(oracle, index, query, nprobe)
+    if "stop_at_empty" in rules:
+        empty = [i for i, l in enumerate(lists) if index.list_rows(int(l)).size == 0]
+        lists = lists[:empty[0]] if empty else lists
     cand = np.concatenate([index.list_rows(int(l)) for l in lists]) if len(lists) else np.zeros(0, np.uint32)
     cand = cand[live[cand]].astype(np.uint32)
     sc = row_scores[cand] if row_scores is not None else oracle.gather_dot(slab_u16, query, cand, index.hreduce)
+    if "stride_k_tiles" in rules and k < TILE_ROWS:
+        # the table of the query's slots: per probed list its best k, best first, in a row of TILE_ROWS entries; read k apart
+        table = np.full((len(lists), TILE_ROWS), -1, dtype=np.int64)   # positions in cand; -1: no entry
+        at = 0
+        for j, l in enumerate(lists):
+            n = int(live[index.list_rows(int(l))].sum())
+            mine = np.arange(at, at + n)
+            best = mine[np.argsort(order_keys(sc[mine], cand[mine]), kind="stable")[::-1][:k]]
+            table[j, :best.size] = best
+            at += n
+        read = np.concatenate([table.ravel()[j * k:j * k + k] for j in range(len(lists))]) if len(lists) else np.zeros(0, np.int64)
+        read = read[read >= 0]
+        cand, sc = cand[read], np.asarray(sc, dtype=F32)[read]
     order = np.argsort(order_keys(sc, cand), kind="stable")[::-1][:k]
     rows, scores = cand[order], np.asarray(sc, dtype=F32)[order]
     need = min(k, int(true_live.sum()))
