@@ -281,6 +281,13 @@ SIGNATURES = {
     "fsgpu_ivf_search": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "fsgpu_ivf_last_stats": (_i32, [_vp, _vp]),
     "fsgpu_ivf_certify_nprobe": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "fsgpu_ivf_set_list_filter": (_i32, [_vp, _u32]),
+    "fsgpu_ivf_list_filter": (_u32, [_vp]),
+    "fsgpu_ivf_last_filter_stats": (_i32, [_vp, _vp]),
+    "fsgpu_lab_ivf_filter_stage": (_i32, [_vp, _vp]),
+    "fsgpu_lab_ivf_filter_set_scratch": (_i32, [_vp, _u64]),
+    "fsgpu_lab_ivf_filter_score_plan": (_i32, [_u32, _vp, _vp, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "fsgpu_lab_ivf_filter_scan_plan": (_i32, [_u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "fsgpu_conformal_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
     "fsgpu_mean_recall_lower_bound": (C.c_double, [_vp, _u64, C.c_double]),
     "fsgpu_mean_recall_lower_bound_bernstein": (C.c_double, [_vp, _u64, C.c_double]),

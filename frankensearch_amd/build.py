@@ -16,9 +16,9 @@ OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libfsgpu.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
-SOURCES = ["scan_kernels.hip", "scan_mq_kernel.hip", "int8_kernels.hip", "f32_kernels.hip", "mfma_scan.hip", "mfma_wide.hip", "sort_general.hip", "m2v_kernels.hip", "bert_kernels.hip", "bert_gemm_w.hip", "bert_docs_w.hip", "bert_query_kernels.hip", "bert_int8.hip", "bert_rerank.hip", "mmr_kernels.hip", "hubness_kernels.hip", "compact_kernels.hip", "knn_graph_kernels.hip", "knn_optimize_kernels.hip", "knn_update_kernels.hip", "ann_kernels.hip", "search_hits_kernels.hip", "index_build_kernels.hip", "hash_embed_kernels.hip", "wordpiece_kernels.hip", "filter_gather_kernels.hip", "ivf_kernels.hip", "bench_fixture.hip", "vector_index.cpp", "vector_index_batched.cpp", "vector_index_lone.cpp", "vector_index_mmr.cpp", "vector_index_hubness.cpp", "vector_index_compact.cpp", "vector_index_knn.cpp", "vector_index_knn_optimize.cpp", "vector_index_knn_update.cpp", "ann_index.cpp", "ivf_index.cpp", "vector_index_hits.cpp", "vector_index_filtered.cpp", "index_builder.cpp", "hash_embedder.cpp", "wordpiece.cpp", "two_tier_index.cpp", "sharded_index.cpp",
+SOURCES = ["scan_kernels.hip", "scan_mq_kernel.hip", "int8_kernels.hip", "f32_kernels.hip", "mfma_scan.hip", "mfma_wide.hip", "sort_general.hip", "m2v_kernels.hip", "bert_kernels.hip", "bert_gemm_w.hip", "bert_docs_w.hip", "bert_query_kernels.hip", "bert_int8.hip", "bert_rerank.hip", "mmr_kernels.hip", "hubness_kernels.hip", "compact_kernels.hip", "knn_graph_kernels.hip", "knn_optimize_kernels.hip", "knn_update_kernels.hip", "ann_kernels.hip", "search_hits_kernels.hip", "index_build_kernels.hip", "hash_embed_kernels.hip", "wordpiece_kernels.hip", "filter_gather_kernels.hip", "ivf_kernels.hip", "ivf_filter_kernels.hip", "bench_fixture.hip", "vector_index.cpp", "vector_index_batched.cpp", "vector_index_lone.cpp", "vector_index_mmr.cpp", "vector_index_hubness.cpp", "vector_index_compact.cpp", "vector_index_knn.cpp", "vector_index_knn_optimize.cpp", "vector_index_knn_update.cpp", "ann_index.cpp", "ivf_index.cpp", "vector_index_hits.cpp", "vector_index_filtered.cpp", "index_builder.cpp", "hash_embedder.cpp", "wordpiece.cpp", "two_tier_index.cpp", "sharded_index.cpp",
            "bert_embedder.cpp", "bert_reranker.cpp", "safetensors.cpp", "fusion.cpp", "fsgpu_api.cpp", "fsgpu_lab_api.cpp"]
-HEADERS = ["device_util.hpp", "scan_common.hpp", "kernels.hpp", "join_tile.hpp", "vector_index.hpp", "vector_index_internal.hpp", "bert_embedder.hpp", "bert_reranker.hpp", "coalescer.hpp", "sharded_index.hpp", "two_tier_index.hpp", "lab_env.hpp", "mmr.hpp", "hubness.hpp", "index_builder.hpp", "hash_embedder.hpp", "wordpiece.hpp", "ann_index.hpp", "ivf_index.hpp", "api_internal.hpp", "lab_guard.hpp"]
+HEADERS = ["device_util.hpp", "scan_common.hpp", "kernels.hpp", "join_tile.hpp", "vector_index.hpp", "vector_index_internal.hpp", "bert_embedder.hpp", "bert_reranker.hpp", "coalescer.hpp", "sharded_index.hpp", "two_tier_index.hpp", "lab_env.hpp", "mmr.hpp", "hubness.hpp", "index_builder.hpp", "hash_embedder.hpp", "wordpiece.hpp", "ann_index.hpp", "ivf_index.hpp", "ivf_filter_plan.hpp", "ivf_filter_tile.hpp", "api_internal.hpp", "lab_guard.hpp"]
 # libfshost.so: the C++ host-side mirror of the reference's two-tier searcher, over the C ABI only (include/fshost.h)
 HOST_LIB = os.path.join(HERE, "libfshost.so")
 HOST_SOURCES = ["host/two_tier_searcher.cpp", "host/two_tier_many.cpp", "host/load_driver.cpp", "host/stream_pipeline.cpp", "host/fshost_api.cpp"]

@@ -1867,6 +1867,49 @@ fsgpu_status fsgpu_ivf_last_stats(const fsgpu_ivf* ivf, fsgpu_ivf_stats* stats) 
     return FSGPU_OK;
 }
 
+fsgpu_status fsgpu_ivf_set_list_filter(fsgpu_ivf* ivf, uint32_t mode) {
+    if (!ivf) return fail(FSGPU_ERR_NULL_ARGUMENT, "handle is null");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        return finish(ivf->impl.set_list_filter(mode));
+    });
+}
+
+uint32_t fsgpu_ivf_list_filter(const fsgpu_ivf* ivf) {
+    if (!ivf) return 0;
+    std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+    return ivf->impl.list_filter();
+}
+
+fsgpu_status fsgpu_ivf_last_filter_stats(const fsgpu_ivf* ivf, fsgpu_ivf_filter_stats* out) {
+    if (!ivf || !out) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+    const fsgpu::IvfFilterStats s = ivf->impl.last_filter_stats();
+    std::memset(out, 0, sizeof(*out));
+    out->mode = s.mode;
+    out->rotated = s.rotated;
+    out->slot_cap = s.slot_cap;
+    out->k_cap = s.k_cap;
+    out->scratch_cap = s.scratch_cap;
+    out->copy_bytes = s.copy_bytes;
+    out->build_ms = s.build_ms;
+    out->queries_filtered = s.queries_filtered;
+    out->queries_uncertified = s.queries_uncertified;
+    out->calls_above_k_cap = s.calls_above_k_cap;
+    out->slots_filtered = s.slots_filtered;
+    out->slots_overflowed = s.slots_overflowed;
+    out->slots_above_scratch = s.slots_above_scratch;
+    out->scratch_ranges = s.scratch_ranges;
+    out->rows_filtered = s.rows_filtered;
+    out->rows_rescored = s.rows_rescored;
+    out->filter_ms = s.filter_ms;
+    out->select_ms = s.select_ms;
+    out->rescore_ms = s.rescore_ms;
+    out->rows_streamed = s.rows_streamed;
+    return FSGPU_OK;
+}
+
 fsgpu_status fsgpu_ivf_certify_nprobe(fsgpu_ivf* ivf, const float* queries, uint32_t nq, const uint32_t* candidate_nprobes, uint32_t n_probes,
                                       uint32_t k, double target, double alpha, fsgpu_certified_ef* chosen, fsgpu_certified_ef* sweep_out,
                                       uint32_t* n_swept) {

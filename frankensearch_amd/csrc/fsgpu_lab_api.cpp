@@ -1306,6 +1306,143 @@ fsgpu_status fsgpu_lab_knn_update_join(int32_t device, const void* slab, uint32_
     });
 }
 
+// ---- the IVF index's int8 list filter ----
+fsgpu_status fsgpu_lab_ivf_filter_stage(fsgpu_ivf* ivf, const fsgpu_lab_ivf_filter_stage_args* a) {
+    if (!ivf || !a || !a->queries || !a->out_delta || !a->out_ran || !a->out_nslots || !a->out_slot_query || !a->out_slot_list ||
+        !a->out_slot_offset || !a->out_scores || !a->out_t || !a->out_m || !a->out_count || !a->out_flag || !a->out_cand)
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (a->nq < 1) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter stage: no query");
+    return guarded([&]() -> fsgpu_status {
+        std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+        std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+        if (const fsgpu_status opened = LabStage::open(ivf->impl.device()); opened != FSGPU_OK) return opened;
+        LabStage s;
+        std::vector<unsigned char> host[6];
+        fsgpu::IvfFilterLab flab;
+        flab.alloc = [&](fsgpu::IvfFilterLab::Which w, size_t bytes) -> void* {
+            host[w].assign(bytes, 0);
+            void* p = s.out_bytes(bytes, lab::kGuardByte, host[w].data());
+            s.hip(hipDeviceSynchronize());   // (the prefill ran on the null stream, the search runs on the index's)
+            return s.ok() ? p : nullptr;
+        };
+        const size_t hits = (size_t)a->nq * std::max<uint32_t>(a->k, 1);
+        std::vector<uint32_t> rows(hits), counts(a->nq), flags(a->nq);
+        std::vector<float> scores(hits);
+        const fsgpu::SearchError e = ivf->impl.search(a->queries, a->nq, a->query_len, a->k, a->nprobe, rows.data(), scores.data(), counts.data(),
+                                                     flags.data(), false, nullptr, &flab);
+        if (!e.ok()) return finish(e);
+        const fsgpu_status st = s.status("ivf filter: a kernel wrote into a guard band of its output");
+        if (st != FSGPU_OK) return st;
+        std::memcpy(a->out_delta, flab.delta.data(), (size_t)a->nq * 4);
+        *a->out_ran = flab.ran ? 1u : 0u;
+        *a->out_nslots = 0;
+        if (a->out_ordered) {
+            const fsgpu::SearchError eo = ivf->impl.filter_ordered_copy(reinterpret_cast<signed char*>(a->out_ordered));
+            if (!eo.ok()) return finish(eo);
+        }
+        if (!flab.ran) return FSGPU_OK;
+        const uint32_t slots = (uint32_t)flab.slot_query.size();
+        if (slots > a->slots_cap) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter stage: slots_cap is below the call's slots");
+        const int32_t* sc = reinterpret_cast<const int32_t*>(host[fsgpu::IvfFilterLab::kScores].data());
+        uint64_t off = 0;
+        for (uint32_t sl = 0; sl < slots; ++sl) {
+            const fsgpu::IvfFilterTile& t = flab.tiles[flab.slot_tile[sl]];
+            const uint64_t len_pad = fsgpu::ivf_filter::round_up(t.len, fsgpu::kIvfFilterRowTile);
+            const int32_t* src = sc + t.scratch0 + (uint64_t)(sl - t.slot0) * len_pad;
+            if (off + t.len > a->scores_cap) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter stage: scores_cap is below the call's scores");
+            a->out_slot_offset[sl] = off;
+            std::memcpy(a->out_scores + off, src, (size_t)t.len * 4);
+            for (uint64_t i = t.len; i < len_pad; ++i)
+                if (src[i] != fsgpu::kIvfFilterDead) return fail(FSGPU_ERR_DEVICE, "ivf filter: a padding row of the scores is not the sentinel");
+            off += t.len;
+        }
+        a->out_slot_offset[slots] = off;
+        std::memcpy(a->out_slot_query, flab.slot_query.data(), (size_t)slots * 4);
+        std::memcpy(a->out_slot_list, flab.slot_list.data(), (size_t)slots * 4);
+        std::memcpy(a->out_t, host[fsgpu::IvfFilterLab::kT].data(), (size_t)slots * 4);
+        std::memcpy(a->out_m, host[fsgpu::IvfFilterLab::kM].data(), (size_t)slots * 8);
+        std::memcpy(a->out_count, host[fsgpu::IvfFilterLab::kCount].data(), (size_t)slots * 4);
+        std::memcpy(a->out_flag, host[fsgpu::IvfFilterLab::kFlag].data(), (size_t)slots * 4);
+        std::memcpy(a->out_cand, host[fsgpu::IvfFilterLab::kCand].data(), (size_t)slots * fsgpu::kIvfFilterSlotCap * 4);
+        *a->out_nslots = slots;
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_lab_ivf_filter_set_scratch(fsgpu_ivf* ivf, uint64_t entries) {
+    if (!ivf) return fail(FSGPU_ERR_NULL_ARGUMENT, "handle is null");
+    std::shared_lock<std::shared_mutex> state(ivf->idx->state_mu);
+    std::lock_guard<std::mutex> lock(ivf->idx->impl.mutex());
+    ivf->impl.set_filter_scratch_entries(entries);
+    return FSGPU_OK;
+}
+
+extern "C++" {
+namespace {
+fsgpu::ivf_filter::Caps lab_filter_caps(uint64_t scratch_cap) {
+    return fsgpu::ivf_filter::Caps{scratch_cap ? scratch_cap : fsgpu::kIvfFilterScratchEntries, fsgpu::kIvfFilterTileQueries, fsgpu::kIvfFilterRowTile,
+                                   fsgpu::kIvfFilterItemRows, fsgpu::kIvfFilterSlotCap};
+}
+std::vector<uint32_t> lab_filter_head(uint32_t nlist, const uint32_t* members) {
+    std::vector<uint32_t> head((size_t)nlist + 1, 0u);
+    for (uint32_t l = 0; l < nlist; ++l) head[l + 1] = head[l] + members[l];
+    return head;
+}
+}  // namespace
+}  // extern "C++"
+
+fsgpu_status fsgpu_lab_ivf_filter_score_plan(uint32_t nlist, const uint64_t* offsets, const uint32_t* members, uint64_t scratch_cap, uint32_t tiles_cap,
+                                             uint64_t* out_tiles, uint32_t* out_ntiles, uint32_t ranges_cap, uint64_t* out_ranges,
+                                             uint32_t* out_nranges, uint32_t* out_slots) {
+    if (!offsets || !members || !out_tiles || !out_ntiles || !out_ranges || !out_nranges || !out_slots)
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    return guarded([&]() -> fsgpu_status {
+        uint64_t total = 0;
+        const std::vector<uint64_t> first = fsgpu::ivf_filter::pad_rows(nlist, offsets, fsgpu::kIvfFilterRowTile, &total);
+        const std::vector<uint32_t> head = lab_filter_head(nlist, members);
+        const fsgpu::ivf_filter::ScorePlan p = fsgpu::ivf_filter::score_plan(nlist, offsets, head.data(), first.data(), lab_filter_caps(scratch_cap));
+        const uint32_t ntiles = (uint32_t)p.tiles.size() - 1;
+        if (ntiles > tiles_cap || p.ranges.size() > ranges_cap) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter plan: an output capacity is too small");
+        for (uint32_t t = 0; t < ntiles; ++t) {
+            const fsgpu::IvfFilterTile& x = p.tiles[t];
+            const uint64_t row[8] = {x.ordered_row0, x.list_pos0, x.scratch0, x.len, x.slot0, x.nmem, x.item0, p.above[t]};
+            std::memcpy(out_tiles + (size_t)t * 8, row, sizeof(row));
+        }
+        for (size_t r = 0; r < p.ranges.size(); ++r) {
+            const fsgpu::ivf_filter::Range& x = p.ranges[r];
+            const uint64_t row[7] = {x.tile_first, x.ntiles, x.item_first, x.nitems, x.slot_first, x.nslots, x.entries};
+            std::memcpy(out_ranges + r * 7, row, sizeof(row));
+        }
+        *out_ntiles = ntiles;
+        *out_nranges = (uint32_t)p.ranges.size();
+        *out_slots = p.slots;
+        return FSGPU_OK;
+    });
+}
+
+fsgpu_status fsgpu_lab_ivf_filter_scan_plan(uint32_t nlist, const uint64_t* offsets, const uint32_t* members, const uint32_t* counts,
+                                            const uint32_t* flags, uint32_t k, uint32_t num_cus, uint32_t groups_cap, uint64_t* out_groups,
+                                            uint32_t* out_ngroups, uint32_t* out_grid_x, uint64_t* out_rows_rescored) {
+    if (!offsets || !members || !counts || !flags || !out_groups || !out_ngroups || !out_grid_x || !out_rows_rescored)
+        return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");
+    if (k < 1) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter plan: k is 0");
+    return guarded([&]() -> fsgpu_status {
+        const std::vector<uint32_t> head = lab_filter_head(nlist, members);
+        const fsgpu::ivf_filter::ScanPlan p =
+            fsgpu::ivf_filter::scan_plan(nlist, offsets, head.data(), counts, flags, k, num_cus, fsgpu::kGatherTileRows, lab_filter_caps(0));
+        if (p.groups.size() > groups_cap) return fail(FSGPU_ERR_INVALID_CONFIG, "ivf filter plan: an output capacity is too small");
+        for (size_t g = 0; g < p.groups.size(); ++g) {
+            const fsgpu::ivf_filter::Group& x = p.groups[g];
+            const uint64_t row[6] = {x.rows_off, x.from_cand, x.n, x.q0, x.nq, x.nblocks};
+            std::memcpy(out_groups + g * 6, row, sizeof(row));
+        }
+        *out_ngroups = (uint32_t)p.groups.size();
+        *out_grid_x = p.grid_x;
+        *out_rows_rescored = p.rows_rescored;
+        return FSGPU_OK;
+    });
+}
+
 fsgpu_status fsgpu_lab_hash_embed_stage_ms(fsgpu_hash* h, const uint8_t* text_bytes, const uint32_t* offsets, uint32_t n, float* out,
                                            float* out_stage_ms) {
     if (!h || !out_stage_ms) return fail(FSGPU_ERR_NULL_ARGUMENT, "null argument");

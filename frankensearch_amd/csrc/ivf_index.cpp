@@ -13,6 +13,9 @@
 // the slots of its pairs; (3) ONE launch of the segmented gather scan and merge_topk over its blocks' lists; (4) the per-query
 // merge; (5) one copy of counts and hits into a pinned block.  Only when some count is below k is the live count taken and the
 // fallback considered.
+// THE LIST FILTER (opt-in) sits between (2) and (3): the probed lists are scored on the int8 matrix cores from the
+// handle's cluster-ordered copy, a selection keeps per slot the rows that can still reach its exact top k, and a second plan
+// (ivf_filter_plan.hpp) hands (3) the candidates in the place of the lists.  (3), (4) and (5) run as they are.
 #include "ivf_index.hpp"
 
 #include <algorithm>
@@ -66,12 +69,30 @@ SearchError VectorIndex::ivf_view(IvfSlabView* out) const {
     return ok();
 }
 
+SearchError VectorIndex::ivf_filter_copy(FilterCopyView* out) {
+    if (!dense_rows() || nrows_ == 0 || nrows_ > 0xffffffffull)
+        return make_error(FSGPU_ERR_INVALID_CONFIG, "the int8 filter serves dense, non-empty slabs only");
+    FSGPU_HIP(hipSetDevice(device_));
+    FSGPU_TRY(ensure_filter_copy(stream_, true));
+    if (!filter_ready()) return make_error(FSGPU_ERR_DEVICE, "no room for the int8 copy of the slab");
+    out->slab_i8 = static_cast<const signed char*>(filter_slab());
+    out->max_bits = filter_max();
+    out->stats = filter_stats();
+    out->rotated = i8f_rot_;
+    out->rot_mat = i8f_rot_ ? static_cast<const double*>(rot_mat_.ptr) : nullptr;
+    out->extra_coeff = i8f_rot_ ? rot_extra_coeff_ : 0.0;
+    return ok();
+}
+
 // ---- the handle ------------------------------------------------------------------------------------------------------------------------
 
 IvfIndex::~IvfIndex() {
     if (device_ >= 0) (void)hipSetDevice(device_);
     if (ev_begin_) (void)hipEventDestroy(ev_begin_);
     if (ev_end_) (void)hipEventDestroy(ev_end_);
+    for (hipEvent_t e : fev_)
+        if (e) (void)hipEventDestroy(e);
+    for (DeviceBuffer* b : {&ordered_, &filter_words_, &filter_rot_mat_, &fq_, &fscratch_, &fslot_, &fplan_}) b->release();
     if (pin_) (void)hipHostFree(pin_);
     centroids_.release();
     offsets_.release();
@@ -302,8 +323,100 @@ SearchError IvfIndex::lists(uint64_t* out_offsets, uint32_t* out_rows) {
     return ok();
 }
 
+// ---- the int8 list filter ---------------------------------------------------------------------------------------------------
+//
+// The handle's copy: ordered[p] = filter_i8[list_rows[p]] list by list, a list's first row on a multiple of 16 rows, rows 64-byte
+// pitched, everything else zero; beside it the scale word and the four statistics words the index's copy was built with and, for a
+// rotated copy, the rotation and what it adds to the bound.  A query is prepared by the index's own kernel against exactly those.
+
+SearchError IvfIndex::set_list_filter(uint32_t mode) {
+    if (mode != FSGPU_IVF_LIST_FILTER_OFF && mode != FSGPU_IVF_LIST_FILTER_INT8)
+        return make_error(FSGPU_ERR_INVALID_CONFIG, "unknown list filter mode " + std::to_string(mode));
+    FSGPU_TRY(check_handle());
+    if (mode == FSGPU_IVF_LIST_FILTER_OFF || filter_built_) {
+        filter_mode_ = mode;
+        return ok();
+    }
+    VectorIndex::FilterCopyView fv;
+    FSGPU_TRY(index_->ivf_filter_copy(&fv));
+    FSGPU_HIP(hipSetDevice(device_));
+    hipStream_t stream = index_->stream();
+    for (hipEvent_t& e : fev_)
+        if (!e) FSGPU_HIP(hipEventCreate(&e));
+    const uint32_t pitch = (dim_ + kIvfFilterPitchAlign - 1) / kIvfFilterPitchAlign * kIvfFilterPitchAlign;
+    uint64_t rows = 0;
+    pad_row0_host_ = ivf_filter::pad_rows(nlist_, offsets_host_.data(), kIvfFilterRowTile, &rows);
+    const size_t copy_bytes = (size_t)rows * pitch, o_pad = align256(copy_bytes);
+    FSGPU_TRY(ordered_.reserve(o_pad + (size_t)nlist_ * 8));   // the copy | the lists' first rows
+    FSGPU_TRY(filter_words_.reserve(32));
+    u64* pad_dev = reinterpret_cast<u64*>(static_cast<unsigned char*>(ordered_.ptr) + o_pad);
+    FSGPU_HIP(hipEventRecord(fev_[0], stream));
+    if (copy_bytes) FSGPU_HIP(hipMemsetAsync(ordered_.ptr, 0, copy_bytes, stream));
+    FSGPU_HIP(hipMemcpyAsync(pad_dev, pad_row0_host_.data(), (size_t)nlist_ * 8, hipMemcpyHostToDevice, stream));
+    FSGPU_HIP(launch_ivf_filter_gather(fv.slab_i8, dim_, static_cast<const uint32_t*>(list_rows_.ptr), static_cast<const u64*>(offsets_.ptr), pad_dev,
+                                       nlist_, offsets_host_[nlist_], pitch, static_cast<signed char*>(ordered_.ptr), stream));
+    FSGPU_HIP(hipMemcpyAsync(filter_words_.ptr, fv.max_bits, 4, hipMemcpyDeviceToDevice, stream));
+    FSGPU_HIP(hipMemcpyAsync(static_cast<unsigned char*>(filter_words_.ptr) + 16, fv.stats, 16, hipMemcpyDeviceToDevice, stream));
+    if (fv.rotated) {
+        FSGPU_TRY(filter_rot_mat_.reserve((size_t)dim_ * dim_ * 8));
+        FSGPU_HIP(hipMemcpyAsync(filter_rot_mat_.ptr, fv.rot_mat, (size_t)dim_ * dim_ * 8, hipMemcpyDeviceToDevice, stream));
+    }
+    FSGPU_HIP(hipEventRecord(fev_[1], stream));
+    FSGPU_HIP(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    FSGPU_HIP(hipEventElapsedTime(&ms, fev_[0], fev_[1]));
+    filter_build_ms_ = ms;
+    filter_rot_ = fv.rotated;
+    filter_extra_coeff_ = fv.extra_coeff;
+    filter_pitch_ = pitch;
+    filter_rows_ = rows;
+    filter_built_ = true;
+    filter_mode_ = mode;
+    return ok();
+}
+
+SearchError IvfIndex::filter_ordered_copy(signed char* out) {
+    FSGPU_TRY(check_handle());
+    if (!filter_built_) return make_error(FSGPU_ERR_INVALID_CONFIG, "the handle has no ordered copy: the list filter was never enabled");
+    FSGPU_HIP(hipSetDevice(device_));
+    std::vector<signed char> phys((size_t)filter_rows_ * filter_pitch_);
+    if (!phys.empty()) FSGPU_HIP(hipMemcpy(phys.data(), ordered_.ptr, phys.size(), hipMemcpyDeviceToHost));
+    for (uint32_t l = 0; l < nlist_; ++l)
+        for (uint64_t i = 0, len = offsets_host_[l + 1] - offsets_host_[l]; i < len; ++i)
+            std::memcpy(out + (size_t)(offsets_host_[l] + i) * dim_, phys.data() + (size_t)(pad_row0_host_[l] + i) * filter_pitch_, dim_);
+    return ok();
+}
+
+// codes [nq, dim] | delta [nq] (| the rotated queries) into fq_
+SearchError IvfIndex::prepare_filter_queries(const float* q_dev, uint32_t nq, hipStream_t stream) {
+    const size_t o_delta = align256((size_t)nq * dim_), o_rq = align256(o_delta + (size_t)nq * 4);
+    FSGPU_TRY(fq_.reserve(o_rq + (filter_rot_ ? (size_t)nq * dim_ * 4 : 0)));
+    unsigned char* base = static_cast<unsigned char*>(fq_.ptr);
+    const unsigned int* words = static_cast<const unsigned int*>(filter_words_.ptr);
+    const float* src = q_dev;
+    if (filter_rot_) {
+        float* rq = reinterpret_cast<float*>(base + o_rq);
+        FSGPU_HIP(launch_rotate_rows_f32(q_dev, nq, dim_, dim_, static_cast<const double*>(filter_rot_mat_.ptr), rq, stream));
+        src = rq;
+    }
+    FSGPU_HIP(launch_prepare_queries_i8_filter(src, nq, nq, dim_, dim_, words, words + 4, base, reinterpret_cast<float*>(base + o_delta), stream,
+                                               nullptr, filter_rot_ ? filter_extra_coeff_ : 0.0));
+    return ok();
+}
+
+void IvfIndex::filter_stats_begin(IvfFilterStats* f) const {
+    *f = IvfFilterStats{};
+    f->mode = filter_mode_;
+    f->rotated = filter_rot_ ? 1u : 0u;
+    f->slot_cap = kIvfFilterSlotCap;
+    f->k_cap = kIvfFilterKCap;
+    f->scratch_cap = scratch_entries_ ? scratch_entries_ : kIvfFilterScratchEntries;
+    f->copy_bytes = filter_built_ ? filter_rows_ * filter_pitch_ : 0;
+    f->build_ms = filter_build_ms_;
+}
+
 SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t* out_rows,
-                             float* out_scores, uint32_t* out_counts, uint32_t* out_flags, bool on_device, IvfStats* stats) {
+                             float* out_scores, uint32_t* out_counts, uint32_t* out_flags, bool on_device, IvfStats* stats, IvfFilterLab* lab) {
     FSGPU_TRY(check_call(k, nprobe));
     const uint32_t dim = dim_;
     if (query_len != dim)
@@ -317,8 +430,16 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
     st.nprobe = nprobe;
     st.k_requested = k;
     st.queries = nq;
+    IvfFilterStats fs;
+    filter_stats_begin(&fs);
+    // the list filter takes the call when it is on and k is within its cap; the queries it cannot certify, the slots that overflow
+    // and a call it does not take are scanned over their whole lists, as with the filter off
+    const bool filt = filter_mode_ == FSGPU_IVF_LIST_FILTER_INT8 && filter_built_ && k <= kIvfFilterKCap;
+    if (filter_mode_ == FSGPU_IVF_LIST_FILTER_INT8 && !filt && nq) fs.calls_above_k_cap = 1;
+    if (lab && !filt) return make_error(FSGPU_ERR_INVALID_CONFIG, "the filter stage needs the list filter on and k <= 64");
     auto done = [&]() {
         last_ = st;
+        flast_ = fs;
         if (stats) *stats = st;
         return ok();
     };
@@ -342,7 +463,8 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
     const size_t o_gq = align256(o_plan + plan_bytes), o_slot_lists = align256(o_gq + (size_t)pairs * dim * 4),
                  total = align256(o_slot_lists + (size_t)pairs * k * 8);
     FSGPU_TRY(ws_.reserve(total));
-    const size_t pin_need = std::max(o_q, align256((size_t)pairs * 8));
+    const size_t p_delta = std::max(o_q, align256((size_t)pairs * 8));   // (the filter's bounds come up behind everything else)
+    const size_t pin_need = p_delta + (filt ? align256((size_t)nq * 4) : 0);
     if (pin_bytes_ < pin_need) {
         if (pin_) (void)hipHostFree(pin_);
         pin_ = nullptr;
@@ -358,6 +480,12 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
 
     // (1) the coarse step: dot_product_f32_bytes_f32(centroid row, query), the nprobe best in the total order
     FSGPU_HIP(hipEventRecord(ev_begin_, stream));
+    const float* delta_host = reinterpret_cast<const float*>(pin + p_delta);
+    if (filt) {   // the filter's queries: codes and bounds, the bounds up with the coarse rows
+        FSGPU_TRY(prepare_filter_queries(q_dev, nq, stream));
+        FSGPU_HIP(hipMemcpyAsync(pin + p_delta, static_cast<unsigned char*>(fq_.ptr) + align256((size_t)nq * dim), (size_t)nq * 4,
+                                 hipMemcpyDeviceToHost, stream));
+    }
     const bool coarse_join = nq >= 16 && nprobe <= kKnnMaxM && dim <= kKnnUpdMaxDim;
     std::vector<uint32_t> probed_rows;
     const uint32_t* probed = nullptr;
@@ -450,11 +578,161 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
     }
     FSGPU_HIP(hipMemcpyAsync(base + o_plan, plan_host_.data(), plan_bytes, hipMemcpyHostToDevice, stream));
 
+    // (2f) the list filter: every probed list scored once on the matrix cores for all its member queries, per slot the rows that can
+    // still reach its exact top k, and the SECOND plan: one single-member group per filtered slot over its candidates, today's groups
+    // for the members that overflowed, are not certified or did not fit the scratch
+    if (fs.calls_above_k_cap) fs.rows_rescored = st.rows_scored;   // every exact dot was made
+    if (filt) {
+        uint32_t certified = 0;
+        for (uint32_t q = 0; q < nq; ++q) certified += delta_host[q] >= 0.0f;
+        fs.queries_filtered = certified;
+        fs.queries_uncertified = nq - certified;
+        fs.rows_rescored = st.rows_scored;
+        if (lab) lab->delta.assign(delta_host, delta_host + nq);
+        if (certified && slots) {
+            const ivf_filter::Caps caps{fs.scratch_cap, kIvfFilterTileQueries, kIvfFilterRowTile, kIvfFilterItemRows, kIvfFilterSlotCap};
+            ivf_filter::ScorePlan sp = ivf_filter::score_plan(nlist_, offsets_host_.data(), head.data(), pad_row0_host_.data(), caps);
+            if (sp.slots != slots) return make_error(FSGPU_ERR_DEVICE, "the filter's plan disagrees with the search's about the slots");
+            const uint32_t ntiles = (uint32_t)sp.tiles.size() - 1;
+            if (lab && (sp.ranges.size() != 1 || sp.ranges[0].ntiles != ntiles))
+                return make_error(FSGPU_ERR_INVALID_CONFIG, "the filter stage needs a call whose scores fit the scratch at once");
+            // device: tiles | slot -> tile, and per slot t | m | count | flag | candidates
+            const size_t f_slot_tile = align256(sp.tiles.size() * sizeof(IvfFilterTile));
+            FSGPU_TRY(fplan_.reserve(f_slot_tile + (size_t)slots * 4));
+            unsigned char* fp = static_cast<unsigned char*>(fplan_.ptr);
+            FSGPU_HIP(hipMemcpyAsync(fp, sp.tiles.data(), sp.tiles.size() * sizeof(IvfFilterTile), hipMemcpyHostToDevice, stream));
+            FSGPU_HIP(hipMemcpyAsync(fp + f_slot_tile, sp.slot_tile.data(), (size_t)slots * 4, hipMemcpyHostToDevice, stream));
+            uint64_t entries = 0;
+            for (const ivf_filter::Range& r : sp.ranges) entries = std::max(entries, r.entries);
+            const size_t s_m = align256((size_t)slots * 4), s_count = align256(s_m + (size_t)slots * 8), s_cand = align256(s_count + (size_t)slots * 8);
+            int32_t* scores_dev = nullptr;
+            int32_t* t_dev = nullptr;
+            long long* m_dev = nullptr;
+            uint32_t *count_dev = nullptr, *flag_dev = nullptr, *cand_dev = nullptr;
+            if (lab) {
+                scores_dev = static_cast<int32_t*>(lab->alloc(IvfFilterLab::kScores, (size_t)entries * 4));
+                t_dev = static_cast<int32_t*>(lab->alloc(IvfFilterLab::kT, (size_t)slots * 4));
+                m_dev = static_cast<long long*>(lab->alloc(IvfFilterLab::kM, (size_t)slots * 8));
+                count_dev = static_cast<uint32_t*>(lab->alloc(IvfFilterLab::kCount, (size_t)slots * 4));
+                flag_dev = static_cast<uint32_t*>(lab->alloc(IvfFilterLab::kFlag, (size_t)slots * 4));
+                cand_dev = static_cast<uint32_t*>(lab->alloc(IvfFilterLab::kCand, (size_t)slots * kIvfFilterSlotCap * 4));
+                if (!scores_dev || !t_dev || !m_dev || !count_dev || !flag_dev || !cand_dev)
+                    return make_error(FSGPU_ERR_DEVICE, "the filter stage's outputs could not be allocated");
+            } else {
+                FSGPU_TRY(fscratch_.reserve(std::max<size_t>((size_t)entries * 4, 256)));
+                FSGPU_TRY(fslot_.reserve(s_cand + (size_t)slots * kIvfFilterSlotCap * 4));
+                unsigned char* sb = static_cast<unsigned char*>(fslot_.ptr);
+                scores_dev = static_cast<int32_t*>(fscratch_.ptr);
+                t_dev = reinterpret_cast<int32_t*>(sb);
+                m_dev = reinterpret_cast<long long*>(sb + s_m);
+                count_dev = reinterpret_cast<uint32_t*>(sb + s_count);   // counts | flags: one copy brings both up
+                flag_dev = count_dev + slots;
+                cand_dev = reinterpret_cast<uint32_t*>(sb + s_cand);
+            }
+            // a slot of a tile above the scratch is in no range: nothing writes its count and flag but this
+            FSGPU_HIP(hipMemsetAsync(count_dev, 0, (size_t)slots * 4, stream));
+            FSGPU_HIP(hipMemsetAsync(flag_dev, 0, (size_t)slots * 4, stream));
+            IvfFilterScoreArgs sa{};
+            sa.ordered = static_cast<const signed char*>(ordered_.ptr);
+            sa.pitch = filter_pitch_;
+            sa.codes = static_cast<const signed char*>(fq_.ptr);
+            sa.dim = dim;
+            sa.slot_query = reinterpret_cast<const uint32_t*>(base + o_plan);
+            sa.list_rows = list_rows;
+            sa.live = v.live;   // as it is NOW
+            sa.tiles = reinterpret_cast<const IvfFilterTile*>(fp);
+            sa.scores = scores_dev;
+            IvfFilterSelectArgs se{};
+            se.scores = scores_dev;
+            se.tiles = sa.tiles;
+            se.slot_tile = reinterpret_cast<const uint32_t*>(fp + f_slot_tile);
+            se.slot_query = sa.slot_query;
+            se.delta = reinterpret_cast<const float*>(static_cast<unsigned char*>(fq_.ptr) + align256((size_t)nq * dim));
+            se.list_rows = list_rows;
+            se.k = k;
+            se.out_t = t_dev;
+            se.out_m = m_dev;
+            se.out_count = count_dev;
+            se.out_flag = flag_dev;
+            se.cand = cand_dev;
+            for (const ivf_filter::Range& r : sp.ranges) {
+                sa.tile_first = r.tile_first;
+                sa.ntiles = r.ntiles;
+                sa.item_first = r.item_first;
+                se.slot_first = r.slot_first;
+                FSGPU_HIP(hipEventRecord(fev_[0], stream));
+                FSGPU_HIP(launch_ivf_filter_score(sa, r.nitems, stream));
+                FSGPU_HIP(hipEventRecord(fev_[1], stream));
+                FSGPU_HIP(launch_ivf_filter_select(se, r.nslots, stream));
+                FSGPU_HIP(hipEventRecord(fev_[2], stream));
+                FSGPU_HIP(hipEventSynchronize(fev_[2]));   // (the next range reuses the scratch and the events)
+                float ms_score = 0.0f, ms_select = 0.0f;
+                FSGPU_HIP(hipEventElapsedTime(&ms_score, fev_[0], fev_[1]));
+                FSGPU_HIP(hipEventElapsedTime(&ms_select, fev_[1], fev_[2]));
+                fs.filter_ms += ms_score;
+                fs.select_ms += ms_select;
+                st.launches += 2;
+                for (uint32_t t = r.tile_first; t < r.tile_first + r.ntiles; ++t) fs.rows_streamed += sp.tiles[t].len;
+            }
+            fs.scratch_ranges = sp.ranges.size();
+            uint32_t* cf = reinterpret_cast<uint32_t*>(pin);   // (2 x slots words <= pairs x 8 bytes; the coarse rows are done with)
+            if (lab) {
+                FSGPU_HIP(hipMemcpyAsync(cf, count_dev, (size_t)slots * 4, hipMemcpyDeviceToHost, stream));
+                FSGPU_HIP(hipMemcpyAsync(cf + slots, flag_dev, (size_t)slots * 4, hipMemcpyDeviceToHost, stream));
+            } else {
+                FSGPU_HIP(hipMemcpyAsync(cf, count_dev, (size_t)slots * 8, hipMemcpyDeviceToHost, stream));
+            }
+            FSGPU_HIP(hipStreamSynchronize(stream));
+            std::vector<uint32_t> counts2(cf, cf + slots), flags2(cf + slots, cf + 2 * (size_t)slots);
+            for (uint32_t t = 0; t < ntiles; ++t)
+                if (sp.above[t])
+                    for (uint32_t j = 0; j < sp.tiles[t].nmem; ++j) flags2[sp.tiles[t].slot0 + j] = kIvfFilterFlagAboveScratch;
+            for (uint32_t s = 0; s < slots; ++s) {
+                if (flags2[s] & kIvfFilterFlagAboveScratch) {
+                    fs.slots_above_scratch += delta_host[slot_query[s]] >= 0.0f;
+                    continue;
+                }
+                if (flags2[s] & kIvfFilterFlagUncertified) continue;
+                fs.slots_filtered += 1;
+                fs.slots_overflowed += (flags2[s] & kIvfFilterFlagOverflow) != 0;
+                fs.rows_filtered += sp.tiles[sp.slot_tile[s]].len;
+            }
+            const ivf_filter::ScanPlan scan = ivf_filter::scan_plan(nlist_, offsets_host_.data(), head.data(), counts2.data(), flags2.data(), k,
+                                                                    (uint32_t)v.num_cus, kGatherTileRows, caps);
+            fs.rows_rescored = scan.rows_rescored;
+            ngroups = (uint32_t)scan.groups.size();
+            grid_x = scan.grid_x;
+            for (uint32_t i = 0; i < ngroups; ++i) {   // (the first plan's image has been uploaded: the stream was synchronised above)
+                const ivf_filter::Group& sg = scan.groups[i];
+                FilterGatherGroup& gd = groups[i];
+                gd.rows = (sg.from_cand ? cand_dev : list_rows) + sg.rows_off;
+                gd.n = sg.n;
+                gd.q0 = sg.q0;
+                gd.nq = sg.nq;
+                gd.nblocks = sg.nblocks;
+            }
+            FSGPU_HIP(hipMemcpyAsync(base + o_plan + p_groups, plan_host_.data() + p_groups, (size_t)ngroups * sizeof(FilterGatherGroup),
+                                     hipMemcpyHostToDevice, stream));
+            if (lab) {
+                lab->tiles = sp.tiles;
+                lab->slot_tile = sp.slot_tile;
+                lab->slot_query.assign(slot_query, slot_query + slots);
+                lab->slot_list.resize(slots);
+                for (uint32_t l = 0, s = 0; l < nlist_; ++l)
+                    if (offsets_host_[l + 1] > offsets_host_[l])
+                        for (uint32_t i = head[l]; i < head[l + 1]; ++i) lab->slot_list[s++] = l;
+                lab->entries = entries;
+                lab->ran = true;
+            }
+        }
+    }
+
     // (3) the probed lists: one segmented gather scan, its blocks' lists merged per slot
     const uint32_t list_stride = k <= 64 ? 64 : k;
     IvfMergeArgs m{};
     m.slot_lists = reinterpret_cast<const u64*>(base + o_slot_lists);
     m.slot_stride = k;
+    if (filt) FSGPU_HIP(hipEventRecord(fev_[0], stream));   // rescore_ms: the exact scan and its merge
     if (slots) {
         FSGPU_TRY(ws_lists_.reserve((size_t)slots * grid_x * list_stride * 8));
         float* gq = reinterpret_cast<float*>(base + o_gq);
@@ -497,6 +775,7 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
             FSGPU_HIP(launch_merge_topk(mm, (int)slots, stream));
         }
     }
+    if (filt) FSGPU_HIP(hipEventRecord(fev_[1], stream));
     // (4) the per-query merge
     m.qslots = reinterpret_cast<const uint32_t*>(base + o_plan + p_qslots);
     m.nprobe = nprobe;
@@ -516,6 +795,10 @@ SearchError IvfIndex::search(const float* queries, uint32_t nq, uint32_t query_l
     float ms = 0.0f;
     FSGPU_HIP(hipEventElapsedTime(&ms, ev_begin_, ev_end_));
     st.device_ms = ms;
+    if (filt) {
+        FSGPU_HIP(hipEventElapsedTime(&ms, fev_[0], fev_[1]));
+        fs.rescore_ms = ms;
+    }
 
     // the fallback (hnsw.rs:1150-1190): count < min(k, live rows) -> the exact search answers
     std::vector<uint32_t> under;
@@ -579,6 +862,8 @@ SearchError IvfIndex::certify_nprobe(const float* queries, uint32_t nq, const ui
     std::vector<float> escores((size_t)nq * k), ascores((size_t)nq * k);
     if (nq) FSGPU_TRY(index_->search_top_k_batched(queries, nq, dim, k, nullptr, erows.data(), escores.data(), ecounts.data(), nullptr));
     IvfStats sum;
+    IvfFilterStats fsum;
+    filter_stats_begin(&fsum);
     std::vector<double> recalls(nq);
     bool have_best = false;
     CertifiedEf best;
@@ -599,6 +884,19 @@ SearchError IvfIndex::certify_nprobe(const float* queries, uint32_t nq, const ui
         sum.lists_probed += st.lists_probed;
         sum.rows_scored += st.rows_scored;
         sum.device_ms += st.device_ms;
+        fsum.queries_filtered += flast_.queries_filtered;
+        fsum.queries_uncertified += flast_.queries_uncertified;
+        fsum.calls_above_k_cap += flast_.calls_above_k_cap;
+        fsum.slots_filtered += flast_.slots_filtered;
+        fsum.slots_overflowed += flast_.slots_overflowed;
+        fsum.slots_above_scratch += flast_.slots_above_scratch;
+        fsum.scratch_ranges += flast_.scratch_ranges;
+        fsum.rows_filtered += flast_.rows_filtered;
+        fsum.rows_rescored += flast_.rows_rescored;
+        fsum.rows_streamed += flast_.rows_streamed;
+        fsum.filter_ms += flast_.filter_ms;
+        fsum.select_ms += flast_.select_ms;
+        fsum.rescore_ms += flast_.rescore_ms;
         for (uint32_t q = 0; q < nq; ++q)
             recalls[q] = aflags[q] ? 0.0
                                    : recall_at_k_of_rows(arows.data() + (size_t)q * k, acounts[q], erows.data() + (size_t)q * k, ecounts[q]);
@@ -618,6 +916,7 @@ SearchError IvfIndex::certify_nprobe(const float* queries, uint32_t nq, const ui
         }
     }
     last_ = sum;
+    flast_ = fsum;
     *chosen = best;
     *n_swept = swept;
     return ok();

@@ -5,9 +5,11 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "ann_index.hpp"
+#include "ivf_filter_plan.hpp"
 #include "vector_index.hpp"
 
 namespace fsgpu {
@@ -30,6 +32,27 @@ struct IvfStats {   // field for field fsgpu_ivf_stats
     double device_ms = 0.0;
 };
 
+struct IvfFilterStats {   // field for field fsgpu_ivf_filter_stats
+    uint32_t mode = 0, rotated = 0, slot_cap = 0, k_cap = 0;
+    uint64_t scratch_cap = 0, copy_bytes = 0;
+    double build_ms = 0.0;
+    uint64_t queries_filtered = 0, queries_uncertified = 0, calls_above_k_cap = 0, slots_filtered = 0, slots_overflowed = 0,
+             slots_above_scratch = 0, scratch_ranges = 0, rows_filtered = 0, rows_rescored = 0, rows_streamed = 0;
+    double filter_ms = 0.0, select_ms = 0.0, rescore_ms = 0.0;
+};
+
+// What fsgpu_lab_ivf_filter_stage asks of a search: the filter's device outputs come from `alloc` (guarded buffers of the lab harness)
+// instead of the handle's workspaces, and the host tables of the call are left here.
+struct IvfFilterLab {
+    enum Which { kScores = 0, kT, kM, kCount, kFlag, kCand };
+    std::function<void*(Which, size_t bytes)> alloc;   // null return: the allocation failed (the harness keeps the error)
+    std::vector<IvfFilterTile> tiles;                  // [ntiles + 1]
+    std::vector<uint32_t> slot_query, slot_list, slot_tile;
+    std::vector<float> delta;                          // [nq]
+    uint64_t entries = 0;                              // of the scores
+    bool ran = false;                                  // the filter stage ran (some query was certified, k <= the cap)
+};
+
 class IvfIndex {
   public:
     ~IvfIndex();
@@ -48,7 +71,20 @@ class IvfIndex {
     SearchError lists(uint64_t* out_offsets, uint32_t* out_rows);   // host [nlist + 1], [out_offsets[nlist]] local rows
     // on_device: queries and the four outputs are device pointers (out_flags may be null either way).  Blocks.
     SearchError search(const float* queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t* out_rows, float* out_scores,
-                       uint32_t* out_counts, uint32_t* out_flags, bool on_device, IvfStats* stats);
+                       uint32_t* out_counts, uint32_t* out_flags, bool on_device, IvfStats* stats, IvfFilterLab* lab = nullptr);
+    // The int8 list filter.  mode 1 builds the handle's cluster-ordered int8 copy on first use (blocks; builds the
+    // index's filter copy if need be); an unknown mode is refused before anything is built.
+    SearchError set_list_filter(uint32_t mode);
+    uint32_t list_filter() const { return filter_mode_; }
+    IvfFilterStats last_filter_stats() const {   // the last call's figures beside the handle's mode, copy and caps as they stand
+        IvfFilterStats now, f = flast_;
+        filter_stats_begin(&now);
+        f.mode = now.mode, f.rotated = now.rotated, f.slot_cap = now.slot_cap, f.k_cap = now.k_cap, f.scratch_cap = now.scratch_cap;
+        f.copy_bytes = now.copy_bytes, f.build_ms = now.build_ms;
+        return f;
+    }
+    SearchError filter_ordered_copy(signed char* out);          // host [offsets[nlist], dim]: the logical ordered copy
+    void set_filter_scratch_entries(uint64_t entries) { scratch_entries_ = entries; }   // (lab) 0: the default
     // sweep holds n_probes entries; CertifiedEf::ef_search carries nprobe
     SearchError certify_nprobe(const float* queries, uint32_t nq, const uint32_t* candidates, uint32_t n_candidates, uint32_t k, double target,
                                double alpha, CertifiedEf* chosen, CertifiedEf* sweep, uint32_t* n_swept);
@@ -74,6 +110,19 @@ class IvfIndex {
     size_t pin_bytes_ = 0;
     hipEvent_t ev_begin_ = nullptr, ev_end_ = nullptr;
     IvfStats last_;
+    // the int8 list filter: the ordered copy and what it was built from — never the index's own buffers, which the index may rebuild
+    // (adopt_global_quant_max) or drop without a generation change of its own making
+    SearchError prepare_filter_queries(const float* q_dev, uint32_t nq, hipStream_t stream);
+    void filter_stats_begin(IvfFilterStats* f) const;
+    uint32_t filter_mode_ = 0;
+    bool filter_built_ = false, filter_rot_ = false;
+    double filter_extra_coeff_ = 0.0, filter_build_ms_ = 0.0;
+    uint32_t filter_pitch_ = 0;
+    uint64_t filter_rows_ = 0, scratch_entries_ = 0;
+    std::vector<uint64_t> pad_row0_host_;   // [nlist]
+    DeviceBuffer ordered_, filter_words_ /* scale word | statistics */, filter_rot_mat_, fq_, fscratch_, fslot_, fplan_;
+    hipEvent_t fev_[3] = {nullptr, nullptr, nullptr};
+    IvfFilterStats flast_;
 };
 
 }  // namespace fsgpu

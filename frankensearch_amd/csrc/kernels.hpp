@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ivf_filter_tile.hpp"
+
 namespace fsgpu {
 
 typedef unsigned long long u64;
@@ -834,5 +836,57 @@ struct IvfMergeArgs {
     uint32_t* out_counts;        // [nq]
 };
 hipError_t launch_ivf_merge(const IvfMergeArgs& args, uint32_t nq, hipStream_t stream);
+
+// ivf_filter_kernels.hip: the int8 matrix-core list filter (ivf_index.cpp; ivf_filter_plan.hpp).  The caps of the filter
+// (mirrored in tests/ivf_filter_cases.py, reported by fsgpu_ivf_filter_stats):
+constexpr uint32_t kIvfFilterKCap = 64;          // k above it: the whole call takes the unfiltered path
+constexpr uint32_t kIvfFilterSlotCap = 128;      // candidates a slot may keep; more: the slot overflows and is scanned whole
+constexpr uint64_t kIvfFilterScratchEntries = 1ull << 26;   // int32 scores resident at once (256 MB); a call above it runs in ranges of tiles
+constexpr uint32_t kIvfFilterTileQueries = 16;   // member queries of a list per work item: one MFMA column tile
+constexpr uint32_t kIvfFilterRowTile = 16;       // list starts of the ordered copy are aligned to it: one MFMA row tile
+constexpr uint32_t kIvfFilterItemRows = 512;     // rows a workgroup scores for its tile: 8 row tiles per wave
+constexpr uint32_t kIvfFilterPitchAlign = 64;    // row pitch of the ordered copy: one MFMA k-step, zero padded
+constexpr int32_t kIvfFilterDead = INT32_MIN;    // the integer score of a dead row and of the padding rows: below every real score
+constexpr uint32_t kIvfFilterFlagOverflow = 1, kIvfFilterFlagUncertified = 2, kIvfFilterFlagAboveScratch = 4;
+// ordered[list start of l, padded to kIvfFilterRowTile rows, + i][0 .. dim) = filter_i8[list_rows[offsets[l] + i]][0 .. dim); the
+// bytes dim .. pitch of a row and the padding rows are zero.  pad_row0: [nlist] the first ordered row of each list.
+hipError_t launch_ivf_filter_gather(const signed char* filter_i8, uint32_t dim, const uint32_t* list_rows, const u64* offsets, const u64* pad_row0,
+                                    uint32_t nlist, uint64_t total, uint32_t pitch, signed char* ordered, hipStream_t stream);
+// A tile: up to kIvfFilterTileQueries consecutive slots of one list.  Slot slot0 + j keeps s[i], i < len_pad = len rounded up to
+// kIvfFilterRowTile, at scores + scratch0 + j * len_pad: the int32 dot of the query's codes with row i's, kIvfFilterDead for a dead row
+// and for i >= len.  Workgroup w of the launch serves the tile t with item0[t] <= item_first + w < item0[t + 1], rows from
+// (item_first + w - item0[t]) * kIvfFilterItemRows on.  (IvfFilterTile: ivf_filter_tile.hpp, which the host plan shares.)
+struct IvfFilterScoreArgs {
+    const signed char* ordered;
+    uint32_t pitch;                 // bytes, a multiple of kIvfFilterPitchAlign
+    const signed char* codes;       // [nq, dim] the queries' int8 codes
+    uint32_t dim;
+    const uint32_t* slot_query;     // [slots]
+    const uint32_t* list_rows;
+    const u64* live;                // as it is now; nullptr = all live
+    const IvfFilterTile* tiles;     // [ntiles + 1]: the last entry carries the end of the items
+    uint32_t tile_first, ntiles, item_first;   // this launch's tiles and the first item among them
+    int32_t* scores;
+};
+hipError_t launch_ivf_filter_score(const IvfFilterScoreArgs& args, uint32_t nitems, hipStream_t stream);
+// One workgroup per slot: the k-th largest score t with multiplicity (kIvfFilterDead when no more than k rows are live), the margin
+// m = ceil(2 delta) of the slot's query, and the list_rows entries of the live rows with s >= t - m (every live row when no more than
+// k are), ascending, the first kIvfFilterSlotCap of them at cand + slot * kIvfFilterSlotCap; count is never clipped.
+// flag: kIvfFilterFlagOverflow | kIvfFilterFlagUncertified (delta < 0: nothing else is written for the slot but count 0).
+struct IvfFilterSelectArgs {
+    const int32_t* scores;
+    const IvfFilterTile* tiles;
+    const uint32_t* slot_tile;      // [slots] the tile of a slot
+    const uint32_t* slot_query;
+    const float* delta;             // [nq]
+    const uint32_t* list_rows;
+    uint32_t slot_first, k;
+    int32_t* out_t;                 // [slots]
+    long long* out_m;               // [slots]
+    uint32_t* out_count;            // [slots]
+    uint32_t* out_flag;             // [slots]
+    uint32_t* cand;                 // [slots, kIvfFilterSlotCap]
+};
+hipError_t launch_ivf_filter_select(const IvfFilterSelectArgs& args, uint32_t nslots, hipStream_t stream);
 
 }  // namespace fsgpu

@@ -322,6 +322,17 @@ class VectorIndex {
         int num_cus = 0;
     };
     SearchError ivf_view(IvfSlabView* out) const;
+    // The int8 filter's copy as the batched search uses it (built now if need be; no room for it is an error), for a handle that
+    // makes a copy of its own: the pointers are good until the index rebuilds or drops its copy.
+    struct FilterCopyView {
+        const signed char* slab_i8 = nullptr;       // [nrows, dim]
+        const unsigned int* max_bits = nullptr;     // the scale word
+        const unsigned int* stats = nullptr;        // four words
+        bool rotated = false;
+        const double* rot_mat = nullptr;            // [dim, dim] when rotated
+        double extra_coeff = 0.0;
+    };
+    SearchError ivf_filter_copy(FilterCopyView* out);
 
     // VectorIndex::append_batch (lib.rs:2546-2720): every entry validated before anything changes, last-wins dedup inside the batch,
     // resident copies superseded, the first live main row of each doc id tombstoned, ONE live-bitmap upload.  wal_append is a batch of one.

@@ -633,12 +633,15 @@ class VectorIndex:
             table = self.optimize_knn_graph(table, optimize)
         return AnnIndex(self, table, AnnConfig(**config))
 
-    def build_ivf(self, nlist: int, iters: int = 8, n_train: int = 0, init_centroids=None):
+    def build_ivf(self, nlist: int, iters: int = 8, n_train: int = 0, init_centroids=None, list_filter: bool = False):
         """fsgpu_ivf_create: an IvfIndex over this index's rows (ivf.py) — spherical k-means with `nlist` centroids trained on the
         device (iters Lloyd iterations over a strided sample of n_train rows, 0 = every live row; init_centroids [nlist, dim] or the
-        strided rows), and the inverted lists of all live rows."""
+        strided rows), and the inverted lists of all live rows.  list_filter: the int8 list filter is switched on (IvfIndex.set_list_filter)."""
         from .ivf import IvfConfig, IvfIndex
-        return IvfIndex(self, nlist, IvfConfig(iters=iters, n_train=n_train), init_centroids)
+        ivf = IvfIndex(self, nlist, IvfConfig(iters=iters, n_train=n_train), init_centroids)
+        if list_filter:
+            ivf.set_list_filter(True)
+        return ivf
 
     def mmr_rerank(self, rows: Sequence[int], scores: Sequence[float], k: int, config=None, want_sims: bool = False):
         """fsgpu_index_mmr_rerank: mmr_rerank (mmr.rs:103-251) over rows of this index, on its device.  Returns the selected indexes

@@ -3,6 +3,7 @@
   IvfIndex(index, nlist, config, init_centroids)   fsgpu_ivf_create: spherical Lloyd k-means on the device, then the lists
   IvfIndex.search_batched / search                 the nprobe nearest lists scored exactly, with the underfill fallback
   IvfIndex.certify_nprobe                          fsgpu_ann_certify_ef with nprobe candidates
+  IvfIndex.set_list_filter / filter_stats          the opt-in int8 matrix-core list filter: the same answers from fewer exact dots
   IvfIndex.centroids / lists                       the index itself: with iters 0 and 1 the assignment and the update alone
 The index and every answer are pure functions of their inputs (include/fsgpu.h, "IVF index"); only recall is statistical, and it is
 certified.  VectorIndex.build_ivf builds one."""
@@ -34,6 +35,15 @@ class _IvfStats(C.Structure):
                 ("k_requested", C.c_uint32), ("launches", C.c_uint32), ("reserved0", C.c_uint32), ("queries", C.c_uint64),
                 ("approximate", C.c_uint64), ("underfilled", C.c_uint64), ("empty_despite_indexed_points", C.c_uint64),
                 ("lists_probed", C.c_uint64), ("rows_scored", C.c_uint64), ("device_ms", C.c_double)]
+
+
+class _IvfFilterStats(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("rotated", C.c_uint32), ("slot_cap", C.c_uint32), ("k_cap", C.c_uint32), ("scratch_cap", C.c_uint64),
+                ("copy_bytes", C.c_uint64), ("build_ms", C.c_double), ("queries_filtered", C.c_uint64), ("queries_uncertified", C.c_uint64),
+                ("calls_above_k_cap", C.c_uint64), ("slots_filtered", C.c_uint64), ("slots_overflowed", C.c_uint64),
+                ("slots_above_scratch", C.c_uint64), ("scratch_ranges", C.c_uint64), ("rows_filtered", C.c_uint64),
+                ("rows_rescored", C.c_uint64), ("filter_ms", C.c_double), ("select_ms", C.c_double), ("rescore_ms", C.c_double),
+                ("rows_streamed", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 @dataclass
@@ -73,6 +83,34 @@ class IvfStats:
     lists_probed: int = 0
     rows_scored: int = 0
     device_ms: float = 0.0
+
+
+@dataclass
+class IvfFilterStats:
+    """fsgpu_ivf_filter_stats: of the last search or certify call."""
+    mode: int = 0
+    rotated: int = 0
+    slot_cap: int = 0
+    k_cap: int = 0
+    scratch_cap: int = 0
+    copy_bytes: int = 0
+    build_ms: float = 0.0
+    queries_filtered: int = 0
+    queries_uncertified: int = 0
+    calls_above_k_cap: int = 0
+    slots_filtered: int = 0
+    slots_overflowed: int = 0
+    slots_above_scratch: int = 0
+    scratch_ranges: int = 0
+    rows_filtered: int = 0
+    rows_rescored: int = 0
+    filter_ms: float = 0.0
+    select_ms: float = 0.0
+    rescore_ms: float = 0.0
+    rows_streamed: int = 0
+
+
+LIST_FILTER_OFF, LIST_FILTER_INT8 = 0, 1
 
 
 def _fields(cls, s):
@@ -127,6 +165,21 @@ class IvfIndex:
         s = _IvfBuildInfo()
         check(_lib.lib().fsgpu_ivf_build_stats(self._h, C.byref(s)))
         return _fields(IvfBuildStats, s)
+
+    def set_list_filter(self, on) -> None:
+        """fsgpu_ivf_set_list_filter: the int8 matrix-core list filter (True / LIST_FILTER_INT8) or the plain probed-list scan.  On
+        first use the handle builds its cluster-ordered int8 copy (blocks).  Answers do not change, bit for bit."""
+        mode = (LIST_FILTER_INT8 if on else LIST_FILTER_OFF) if isinstance(on, (bool, np.bool_)) else int(on)
+        check(_lib.lib().fsgpu_ivf_set_list_filter(self._h, min(max(mode, 0), 0xFFFFFFFF)))
+
+    @property
+    def list_filter(self) -> bool:
+        return _lib.lib().fsgpu_ivf_list_filter(self._h) != LIST_FILTER_OFF
+
+    def filter_stats(self) -> IvfFilterStats:
+        s = _IvfFilterStats()
+        check(_lib.lib().fsgpu_ivf_last_filter_stats(self._h, C.byref(s)))
+        return _fields(IvfFilterStats, s)
 
     def centroids(self) -> np.ndarray:
         """-> [nlist, dimension] f32, the final centroids."""

@@ -1560,6 +1560,47 @@ fsgpu_status fsgpu_ivf_last_stats(const fsgpu_ivf *ivf, fsgpu_ivf_stats *stats);
 fsgpu_status fsgpu_ivf_certify_nprobe(fsgpu_ivf *ivf, const float *queries, uint32_t nq, const uint32_t *candidate_nprobes,
                                       uint32_t n_probes, uint32_t k, double target, double alpha, fsgpu_certified_ef *chosen,
                                       fsgpu_certified_ef *sweep_out, uint32_t *n_swept);
+/* The int8 list filter (opt-in, default off; off is the path and the stats described above).  On, every probed list is scored once
+ * on the int8 matrix cores for all the queries that probe it, from a copy of the index's int8 filter rows laid out list by list; per
+ * (query, list) slot only the rows that can still reach the slot's exact top k under the proven per-query bound delta of
+ * fsgpu_index_int8_filter_bound are then scored exactly.  EVERY ANSWER IS BIT FOR BIT THE FILTER-OFF ANSWER, and every field of
+ * fsgpu_ivf_stats but launches and device_ms is the filter-off value (rows_scored stays the sum of the list lengths).
+ *   rule      slot (q, c), delta_q >= 0, L = the rows of list c live now, s_r = the int32 dot of q's codes with row r's.  |L| <= k:
+ *             the candidates are L.  Otherwise t = the k-th largest s_r with multiplicity, m = ceil(2 delta_q), and the candidates
+ *             are the rows of L with s_r >= t - m, ascending.  More than slot_cap (128) candidates: the slot overflows and is scored
+ *             over its whole list.  A query with delta_q < 0 (non-finite, zero or overflowing; a slab the bound does not cover) is
+ *             uncertified and takes the filter-off path inside the same call; so does a whole call with k > k_cap (64).
+ *   handle    the cluster-ordered copy, the scale word, the statistics and the rotation it was built from are the handle's own: the
+ *             index may rebuild or drop its filter copy afterwards.  fsgpu_ivf_certify_nprobe and the three searches honour the mode. */
+#define FSGPU_IVF_LIST_FILTER_OFF  0
+#define FSGPU_IVF_LIST_FILTER_INT8 1
+/* INT8: builds the handle's cluster-ordered int8 copy on first use (blocks; builds the index's filter copy if need be).  An unknown
+ * mode is FSGPU_ERR_INVALID_CONFIG: nothing is built, nothing changes. */
+fsgpu_status fsgpu_ivf_set_list_filter(fsgpu_ivf *ivf, uint32_t mode);
+uint32_t fsgpu_ivf_list_filter(const fsgpu_ivf *ivf);
+/* Of the last search or certify call (summed over the sweep's searches); with the filter off everything per call is 0.  mode, rotated,
+ * the caps, copy_bytes and build_ms are the handle's as it stands. */
+typedef struct fsgpu_ivf_filter_stats {
+    uint32_t mode;                /* FSGPU_IVF_LIST_FILTER_* */
+    uint32_t rotated;             /* the handle's copy was made from a rotated filter copy */
+    uint32_t slot_cap, k_cap;     /* 128, 64 */
+    uint64_t scratch_cap;         /* int32 scores resident at once; a call above it runs in ranges */
+    uint64_t copy_bytes;          /* of the ordered copy, padding included */
+    double build_ms;              /* what building it cost on the device */
+    uint64_t queries_filtered;    /* delta >= 0 */
+    uint64_t queries_uncertified; /* delta < 0: the filter-off path inside the same call */
+    uint64_t calls_above_k_cap;   /* 1: k > k_cap sent the whole call down the filter-off path */
+    uint64_t slots_filtered;      /* slots the filter scored and selected from, the overflowed ones included */
+    uint64_t slots_overflowed;    /* more than slot_cap candidates */
+    uint64_t slots_above_scratch; /* slots of certified queries whose tile alone exceeds scratch_cap: scanned whole */
+    uint64_t scratch_ranges;      /* score + selection launch pairs */
+    uint64_t rows_filtered;       /* int8 dots: the sum of the list lengths, dead rows included, over slots_filtered */
+    uint64_t rows_rescored;       /* exact dots made: candidates + the whole lists of every other slot (k > k_cap: rows_scored) */
+    double filter_ms, select_ms, rescore_ms;   /* device time of the score launches, the selections, the exact scan and its merge */
+    uint64_t rows_streamed;       /* rows of the ordered copy the score launches read: a list once per 16 member queries */
+    uint64_t reserved[3];
+} fsgpu_ivf_filter_stats;
+fsgpu_status fsgpu_ivf_last_filter_stats(const fsgpu_ivf *ivf, fsgpu_ivf_filter_stats *out);
 
 /* ---- MRL: truncated scan + full-dimension rescore ---- */
 /* MrlSearchStats (crates/frankensearch-index/src/mrl.rs:122-139). */

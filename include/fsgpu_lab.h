@@ -343,6 +343,50 @@ fsgpu_status fsgpu_lab_wordpiece_encode_stage_ms(fsgpu_wordpiece *tok, const uin
 fsgpu_status fsgpu_lab_knn_update_join(int32_t device, const void *slab, uint32_t slab_f32, uint32_t nrows, uint32_t dim, int32_t hreduce,
                                        uint32_t m, const uint8_t *classes, uint64_t *work, const float *added, const uint32_t *added_rows,
                                        uint32_t n_added);
+/* ---- the IVF index's int8 list filter (fsgpu_ivf_set_list_filter) ---- */
+/* One search of a handle with the filter on, its filter stage through the guard-band harness: the scores, the per-slot results and
+ * the candidates are written by the kernels into buffers that sit between guard bands (a touched band, or a padding entry of the
+ * scores that is not the dead-row sentinel, is FSGPU_ERR_DEVICE).  The call must fit the scratch at once and k <= 64.
+ *   out_ordered      [lists' rows, dimension] int8: the LOGICAL ordered copy, ordered[p] = filter_i8[list_rows[p]] (nullable)
+ *   out_delta        [nq] the bound of each query against the handle's statistics (< 0: uncertified)
+ *   out_ran          0: no query was certified (or no slot exists) and the filter stage did not run; everything below is then unwritten
+ *   out_nslots       the slots: (list, query) pairs of the non-empty probed lists, by list, then by query
+ *   out_slot_query, out_slot_list   [slots]
+ *   out_slot_offset  [slots + 1]: slot s owns out_scores[out_slot_offset[s] .. out_slot_offset[s + 1]), one entry per row of its list in
+ *                    list order: the int32 dot of the query's codes with the row's, INT32_MIN for a dead row
+ *   out_t, out_m, out_count, out_flag   [slots]: the k-th largest score (INT32_MIN when no more than k rows are live), ceil(2 delta),
+ *                    the candidates (never clipped), 1 = overflowed | 2 = uncertified (t, m, count then 0 / INT32_MIN)
+ *   out_cand         [slots, 128]: the first min(count, 128) candidates, local rows ascending; the rest keeps the byte 0xA5
+ * slots_cap / scores_cap: what the caller's arrays hold (nq * nprobe slots and fsgpu_ivf_stats.rows_scored entries always do). */
+typedef struct fsgpu_lab_ivf_filter_stage_args {
+    const float *queries;   /* HOST [nq, query_len] */
+    uint32_t nq, query_len, k, nprobe;
+    uint32_t slots_cap, reserved0;
+    uint64_t scores_cap;
+    int8_t *out_ordered;
+    float *out_delta;
+    uint32_t *out_ran, *out_nslots, *out_slot_query, *out_slot_list;
+    uint64_t *out_slot_offset;
+    int32_t *out_scores, *out_t;
+    int64_t *out_m;
+    uint32_t *out_count, *out_flag, *out_cand;
+} fsgpu_lab_ivf_filter_stage_args;
+fsgpu_status fsgpu_lab_ivf_filter_stage(fsgpu_ivf *ivf, const fsgpu_lab_ivf_filter_stage_args *args);
+/* The scores the filter keeps resident at once (0: the default, 2^26): lets a test cross the range split, and put a tile above the
+ * scratch, with lists of a few hundred rows. */
+fsgpu_status fsgpu_lab_ivf_filter_set_scratch(fsgpu_ivf *ivf, uint64_t entries);
+/* The filter's two host plans (ivf_filter_plan.hpp) on their own; no device is needed.  offsets [nlist + 1] the lists, members
+ * [nlist] the queries that probe each list.
+ * score plan: out_tiles [tiles_cap][8] = ordered_row0, list_pos0, scratch0, len, slot0, nmem, item0, above-the-scratch;
+ *             out_ranges [ranges_cap][7] = tile_first, ntiles, item_first, nitems, slot_first, nslots, entries.
+ * scan plan:  counts, flags [slots] as the selection reports them; out_groups [groups_cap][6] = rows_off, from_cand, n, q0, nq, nblocks.
+ * A capacity too small for the result is FSGPU_ERR_INVALID_CONFIG. */
+fsgpu_status fsgpu_lab_ivf_filter_score_plan(uint32_t nlist, const uint64_t *offsets, const uint32_t *members, uint64_t scratch_cap,
+                                             uint32_t tiles_cap, uint64_t *out_tiles, uint32_t *out_ntiles, uint32_t ranges_cap,
+                                             uint64_t *out_ranges, uint32_t *out_nranges, uint32_t *out_slots);
+fsgpu_status fsgpu_lab_ivf_filter_scan_plan(uint32_t nlist, const uint64_t *offsets, const uint32_t *members, const uint32_t *counts,
+                                            const uint32_t *flags, uint32_t k, uint32_t num_cus, uint32_t groups_cap, uint64_t *out_groups,
+                                            uint32_t *out_ngroups, uint32_t *out_grid_x, uint64_t *out_rows_rescored);
 /* Selects the scan kernel variant (0 = default) — used by bench A/B runs only. */
 fsgpu_status fsgpu_index_set_variant(fsgpu_index *idx, int32_t variant);
 
